@@ -10,9 +10,13 @@ eval pass).  value = nnz(A_low) / t_step summed over the job (SURVEY.md section 
 the CSR rows are sharded over the ranks (strong scaling: the graph is fixed) and the halo
 features are all-gathered over RCCL.  Inputs are resident in HBM before the timed region.
 
-Rank 0 prints one JSON line (contract in the task statement) that also carries
+A plain run sets up, warms up (--warmup steps), times exactly --steps steps (ms_per_step = their wall time / --steps),
+writes the arrays of the last step if --dump-outputs DIR is given, and prints one JSON line from rank 0.  Everything else
+is measured only with --full, and then carried in the same line:
   roofline     -- algorithmic bytes / HIP-event time of the dominant kernel vs the 8 TB/s HBM peak
   cpu_baseline -- the oracle's literal restatement of the reference step on the host cores
+  config       -- eager timing, per-kernel times, the spread over several windows, the parity checks against the CPU
+                  oracle and the side measurements (other forms / node orders of the same step)
 """
 import argparse
 import json
@@ -67,6 +71,13 @@ def parse():
                     help="skip the side measurements of the single-GPU run (literal form, random node order)")
     ap.add_argument("--no-check", action="store_true", help="skip the comparisons with the CPU oracle (eval-mode logits on "
                     "sampled rows; one training-mode step: loss and every parameter gradient)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: eager timing, per-kernel times and "
+                         "roofline, spread over several windows, parity checks against the CPU oracle, side measurements, "
+                         "CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, updated parameters, their "
+                         "gradients) as DIR/<name>.npy in float32")
     ap.add_argument("--dry-run-launch", action="store_true",
                     help="print (as one JSON line) the command and environment bench.py would start its ranks with, then exit; "
                          "{\"launch\": null} when this process would run the benchmark itself")
@@ -221,21 +232,151 @@ def main():
     # mean NLL over the (global) training set; rows a rank does not own have weight 0
     w = T.row_weights(tr_loc, e - b, n_train_total=n_train, device=dev)
     fused_drop = args.dropout_impl == "fused"
-    step = T.TrainStep(model, opt, x, ops, y, w, use_graph=False, fused_dropout=fused_drop)
+    use_graph_steps = 1 if args.steps_per_graph < 0 else args.steps_per_graph
 
     def fence():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---------------- warm-up, then 3 calibration steps with per-launch HIP events on every kernel of the
-    # library (outside the timed region) to find the dominant one ----------------
+    def emit(ms, launch, final_loss, with_cpu, extras=None, check=None, eager_ms=None, breakdown=None, roofline=None):
+        cpu = cpu_baseline(args, model, wl) if (with_cpu and args.full and world == 1 and not args.no_cpu_baseline) else None
+        config = {"workload": f"{args.dataset}-shaped Chung-Lu graph: {n_real} nodes, {adj.nnz // 2} undirected "
+                              f"edges, nnz(A_low)={nnz}, F_in={x.shape[1]}, hidden={args.hidden}, classes={n_cls}; "
+                              f"2-layer {args.method} (variant={args.variant}, structure_info={args.structure_info}, "
+                              f"attention LayerNorm on), dropout {args.dropout} ({'counter-based, masks regenerated in the kernels' if fused_drop else 'F.dropout mask tensors'}), "
+                              f"AdamW ({args.optimizer}); "
+                              "step = fwd + NLL loss + bwd + optimizer update",
+                  "parallelism": f"csr-row-shard x{world}" if world > 1 else "single-gpu",
+                  "node_order": args.node_order, "launch": launch,
+                  "operator_form": "pattern-only P + row scale (shared by A_low and A_low^T)" if ops.implicit
+                  else "explicit (column id, value) CSR + transposed CSR",
+                  "file_edges_per_s": round((adj.nnz // 2) / (ms * 1e-3), 1),
+                  "prep_s": round(prep_s, 1), "final_loss": final_loss, "full": bool(args.full)}
+        if eager_ms is not None:
+            config["eager_ms_per_step"] = round(eager_ms, 4)
+        if breakdown is not None:
+            config["kernel_ms"] = breakdown
+        if shard is not None:
+            config["shard"] = shard
+        config.update(extras or {})
+        config.update(check or {"checked": False})
+        result = {
+            "metric": "edges/sec ACM-GCN fwd+bwd on twitch-gamer",
+            "value": round(nnz / (ms * 1e-3), 1), "unit": "edges/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic", "config": config, "roofline": roofline, "cpu_baseline": cpu,
+        }
+        print(json.dumps(result), flush=True)
+
+    def timed_graph_steps(gstep, spread=None, windows=WINDOWS):
+        """ms per step of `gstep`: `windows` windows of exactly --steps calls, each bracketed by barrier + synchronize and
+        reduced with MAX over the ranks; the MEDIAN window is reported (``spread`` receives min / median / max)."""
+        per_call = int(getattr(gstep, "steps_per_call", 1))      # optimizer steps one call runs (TrainStep(steps_per_graph=...))
+        assert args.steps % per_call == 0
+        for _ in range(max(-(-args.warmup // per_call), 1)):
+            out = gstep()
+        wins = []
+        for _ in range(windows):
+            fence()
+            t = time.perf_counter()
+            for _ in range(args.steps // per_call):                # exactly --steps optimizer steps per window
+                out = gstep()
+            fence()
+            dtg = time.perf_counter() - t
+            if world > 1:
+                tt = torch.tensor([dtg], device=dev, dtype=torch.float64)
+                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                dtg = float(tt.item())
+            wins.append(dtg / args.steps * 1e3)
+        wins.sort()
+        if spread is not None:
+            spread.update({"windows": windows, "steps_per_window": args.steps, "min": round(wins[0], 4),
+                           "median": round(wins[len(wins) // 2], 4), "max": round(wins[-1], 4)})
+        return wins[len(wins) // 2], out
+
+    # A watchdog ends the run if the captured path does not finish: before the headline is measured the run fails (exit
+    # status 1); in the --full measurements after it, rank 0 reports the headline alone instead of hanging the job.
+    import threading
+    state = {"done": False, "headline": None}
+
+    def fallback():
+        if state["done"]:
+            return
+        if state["headline"] is None:
+            sys.stderr.write("bench.py: the hipGraph path did not finish in time\n")
+            sys.stderr.flush()
+            os._exit(1)
+        if rank == 0:
+            emit(*state["headline"], with_cpu=False, extras={"extras_error": "hipGraph measurements after the headline timed out"})
+        os._exit(0)
+
+    def watchdog(seconds):
+        state["done"] = False
+        t = threading.Timer(seconds, fallback)
+        t.daemon = True
+        t.start()
+        return t
+
+    def disarm(t):
+        state["done"] = True
+        t.cancel()
+
+    # ---------------- headline: --warmup steps, then exactly --steps timed steps as replays of one captured HIP graph
+    # (collectives included when sharded), or as eager launches with --graph 0 or where the capture is refused ----------------
+    graph_ok, gstep, step = False, None, None
+    launch = "eager launches"
+    if use_graph:
+        wd = watchdog(120.0 + 0.05 * (args.steps + args.warmup))
+        try:
+            # one optimizer step per captured graph.  (--steps-per-graph K captures K consecutive steps in one graph: measured
+            # SLOWER on the same box, 0.2842 ms against 0.2785 / 0.2798 at K = 5 / 1 -- back-to-back replays of a small graph
+            # already overlap the next launch with the running one; profiles/r04_steps_per_graph.txt)
+            gstep = T.TrainStep(model, opt, x, ops, y, w, use_graph=True, fused_dropout=fused_drop,
+                                steps_per_graph=use_graph_steps)
+            ms_per_step, loss = timed_graph_steps(gstep, windows=1)
+            launch = f"hipGraph replay of the captured step ({use_graph_steps} consecutive steps per graph)"
+            graph_ok = True
+        except Exception as exc:                      # capture refused: time eager launches instead
+            sys.stderr.write(f"bench.py: hipGraph capture failed ({exc!r}); reporting eager launches\n")
+            gstep = None
+        disarm(wd)
+    if not graph_ok:
+        step = T.TrainStep(model, opt, x, ops, y, w, use_graph=False, fused_dropout=fused_drop)
+        ms_per_step, loss = timed_graph_steps(step, windows=1)
+    timed = gstep if graph_ok else step
+    if world > 1:                                  # each rank holds the loss over its own rows
+        loss = loss.detach().clone()
+        dist.all_reduce(loss)
+    final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model)
+    state["headline"] = (ms_per_step, launch, final_loss)
+
+    # which form of the step was timed: with the first layer's input aggregation of step t + 1 inside that layer's backward
+    # of step t (train.TrainStep's default where it qualifies; ACM_TUNING=pipeline=0 switches it off) or without
+    extras = {"input_pipeline": timed.pipe is not None}
+    if not args.full:
+        if rank == 0:
+            emit(ms_per_step, launch, final_loss, with_cpu=False, extras=extras)
+        if dist.is_initialized():
+            if world > 1:
+                dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ======================== --full: everything beyond the headline figure ========================
+    # ---------------- eager launches: warm-up, then 3 calibration steps with per-launch HIP events on every kernel of
+    # the library to find the dominant one, then --steps timed eager steps ----------------
+    if step is None:
+        step = T.TrainStep(model, opt, x, ops, y, w, use_graph=False, fused_dropout=fused_drop)
     for _ in range(max(args.warmup, 1)):
-        loss = step()
+        step()
     timer = AF.KernelTimer()
     AF.set_kernel_timer(timer)
     for _ in range(3):
-        loss = step()
+        step()
     warm = timer.summary()
     AF.set_kernel_timer(None)
     # row-sharded runs: what each rank spent per step in the library's kernels and in the collectives (HIP events of the
@@ -254,13 +395,12 @@ def main():
         shard["per_rank"] = per_rank
     warm = {k: v for k, v in warm.items() if not k.startswith(("all_gather", "all_reduce"))}
     dominant = max(warm, key=lambda k: warm[k][1])
-    # ---------------- timed region ----------------
     focus = AF.KernelTimer(only=dominant)
     AF.set_kernel_timer(focus)
     fence()
     t1 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        step()
     fence()
     dt = time.perf_counter() - t1
     AF.set_kernel_timer(None)
@@ -269,8 +409,6 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     eager_ms = dt / args.steps * 1e3
-    ms_per_step = eager_ms
-    eager_loss = float(loss.item())
 
     # ---------------- roofline of the dominant kernel (from the eager timed region) ----------------
     roofline, breakdown = None, None
@@ -301,95 +439,16 @@ def main():
                     "algorithmic_bytes": alg}
         breakdown = {k: round(v[1] / v[0], 4) for k, v in sorted(warm.items(), key=lambda kv: -kv[1][1])}
 
-    def emit(ms, launch, final_loss, with_cpu, extras=None, check=None):
-        cpu = cpu_baseline(args, model, wl) if (with_cpu and world == 1 and not args.no_cpu_baseline) else None
-        config = {"workload": f"{args.dataset}-shaped Chung-Lu graph: {n_real} nodes, {adj.nnz // 2} undirected "
-                              f"edges, nnz(A_low)={nnz}, F_in={x.shape[1]}, hidden={args.hidden}, classes={n_cls}; "
-                              f"2-layer {args.method} (variant={args.variant}, structure_info={args.structure_info}, "
-                              f"attention LayerNorm on), dropout {args.dropout} ({'counter-based, masks regenerated in the kernels' if fused_drop else 'F.dropout mask tensors'}), "
-                              f"AdamW ({args.optimizer}); "
-                              "step = fwd + NLL loss + bwd + optimizer update",
-                  "parallelism": f"csr-row-shard x{world}" if world > 1 else "single-gpu",
-                  "node_order": args.node_order, "launch": launch,
-                  "operator_form": "pattern-only P + row scale (shared by A_low and A_low^T)" if ops.implicit
-                  else "explicit (column id, value) CSR + transposed CSR",
-                  "eager_ms_per_step": round(eager_ms, 4),
-                  "file_edges_per_s": round((adj.nnz // 2) / (ms * 1e-3), 1),
-                  "kernel_ms": breakdown, "prep_s": round(prep_s, 1), "final_loss": final_loss}
-        if shard is not None:
-            config["shard"] = shard
-        config.update(extras or {})
-        config.update(check or {"checked": False})
-        result = {
-            "metric": "edges/sec ACM-GCN fwd+bwd on twitch-gamer",
-            "value": round(nnz / (ms * 1e-3), 1), "unit": "edges/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic", "config": config, "roofline": roofline, "cpu_baseline": cpu,
-        }
-        print(json.dumps(result), flush=True)
-
-    def timed_graph_steps(gstep, spread=None):
-        """ms per step of `gstep`: WINDOWS windows of exactly --steps calls, each bracketed by barrier + synchronize and
-        reduced with MAX over the ranks; the MEDIAN window is reported (``spread`` receives min / median / max)."""
-        per_call = int(getattr(gstep, "steps_per_call", 1))      # optimizer steps one call runs (TrainStep(steps_per_graph=...))
-        assert args.steps % per_call == 0
-        for _ in range(max(-(-args.warmup // per_call), 1)):
-            out = gstep()
-        wins = []
-        for _ in range(WINDOWS):
-            fence()
-            t = time.perf_counter()
-            for _ in range(args.steps // per_call):                # exactly --steps optimizer steps per window
-                out = gstep()
-            fence()
-            dtg = time.perf_counter() - t
-            if world > 1:
-                tt = torch.tensor([dtg], device=dev, dtype=torch.float64)
-                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-                dtg = float(tt.item())
-            wins.append(dtg / args.steps * 1e3)
-        wins.sort()
-        if spread is not None:
-            spread.update({"windows": WINDOWS, "steps_per_window": args.steps, "min": round(wins[0], 4),
-                           "median": round(wins[len(wins) // 2], 4), "max": round(wins[-1], 4)})
-        return wins[len(wins) // 2], out
-
-    # ---------------- second timed region: the same K steps as replays of one captured HIP graph ----------------
-    # (collectives included when sharded).  A watchdog makes the run fall back to the eager measurement if the
-    # captured path does not finish: rank 0 then reports the eager numbers instead of hanging the job.
-    graph_ok = False
+    # ---------------- the captured step again: the spread over WINDOWS windows of --steps replays, and the dominant
+    # kernel's duration INSIDE the replayed graph (the number that belongs next to a hipGraph-replay ms_per_step): a second
+    # capture of the same step with external HIP events around that kernel, replayed after -- never inside -- the timed
+    # windows.  Falls back to the eager-region figure (and says so) where the runtime refuses event-record nodes.
     spread = {}
-    if use_graph:
-        import threading
-        state = {"done": False}
-
-        def fallback():
-            if state["done"]:
-                return
-            if rank == 0:
-                emit(eager_ms, "eager launches (hipGraph path timed out)", eager_loss, with_cpu=False)
-            os._exit(0)
-
-        timer_t = threading.Timer(120.0, fallback)
-        timer_t.daemon = True
-        timer_t.start()
-        try:
-            # one optimizer step per captured graph.  (--steps-per-graph K captures K consecutive steps in one graph: measured
-            # SLOWER on the same box, 0.2842 ms against 0.2785 / 0.2798 at K = 5 / 1 -- back-to-back replays of a small graph
-            # already overlap the next launch with the running one; profiles/r04_steps_per_graph.txt)
-            spg = 1 if args.steps_per_graph < 0 else args.steps_per_graph
-            gstep = T.TrainStep(model, opt, x, ops, y, w, use_graph=True, fused_dropout=fused_drop, steps_per_graph=spg)
-            ms_per_step, loss = timed_graph_steps(gstep, spread)
-            spread["steps_per_graph"] = spg
-            graph_ok = True
-        except Exception as exc:                      # capture refused: keep the eager measurement
-            sys.stderr.write(f"bench.py: hipGraph capture failed ({exc!r}); reporting eager launches\n")
-        # the dominant kernel's duration INSIDE the replayed graph (the number that belongs next to a hipGraph-replay
-        # ms_per_step): a second capture of the same step with external HIP events around that kernel, replayed after --
-        # never inside -- the timed windows.  Falls back to the eager-region figure (and says so) where the runtime
-        # refuses event-record nodes.
-        if graph_ok and rank == 0 and roofline is not None and world == 1:
+    if graph_ok:
+        wd = watchdog(120.0 + 0.05 * WINDOWS * (args.steps + args.warmup))
+        timed_graph_steps(gstep, spread)
+        spread["steps_per_graph"] = use_graph_steps
+        if rank == 0 and roofline is not None and world == 1:
             try:
                 got = replayed_kernel_ms(dominant, lambda: T.TrainStep(model, opt, x, ops, y, w, use_graph=True,
                                                                        fused_dropout=fused_drop, steps_per_graph=1))
@@ -402,12 +461,7 @@ def main():
                     roofline["frac"] = round(roofline["achieved"] / HBM_PEAK_GBS, 4)
             except Exception as exc:
                 sys.stderr.write(f"bench.py: in-graph kernel timing unavailable ({exc!r}); roofline.avg_ms is the eager figure\n")
-        state["done"] = True
-        timer_t.cancel()
-    if world > 1:                                  # each rank holds the loss over its own rows
-        loss = loss.detach().clone()
-        dist.all_reduce(loss)
-    final_loss = float(loss.item())
+        disarm(wd)
 
     # ---------------- parity of what was just timed: eval-mode logits of the trained model against the CPU oracle
     # on sampled rows (outside the timed regions; rank 0, its own rows) ----------------
@@ -424,28 +478,50 @@ def main():
 
     # ---------------- side measurements (single GPU): the same step in the literal project-then-aggregate form, and
     # on the generator's random node ids (no degree relabelling) -- SURVEY.md section 7 asks for both ----------------
-    extras = {}
     if world == 1 and use_graph and graph_ok and not args.no_extras:
         try:
-            extras = side_measurements(args, timed_graph_steps, model, opt, x, ops, y, w, fused_drop, dev, (tr, va, te))
+            extras.update(side_measurements(args, timed_graph_steps, model, opt, x, ops, y, w, fused_drop, dev, (tr, va, te)))
         except Exception as exc:
-            extras = {"extras_error": repr(exc)}
-
-    # which form of the step was timed: with the first layer's input aggregation of step t + 1 inside that layer's backward
-    # of step t (train.TrainStep's default where it qualifies; ACM_TUNING=pipeline=0 switches it off) or without
-    extras["input_pipeline"] = step.pipe is not None
+            extras["extras_error"] = repr(exc)
     if spread:
         extras["ms_per_step_windows"] = spread
     if rank == 0:
-        emit(ms_per_step, (f"hipGraph replay of the captured step ({spread.get('steps_per_graph', 1)} consecutive steps per graph)"
-                           if graph_ok else "eager launches"), final_loss,
-             with_cpu=True, extras=extras, check=check)
+        emit(ms_per_step, launch, final_loss, with_cpu=True, extras=extras, check=check, eager_ms=eager_ms,
+             breakdown=breakdown, roofline=roofline)
     if dist.is_initialized():
         if world > 1:
             dist.barrier()
         dist.destroy_process_group()
     if check is not None and rank == 0 and not check["checked"]:
         sys.exit(1)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loss, model):
+    """What a caller of the timed step receives after its last call, as <out_dir>/<name>.npy in float32: the loss, every
+    parameter as the optimizer update left it and the gradient it was updated with (``grad.<name>``).  Should they exceed
+    DUMP_LIMIT_BYTES in all, the arrays above 1 MB keep a fixed, seeded sample of their rows (the row numbers are written
+    as ``<name>.rows.npy``, float64)."""
+    import torch
+    arrays = {"loss": loss.detach().reshape(-1)}
+    for name, p in model.named_parameters():
+        arrays[f"param.{name}"] = p.detach()
+        if p.grad is not None:
+            arrays[f"grad.{name}"] = p.grad.detach()
+    torch.cuda.synchronize()
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = 0.9 * DUMP_LIMIT_BYTES / total
+        for k in [k for k, a in arrays.items() if a.nbytes > (1 << 20) and a.ndim >= 1 and a.shape[0] > 1]:
+            a = arrays[k]
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=max(1, int(a.shape[0] * keep)), replace=False))
+            arrays[k], arrays[k + ".rows"] = a[rows], rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float64 if k.endswith(".rows") else np.float32))
 
 
 def replayed_kernel_ms(label, make_step, replays=20):

@@ -32,7 +32,7 @@ for NAME in $PASSES; do
     write) CNT="WRITE_SIZE";;
   esac
   rm -rf /tmp/prof_pmc
-  CMD=${PMC_CMD:-"python $REPO/bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-extras --no-check"}
+  CMD=${PMC_CMD:-"python $REPO/bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-extras --no-check"}
   (cd $REPO && env "$@" timeout 300 rocprofv3 --pmc $CNT --kernel-trace -d /tmp/prof_pmc -o pmc -- $CMD > /dev/null 2> $OUT/${PREFIX}_$NAME.err)
   DB=$(find /tmp/prof_pmc -name "*.db" | head -1)
   [ -n "$DB" ] && python $REPO/scripts/rocpd_pmc_summary.py $DB 2>> $OUT/${PREFIX}_$NAME.err | grep -E "^kernel|$MATCH" > $OUT/${PREFIX}_$NAME.csv
