@@ -1439,6 +1439,37 @@ def test_small_graph_step_host_path_equals_the_general_path(model_type, s, varia
     assert "optimizer" in SmallPlan.why_not(ma, xs, ops, torch.optim.Adam(ma.parameters()))
 
 
+def test_small_graph_step_envelope_ends_at_16384_rows_and_8_classes(monkeypatch):
+    """small.SmallPlan.why_not at the edges of the envelope (MAX_ROWS, MAX_CLASSES): a graph of 16 384 nodes with 8 classes
+    takes the fused step, 16 385 nodes or 9 classes are declined with the reason, and TrainStep then stays on the general
+    path and reports that reason."""
+    import scipy.sparse as sp
+    fake_lib.install(monkeypatch)
+    from acm_gnn_amd import GCN, FusedAdam, SparseFeatures, data as D, train as T
+    from acm_gnn_amd.distributed import make_sharded_operators
+    from acm_gnn_amd.small import MAX_CLASSES, MAX_ROWS, SmallPlan
+    assert (MAX_ROWS, MAX_CLASSES) == (16384, 8)
+
+    def why(n, classes):
+        path = sp.diags([np.ones(n - 1, np.float32)], [1], shape=(n, n), format="csr")
+        low, deg = D.build_filters(((path + path.T) > 0).astype(np.float32).tocsr())
+        ops = make_sharded_operators(low, deg, torch.device("cpu"))
+        assert ops.implicit
+        xs = SparseFeatures.from_scipy(sp.csr_matrix((np.ones(n, np.float32), (np.arange(n), np.arange(n) % 16)), shape=(n, 16)), "cpu")
+        torch.manual_seed(0)
+        model = GCN(16, 64, classes, 2, n, 0.0, "acmgcn", 0)
+        opt = FusedAdam(model.parameters(), lr=0.01)
+        reason = SmallPlan.why_not(model, xs, ops, opt)
+        y = torch.arange(n) % classes
+        step = T.TrainStep(model, opt, xs, ops, y, T.row_weights(torch.arange(0, n, 2), n))
+        assert (step.small is None) == (reason is not None) and step.small_refused == reason
+        return reason
+
+    assert why(16384, 8) is None
+    assert why(16385, 8) == "16385 rows (<= 16384)"
+    assert why(16384, 9) == "9 classes (<= 8)"
+
+
 def test_train_step_keeps_the_operators_it_builds_from_adjacency_tensors(monkeypatch):
     """a caller that hands TrainStep the reference's TENSORS (ACM-Pytorch dialect: dense adj_low, sparse
     adj_high / adj_low_unnormalized, dense bag-of-words features; ACM-Pytorch/train.py:95-139) gets the operator set built
