@@ -19,7 +19,7 @@ Per layer the only data-path collectives are
     backward: all-gather of the row-local gradients [G_L | G_H] (and D*G_S)
               + one all-reduce of the (tiny) replicated-parameter gradients
 
-(functional.AcmConvFunction issues them through ``FilterOperators.group``).
+(the layer Functions behind functional.acm_conv issue them through ``FilterOperators.group``).
 The reference is single-process (no collective call sites), so
 this module has no reference counterpart; its contract is "N-rank result ==
 1-rank result", tested with world_size 2 and 4 on gloo (CPU) with the kernel launches

@@ -1411,6 +1411,82 @@ def _narrow_tables(n, fb, f, dev, packed):
     return torch.empty(n, 2 * fb, dtype=_F32, device=dev), None
 
 
+def _set_post(st, post_relu, post_scale, post_drop, row_offset):
+    """The fused post-op fields of a kernel's struct: relu(out) * post_scale, or the counter-based dropout ``post_drop``."""
+    st.post_relu = int(post_relu)
+    if post_scale is not None:
+        st.post_scale, st.ld_post_scale = post_scale.data_ptr(), post_scale.stride(0)
+    spec = _drop_spec(post_drop, row_offset)
+    if spec is not None:
+        st.post_drop = spec
+
+
+def _head_params(cfg, vecs, att_mix, lnw, lnb):
+    """The head's parameters of a layer of cfg.n_channels = k channels: (att_vec list, LayerNorm weights, LayerNorm biases,
+    the k x k att_mix), each float32 and contiguous; ``vecs`` / ``lnw`` / ``lnb`` list the four channels' tensors."""
+    k = cfg.n_channels
+    vecs = [_as_f32c(t, "att_vec") for t in vecs[:k]]
+    lnw = [_as_f32c(t, "ln") for t in lnw[:k]] if cfg.layernorm else []
+    lnb = [_as_f32c(t, "ln") for t in lnb[:k]] if cfg.layernorm else []
+    mix = _as_f32c(att_mix, "att_vec")
+    if tuple(mix.shape) != (k, k):
+        raise RuntimeError(f"att_vec is {tuple(mix.shape)} but the layer mixes {k} channels "
+                           "(structure_info is only valid with acmgcnp/acmgcnpp)")
+    return vecs, lnw, lnb, mix
+
+
+def _workspace(lib, dev, query, *args):
+    """The float32 workspace an entry point needs: ``query`` names its acm_*_workspace_bytes companion, ``args`` its shape."""
+    nbytes = C.c_size_t()
+    _lib.check(getattr(lib, query)(*args, C.byref(nbytes)), query)
+    return torch.empty(max(nbytes.value // 4, 1), dtype=_F32, device=dev)
+
+
+def _reduce_replicated(flat, ops, defer):
+    """Row-sharded: sum the row-shard partials of the replicated parameters' gradients, ONE all-reduce of the layer's flat
+    gradient buffer (under a deferral list: after the step's single flush, whose second phases write those partials)."""
+    if not ops.sharded:
+        return
+    if defer is not None:
+        defer.allreduce(flat, ops.group)
+    else:
+        import torch.distributed as dist
+        dist.all_reduce(flat, group=ops.group)
+
+
+def _struc_grad(ops, cfg, gs):
+    """d struc_low = A_low^T (D G_S) - G_S (pattern-only: P G_S - G_S, G_S unscaled) from the row-local backward's G_S: one
+    F-wide transposed product that subtracts the self term in its epilogue, after the all-gather of G_S when row-sharded."""
+    n, f = gs.shape
+    gsg = _gather_rows(ops, gs)
+    low_t = ops.low_t
+    d_struc = torch.empty(n, f, dtype=_F32, device=gs.device)
+    ws = low_t.workspace(f)
+    o = _lib.SpmmOpts()
+    o.sub, o.ld_sub = gs.data_ptr(), gs.stride(0)
+    o.sub_scale = None if ops.implicit else ops.inv_deg.data_ptr()
+    if cfg.gather_bf16 and 8 < f <= 64 and f % 2 == 0:       # bf16 gathered operand (the self term stays fp32)
+        gsg = cast_bf16(gsg)
+        o.g_bf16 = 1
+    with _device_ctx(gs.device), _Timed(f"spmm_sub/{f}"):
+        st = _lib.load().acm_spmm_ex(low_t.handle, _vp(gsg), gsg.stride(0), f, _vp(d_struc), d_struc.stride(0),
+                                     C.byref(o), _vp(ws), ws.numel() * 4, _stream())
+    _lib.check(st, "acm_spmm_ex")
+    return d_struc
+
+
+_NONE4 = (None,) * 4
+_NO_GRADS = (None,) * 28          # one per argument of the layer Functions (see acm_conv)
+
+
+def _grads(d_x, d_w3, d_vec, d_struc, d_mix, d_lnw, d_lnb):
+    """The gradient tuple of the layer Functions' argument list; ``d_vec`` / ``d_lnw`` / ``d_lnb`` hold the k channels' (no
+    LayerNorm: empty).  The gradients must be view objects of THIS call (_flat_views)."""
+    pad = (None,) * (4 - len(d_vec))
+    return (d_x, *d_w3, *d_vec, *pad, d_struc, d_mix, *((*d_lnw, *pad) if d_lnw else _NONE4),
+            *((*d_lnb, *pad) if d_lnb else _NONE4), *_NO_GRADS[:10])
+
+
 def _k3_setup(cfg, ops, k, f, n, dev, f_in_w, pre, zi, vecs, lnw, lnb, mix, grad_out, post_relu, post_scale, post_drop,
               fb=None):
     """Buffers and acm_conv_bwd_local_t of the row-local backward of one layer: G tables, dZ, the flat buffer every
@@ -1449,383 +1525,605 @@ def _k3_setup(cfg, ops, k, f, n, dev, f_in_w, pre, zi, vecs, lnw, lnb, mix, grad
         q.g_struc, q.ld_g_struc = gs.data_ptr(), gs.stride(0)
     q.d_att_vec, q.d_ln_weight, q.d_ln_bias = _ptr_array(d_vec), _ptr_array(d_lnw), _ptr_array(d_lnb)
     q.d_att_mix = d_mix.data_ptr()
-    q.post_relu = int(post_relu)
-    if post_scale is not None:
-        q.post_scale, q.ld_post_scale = post_scale.data_ptr(), post_scale.stride(0)
-    spec = _drop_spec(post_drop, ops.row_offset)
-    if spec is not None:
-        q.post_drop = spec
+    _set_post(q, post_relu, post_scale, post_drop, ops.row_offset)
     return dict(q=q, g=g, dz=dz, gs=gs, flat=flat, nw=nw, d_vec=d_vec, d_lnw=d_lnw, d_lnb=d_lnb, d_mix=d_mix,
                 general=general, ones=ones, grad_out=grad_out)
 
 
-class AcmConvFunction(torch.autograd.Function):
-    """out, att = ACM layer(x; parameters) over the operators in ``ops``.
+# --------------------------------------------------------------------------
+# route selection: one autograd Function per execution form
+# --------------------------------------------------------------------------
+def _agg_first_shape(cfg, f_in, f_out):
+    """Aggregate-first, A (X W) = (A X) W on the f_pad <= 16 kernels: legal without a ReLU between projection and filter, worth
+    it when F_in < F."""
+    return not cfg.relu_before and f_in <= 16 and f_in < f_out and f_out <= 64
 
-    forward : K1 acm_gemm (X [W_L|W_H|W_I]) -> K2 acm_conv_fwd
-    backward: K3 acm_conv_bwd_local -> K4 acm_conv_bwd_spmm -> K5 acm_gemm (X^T dZ, dZ Wcat^T)
-    """
+
+def _acmii_shape(cfg, f_in, f_out):
+    """ACMII first layer with a narrow input: gather the input rows and recompute relu(x_j [W_L | W_H]) per edge on the matrix
+    pipe instead of gathering the 2F-wide projected rows (acm_conv_acmii_fwd = K1 + K2)."""
+    return cfg.relu_before and not cfg.relu_after and cfg.relu_mlp and f_out == 64 and f_in <= 8
+
+
+def _conv_route(x, ops, cfg, f_in, f_out, post_scale=None, call=None, tail_layer=False):
+    """The execution form of one ACM layer: "wide" (_AcmAggWide), "agg" (_AcmAggFirst), "acmii" (_AcmAcmii) or "literal"
+    (_AcmLiteral).  Aggregate-first needs an input that takes no gradient (its backward runs no SpMM); the k-hop chain, general
+    operator pairs and CSR features take the literal form; tuning rewrites bits 1 / 2 switch the two narrow rewrites off."""
+    if agg_wide_supported(x, ops, cfg, f_in, f_out, post_scale, call, tail_layer):
+        return "wide"
+    hops = int(getattr(ops, "hops", 1))
+    if isinstance(x, SparseFeatures) or getattr(ops, "general", False) or hops > 1:
+        return "literal"
+    rewrites = tuning.HOST.rewrites
+    if (_agg_first_shape(cfg, f_in, f_out) and not (isinstance(x, torch.Tensor) and x.requires_grad)
+            and rewrites & tuning.REWRITE_AGG_FIRST):
+        return "agg"
+    if _acmii_shape(cfg, f_in, f_out) and hops == 1 and rewrites & tuning.REWRITE_ACMII_RECOMPUTE:
+        return "acmii"
+    return "literal"
+
+
+def _conv_prologue(ctx, x, w_low, ops, post_relu, post_scale, post_drop, call, in_drop):
+    """What the narrow forms (aggregate-first, ACMII, literal) check and record first; returns the input as float32.
+
+    ``call``: the model call's context (deferral list, loss-tail request, input pipeline, projection hand-off);
+    ``in_drop = (p, tag, DropoutState)``: the caller's INPUT dropout (models.py:54), left to this layer -- the forms that gather
+    X apply it first, the literal one inside the dense projection (acm_gemm_drop) where it can, forward and backward."""
+    ctx.set_materialize_grads(False)          # no zero-filled gradient for the (non-differentiable) att output
+    ctx.call = _call_or_ambient(call)
+    ctx.in_drop = in_drop if (in_drop is not None and in_drop[0] > 0) else None
+    sparse_x = isinstance(x, SparseFeatures)
+    if not sparse_x:
+        x = _as_f32c(x, "input")
+    n, f = x.shape[0], w_low.shape[1]
+    if post_scale is not None:
+        post_scale = _as_f32c(post_scale, "post_scale")
+        if tuple(post_scale.shape) != (n, f):
+            raise ValueError(f"post_scale must be [{n}, {f}]")
+    ctx.post_relu, ctx.post_scale = bool(post_relu), post_scale
+    ctx.post_drop = post_drop if (post_drop is not None and post_drop[0] > 0) else None
+    if n != ops.n_local:
+        raise ValueError(f"input has {n} rows but the graph operator has {ops.n_local}")
+    ctx.x_width = x.shape[1]
+    if x.shape[1] != w_low.shape[0] and (sparse_x or x.shape[1] < w_low.shape[0]):   # (dropout(..., pad_to=...): zero columns)
+        raise ValueError(f"input has {x.shape[1]} columns but the weights have {w_low.shape[0]} rows")
+    return x
+
+
+def _gathered_input(ctx, x, ops, f_in, f, fp, agg_holder, pregathered, agg_first):
+    """The input of the two forms that gather X itself (aggregate-first, ACMII recompute): the caller's input dropout applied,
+    X zero-padded to ``fp`` columns, P = A_low X when it is at hand already and the gathered rows.  Returns
+    (x, xpad, xg, agg_given, agg_holder); sets ctx.pipe.
+
+    ``agg_holder``: layers.GraphConvolution's {"agg": P-or-None} of a pass over a static input; ``pregathered``: every node's
+    (dropped) input from the caller (models.GCN, row-sharded); a training step's InputPipeline (call.pipe) hands an
+    aggregate-first layer the P that the previous step's backward gathered."""
+    n, call = x.shape[0], ctx.call
+    if ctx.in_drop is not None:               # these forms gather the input itself: they need the dropped rows
+        x = _drop_now(x, _drop_spec(ctx.in_drop, ops.row_offset))
+    # (the pipeline's table is refilled in place through raw pointers -- no version bump: never through the holder;
+    #  ACMII recomputes per edge from the gathered rows: there is no P to keep)
+    if agg_holder is not None and (ops.sharded or call.pipe is not None or not agg_first or ctx.in_drop is not None):
+        agg_holder = None
+    if x.shape[1] == fp:
+        xpad = x
+    else:                                     # the zero-padded copy of a static input is kept with its P
+        xpad = agg_holder.get("xpad") if agg_holder is not None else None
+        if xpad is None or tuple(xpad.shape) != (n, fp):
+            xpad = torch.nn.functional.pad(x[:, :f_in], (0, fp - f_in))
+            if agg_holder is not None:
+                agg_holder["xpad"] = xpad
+    agg_given = agg_holder.get("agg") if agg_holder is not None else None
+    if agg_given is not None and tuple(agg_given.shape) != (n, fp):
+        agg_given = None
+    # a training loop's input pipeline (InputPipeline): P for this step came out of the previous step's backward
+    pipe = call.pipe
+    ctx.pipe = None
+    if (pipe is not None and pipe.primed and agg_first and fp == 8 and f == 64 and ops is pipe.ops
+            and xpad.data_ptr() == pipe.local_table().data_ptr() and agg_holder is None):   # (only a training step carries a pipe)
+        agg_given = pipe.agg()
+        ctx.pipe = pipe
+        pipe.adopted = True               # the loop may refill the table: this forward leaves its copies in ``saved``
+    if agg_given is not None:
+        xg = xpad                             # not read: P = A_low X comes from the holder
+    elif (pregathered is not None and pregathered[0].data_ptr() == xpad.data_ptr()
+            and pregathered[1].shape[1] == fp and pregathered[1].shape[0] == ops.n_gathered):
+        xg = pregathered[1]                   # the caller already holds every node's (dropped) input
+    else:
+        xg = _gather_rows(ops, xpad)
+    return x, xpad, xg, agg_given, agg_holder
+
+
+def _struc_rows(ops, struc_low, n):
+    """The structure channel's parameter rows of this process, and of every node (all-gathered when row-sharded)."""
+    if ops.deg is None:
+        raise RuntimeError("structure_info=1 needs adj_low_unnormalized")
+    s_local = _as_f32c(struc_low, "struc_low")
+    if s_local.shape[0] != n:
+        raise ValueError("struc_low rows != local nodes")
+    return s_local, _gather_rows(ops, s_local)
+
+
+class _AcmAggFirst(torch.autograd.Function):
+    """out, att = ACM layer in the aggregate-first form for F_in <= 16 (_agg_first_shape): the input takes no gradient.
+
+    forward : acm_conv_agg_fwd (P = A_low X, the three projections of P / X and the head in one kernel; the row-local stage only
+              when P is given) [-> the next layer's narrow projection in its epilogue]
+    backward: acm_conv_agg_bwd (one row-local kernel, no SpMM for the three filterbank channels) [-> spmm_sub for d struc_low]
+
+    Argument list (shared by the four layer Functions): x, the three weights, att_vec_low / high / mlp, att_struc_low,
+    struc_low, att_vec (the k x k mix), the four LayerNorm weights and biases, ops, cfg, post_relu, post_scale, post_drop, call,
+    tail_layer, agg_holder, in_drop, pregathered -- see acm_conv."""
 
     @staticmethod
-    def forward(ctx, x, w_low, w_high, w_mlp, v_low, v_high, v_mlp, v_struc, struc_low, att_mix,
-                lnw_low, lnw_high, lnw_mlp, lnw_struc, lnb_low, lnb_high, lnb_mlp, lnb_struc, ops, cfg,
-                post_relu=False, post_scale=None, post_drop=None, call=None, tail_layer=False, agg_holder=None,
-                in_drop=None):
+    def forward(ctx, x, w_low, w_high, w_mlp, v_low, v_high, v_mlp, v_struc, struc_low, att_mix, lnw_low, lnw_high, lnw_mlp,
+                lnw_struc, lnb_low, lnb_high, lnb_mlp, lnb_struc, ops, cfg, post_relu, post_scale, post_drop, call, tail_layer,
+                agg_holder, in_drop, pregathered):
         lib = _lib.load()
-        ctx.set_materialize_grads(False)          # no zero-filled gradient for the (non-differentiable) att output
-        # the model call's context (deferral list, loss-tail request, input pipeline, projection hand-off); ``tail_layer``:
-        # the caller is an output layer without post-op working in the operator's numbering (it may take call.tail);
-        # ``agg_holder``: layers.GraphConvolution's {"agg": P-or-None} of an evaluation pass over a static input
-        # ``in_drop = (p, tag, DropoutState)``: the caller's INPUT dropout (models.py:54), left to this layer: the dense
-        # projection applies it while staging X (acm_gemm_drop), forward and backward, and X itself is saved un-dropped
-        call = ctx.call = _call_or_ambient(call)
-        ctx.in_drop = in_drop if (in_drop is not None and in_drop[0] > 0) else None
-        sparse_x = isinstance(x, SparseFeatures)
-        if not sparse_x:
-            x = _as_f32c(x, "input")
-        dev = x.device
-        n, f = x.shape[0], w_low.shape[1]
+        x = _conv_prologue(ctx, x, w_low, ops, post_relu, post_scale, post_drop, call, in_drop)
+        call = ctx.call
+        ctx.agg_first = True                      # what a following layer's lazy input gradient looks for (_AcmLiteral)
+        dev, n = x.device, x.shape[0]
+        f_in, f = w_low.shape
         k = cfg.n_channels
-        if post_scale is not None:
-            post_scale = _as_f32c(post_scale, "post_scale")
-            if tuple(post_scale.shape) != (n, f):
-                raise ValueError(f"post_scale must be [{n}, {f}]")
-        ctx.post_relu, ctx.post_scale = bool(post_relu), post_scale
-        ctx.post_drop = post_drop if (post_drop is not None and post_drop[0] > 0) else None
+        four = k == 4
+        fp = 4 if f_in <= 4 else (8 if f_in <= 8 else 16)
+        x, xpad, xg, agg_given, agg_holder = _gathered_input(ctx, x, ops, f_in, f, fp, agg_holder, pregathered, True)
+        wl, wh, wm = (_as_f32c(t, "weight") for t in (w_low, w_high, w_mlp))
+        if four:
+            s_local, s_gath = _struc_rows(ops, struc_low, n)
+        vecs, lnw, lnb, mix = _head_params(cfg, (v_low, v_high, v_mlp, v_struc), att_mix, (lnw_low, lnw_high, lnw_mlp, lnw_struc),
+                                           (lnb_low, lnb_high, lnb_mlp, lnb_struc))
+        out = torch.empty(n, f, dtype=_F32, device=dev)
+        att = torch.empty(n, 4, dtype=_F32, device=dev)
+        p = _lib.ConvAggFwd()
+        p.f_in, p.f_pad, p.f_out = f_in, fp, f
+        p.relu_after, p.relu_mlp, p.layernorm, p.scale = int(cfg.relu_after), int(cfg.relu_mlp), int(cfg.layernorm), cfg.scale
+        p.xg, p.ld_xg = xg.data_ptr(), xg.stride(0)
+        p.xs, p.ld_xs = xpad.data_ptr(), xpad.stride(0)
+        p.w_low, p.w_high, p.w_mlp, p.ld_w = wl.data_ptr(), wh.data_ptr(), wm.data_ptr(), f
+        p.att_vec, p.ln_weight, p.ln_bias = _ptr_array(vecs), _ptr_array(lnw), _ptr_array(lnb)
+        p.att_mix = mix.data_ptr()
+        agg = agg_given if agg_given is not None else torch.empty(n, fp, dtype=_F32, device=dev)
+        p.agg_given = int(agg_given is not None)
+        refill = False
+        if ctx.pipe is not None:                  # the backward's operands: copies the row-local kernel leaves
+            p.agg_copy, p.ld_agg_copy = ctx.pipe.saved[1].data_ptr(), ctx.pipe.saved[1].stride(0)
+            p.xs_copy, p.ld_xs_copy = ctx.pipe.saved[0].data_ptr(), ctx.pipe.saved[0].stride(0)
+            # ... and (one device: the table IS this rank's rows) it refills the table with dropout_{t+1}(x) over the rows
+            # it has just copied: make_next()'s acm_dropout launch is gone
+            refill = ctx.pipe.refill_spec(p)
+        p.out, p.ld_out = out.data_ptr(), out.stride(0)
+        p.agg, p.ld_agg = agg.data_ptr(), agg.stride(0)
+        p.att = att.data_ptr()
+        p.n_channels = k
+        if ops.implicit:
+            p.row_scale = ops.row_scale.data_ptr()
+        extra = ()
+        if four:                                  # pre_S = deg * (A_low S) - S: one F-wide gather of S
+            ps = torch.empty(n, f, dtype=_F32, device=dev)
+            if cfg.gather_bf16 and f % 2 == 0 and f > 8:
+                sgt = cast_bf16(s_gath)
+                p.sg_bf16 = 1
+            else:
+                sgt = s_gath
+            p.sg, p.ld_sg = sgt.data_ptr(), sgt.stride(0)
+            p.ss, p.ld_ss = s_local.data_ptr(), s_local.stride(0)
+            p.deg = ops.deg.data_ptr()
+            p.ps, p.ld_ps = ps.data_ptr(), ps.stride(0)
+            extra = (ps, s_local)
+        _set_post(p, ctx.post_relu, ctx.post_scale, ctx.post_drop, ops.row_offset)
+        # the row's head statistics (mean | rstd | sigmoid | alpha per channel): 16 k bytes per row that save
+        # the backward three 16-lane reductions per channel and row
+        stats = torch.empty(n, 4 * k, dtype=_F32, device=dev) if any(ctx.needs_input_grad) else None
+        if stats is not None:
+            p.head_stats, p.ld_head_stats = stats.data_ptr(), stats.stride(0)
+        ctx.head_stats = stats
+        # (the row-local stage is a kernel of its own when P is given, and always with the structure channel)
+        nxt = _next_proj_request(call, f, dev, row_local_only=f == 64 and (agg_given is not None or four))
+        if nxt is not None:
+            n_w3, n_relu, f2, n_pack = nxt
+            n_zlh, _ = _narrow_tables(n, f2, f2, dev, n_pack)
+            n_zi = torch.empty(n, f2, dtype=_F32, device=dev)
+            p.next_w_low, p.next_w_high, p.next_w_mlp = (w.data_ptr() for w in n_w3)
+            p.next_ld_w, p.next_f, p.next_relu = n_w3[0].stride(0), f2, int(n_relu)
+            p.next_zlh, p.ld_next_zlh = n_zlh.data_ptr(), n_zlh.stride(0)
+            p.next_zi, p.ld_next_zi = n_zi.data_ptr(), n_zi.stride(0)
+        ws = ops.low.workspace(max(fp, f) if four else fp)
+        with _device_ctx(dev), _Timed(f"conv_agg_{'epi' if agg_given is not None else 'fwd'}/F{f}k{k}i{f_in}"):
+            st = lib.acm_conv_agg_fwd(ops.low.handle, C.byref(p), _vp(ws), ws.numel() * 4, _stream())
+        _lib.check(st, "acm_conv_agg_fwd")
+        if refill:
+            ctx.pipe.next_table_ready = True
+        if agg_holder is not None and agg_given is None:
+            agg_holder["agg"] = agg
+        if nxt is not None:
+            call.pre_proj = (out, n_zlh, n_zi, tuple(w.data_ptr() for w in n_w3), n_relu)
+        ctx.ops, ctx.cfg, ctx.f_in = ops, cfg, f_in
+        # with a fused ReLU the output itself records which elements the post-op let through: the backward reads it
+        # instead of regenerating the dropout mask (no extra memory: the next layer keeps the same tensor alive)
+        ctx.out_mask = bool(ctx.post_relu) and ctx.post_scale is None
+        if ctx.pipe is not None:
+            xpad, agg = ctx.pipe.saved[0], ctx.pipe.saved[1]
+        ctx.save_for_backward(xpad, agg, wl, wh, wm, mix, *vecs, *lnw, *lnb, *extra, *((out,) if ctx.out_mask else ()))
+        ctx.mark_non_differentiable(att)
+        return out, att
 
-        def set_post(st):
-            st.post_relu = int(ctx.post_relu)
-            if post_scale is not None:
-                st.post_scale, st.ld_post_scale = post_scale.data_ptr(), post_scale.stride(0)
-            spec = _drop_spec(ctx.post_drop, ops.row_offset)
-            if spec is not None:
-                st.post_drop = spec
-        if n != ops.n_local:
-            raise ValueError(f"input has {n} rows but the graph operator has {ops.n_local}")
-        pregathered = getattr(ops, "_pregathered", None)      # one-shot hand-over from the caller (models.GCN)
-        ops._pregathered = None
-        f_in = w_low.shape[0]
-        ctx.x_width = x.shape[1]
-        zero_padded = x.shape[1] != f_in          # dropout(..., pad_to=...) output: extra columns are zero
-        if zero_padded and (sparse_x or x.shape[1] < f_in):
-            raise ValueError(f"input has {x.shape[1]} columns but the weights have {f_in} rows")
-        # Aggregate-first (A (X W) = (A X) W): legal without a ReLU between projection and
-        # filter, worth it when F_in < F, and free of any backward SpMM when x needs no gradient.
-        ctx.agg_first = (not cfg.relu_before and f_in <= 16 and f_in < f and f <= 64 and not sparse_x
-                         and not ctx.needs_input_grad[0] and (tuning.HOST.rewrites & tuning.REWRITE_AGG_FIRST) != 0)
+    @staticmethod
+    def backward(ctx, grad_out, _grad_att):
+        """One row-local kernel and no SpMM for the three filterbank channels; the structure channel (k = 4) adds one F-wide
+        transposed product for d struc_low.  Collectives: the all-reduce of the replicated-parameter gradients, plus the
+        all-gather of D*G_S when sharded with k = 4."""
+        if grad_out is None:
+            return _NO_GRADS
+        lib = _lib.load()
+        ops, cfg, f_in = ctx.ops, ctx.cfg, ctx.f_in
+        k = cfg.n_channels
+        four = k == 4
+        saved = ctx.saved_tensors
+        out_fwd = None
+        if ctx.out_mask:
+            out_fwd, saved = saved[-1], saved[:-1]
+        xpad, agg, wl, wh, wm, mix = saved[:6]
+        vecs = list(saved[6:6 + k])
+        nln = k if cfg.layernorm else 0
+        lnw = list(saved[6 + k:6 + k + nln])
+        lnb = list(saved[6 + k + nln:6 + k + 2 * nln])
+        dev = xpad.device
+        n, f, fp = xpad.shape[0], wl.shape[1], xpad.shape[1]
+        lazy, ctx.lazy = getattr(ctx, "lazy", None), None
+        if lazy is not None and (grad_out is not lazy["placeholder"] and grad_out.data_ptr() != lazy["placeholder"].data_ptr()):
+            raise RuntimeError("acm_conv: the hidden activation marked private (CallContext.hidden_private) received a gradient "
+                               "from somewhere else as well")
+        fuse_proj = (lazy is not None and fp == 8 and f == 64 and out_fwd is not None and ctx.post_scale is None
+                     and ctx.head_stats is not None)
+        defer = ctx.call.defer
+        if lazy is not None and not fuse_proj:            # the kernel cannot take it: materialise dX and dW' now
+            proj_bwd(lazy["x"], lazy["dz"], lazy["w3"], lazy["d_w"], defer=defer, dx_out=lazy["placeholder"])
+            lazy = None
+        grad_out = _as_f32c(grad_out, "grad_out")
+        # [dW_L | dW_H | dW_I | d att_vec | d LayerNorm weights | biases | d att_mix] (the LayerNorm parts whether used or not)
+        nw = 3 * f_in * f
+        d_params = torch.empty(nw + 3 * k * f + k * k, dtype=_F32, device=dev)
+        q = _lib.ConvAggBwd()
+        q.f_in, q.f_pad, q.f_out = f_in, fp, f
+        q.relu_after, q.relu_mlp, q.layernorm, q.scale = int(cfg.relu_after), int(cfg.relu_mlp), int(cfg.layernorm), cfg.scale
+        q.grad_out, q.ld_grad_out = grad_out.data_ptr(), grad_out.stride(0)
+        if lazy is not None:                              # the following layer's projection backward rides this launch
+            dz2, w32 = lazy["dz"], lazy["w3"]
+            q.grad_out = None
+            q.proj_dz, q.ld_proj_dz = dz2.data_ptr(), dz2.stride(0)
+            q.proj_w_low, q.proj_w_high, q.proj_w_mlp = (w.data_ptr() for w in w32)
+            q.proj_ld_w, q.proj_f = w32[0].stride(0), w32[0].shape[1]
+            q.proj_d_w = lazy["d_w"].data_ptr()
+        q.agg, q.ld_agg = agg.data_ptr(), agg.stride(0)
+        if ctx.head_stats is not None:
+            q.head_stats, q.ld_head_stats = ctx.head_stats.data_ptr(), ctx.head_stats.stride(0)
+        q.xs, q.ld_xs = xpad.data_ptr(), xpad.stride(0)
+        q.w_low, q.w_high, q.w_mlp, q.ld_w = wl.data_ptr(), wh.data_ptr(), wm.data_ptr(), f
+        q.att_vec, q.ln_weight, q.ln_bias = _ptr_array(vecs), _ptr_array(lnw), _ptr_array(lnb)
+        q.att_mix = mix.data_ptr()
+        q.d_params = d_params.data_ptr()
+        q.n_channels = k
+        _set_post(q, ctx.post_relu, ctx.post_scale, ctx.post_drop, ops.row_offset)
+        if out_fwd is not None:
+            q.out, q.ld_out = out_fwd.data_ptr(), out_fwd.stride(0)
+        if four:
+            ps, s_local = saved[-2], saved[-1]
+            gs = torch.empty(n, f, dtype=_F32, device=dev)            # D * dL/dpre_S
+            q.ps, q.ld_ps = ps.data_ptr(), ps.stride(0)
+            q.ss, q.ld_ss = s_local.data_ptr(), s_local.stride(0)
+            q.deg = ops.deg.data_ptr()
+            q.g_struc, q.ld_g_struc = gs.data_ptr(), gs.stride(0)
+            q.g_struc_scale = None if ops.implicit else ops.deg.data_ptr()
+        ws = _workspace(lib, dev, "acm_conv_agg_bwd_workspace_bytes", n, f_in, f)
+        q.defer = defer.pointer() if defer is not None else None
+        pipe = ctx.pipe
+        carry = pipe is not None and pipe.next_table_ready and not pipe.next_agg_ready
+        if carry:                                     # the next step's P = A_low dropout(x) rides this launch
+            q.next_a = ops.low.handle
+            q.next_xg, q.ld_next_xg = pipe.table().data_ptr(), pipe.table().stride(0)
+            q.next_row_scale = ops.row_scale.data_ptr()
+            q.next_agg, q.ld_next_agg = pipe.agg().data_ptr(), pipe.agg().stride(0)
+        with _device_ctx(dev), _Timed(f"conv_agg_bwd{'+gather' if carry else ''}{'+proj' if lazy is not None else ''}/F{f}k{k}i{f_in}"):
+            st = lib.acm_conv_agg_bwd(n, C.byref(q), _vp(ws), ws.numel() * 4, _stream())
+        if st == 4 and (lazy is not None or carry):       # ACM_EUNSUPPORTED for this shape after all: the plain launch(es)
+            if lazy is not None:
+                proj_bwd(lazy["x"], lazy["dz"], lazy["w3"], lazy["d_w"], defer=defer, dx_out=lazy["placeholder"])
+                q.grad_out, q.proj_dz, lazy = grad_out.data_ptr(), None, None
+            if carry:                                     # the gather as its own launch, right here: the pipeline stays valid
+                q.next_a, q.next_xg, q.next_row_scale, q.next_agg = None, None, None, None          # (also inside a capture, where
+                spmm(ops.low, pipe.table(), out=pipe.agg(), row_scale=ops.row_scale)                 # nobody could prime() it again)
+            with _device_ctx(dev), _Timed(f"conv_agg_bwd/F{f}k{k}i{f_in}"):
+                st = lib.acm_conv_agg_bwd(n, C.byref(q), _vp(ws), ws.numel() * 4, _stream())
+        _lib.check(st, "acm_conv_agg_bwd")
+        if carry:
+            pipe.next_agg_ready = True
+        if defer is not None:
+            defer.hold(ws, [d_params] + ([lazy["d_w"]] if lazy is not None else []),
+                       keep=[d_params] + ([lazy["d_w"]._base if lazy["d_w"]._base is not None else lazy["d_w"]] if lazy is not None else []))
+        d_struc = _struc_grad(ops, cfg, gs) if four else None
+        _reduce_replicated(d_params, ops, defer)
+        d_w = d_params[:nw].view(3, f_in, f)
+        d_vec, d_lnw, d_lnb, d_mix = _flat_views(d_params, nw, k, f, True)
+        if not cfg.layernorm:
+            d_lnw = d_lnb = []
+        return _grads(None, (d_w[0], d_w[1], d_w[2]), d_vec, d_struc, d_mix, d_lnw, d_lnb)
+
+
+class _AcmAcmii(torch.autograd.Function):
+    """out, att = ACMII layer that recomputes relu(x_j [W_L | W_H]) per edge from the gathered narrow input rows
+    (_acmii_shape; arguments as _AcmAggFirst).
+
+    forward : the mask form (pattern-only operator, input without gradient): acm_acmii_table -> acm_conv_acmii_v_fwd; else (or
+              ACM_EUNSUPPORTED) the fp32 acm_conv_acmii_fwd, which leaves the literal form's saved layout
+    backward: mask form: acm_conv_bwd_local -> acm_conv_acmii_v_bwd (all three weight gradients) [-> spmm_sub];
+              else the literal backward (_literal_backward)"""
+
+    @staticmethod
+    def forward(ctx, x, w_low, w_high, w_mlp, v_low, v_high, v_mlp, v_struc, struc_low, att_mix, lnw_low, lnw_high, lnw_mlp,
+                lnw_struc, lnb_low, lnb_high, lnb_mlp, lnb_struc, ops, cfg, post_relu, post_scale, post_drop, call, tail_layer,
+                agg_holder, in_drop, pregathered):
+        lib = _lib.load()
+        x = _conv_prologue(ctx, x, w_low, ops, post_relu, post_scale, post_drop, call, in_drop)
+        dev, n = x.device, x.shape[0]
+        f_in, f = w_low.shape
+        k = cfg.n_channels
+        four = k == 4
+        fp = 8
+        zero_padded = x.shape[1] != f_in
+        x, xpad, xg, _, _ = _gathered_input(ctx, x, ops, f_in, f, fp, agg_holder, pregathered, False)
+        w3 = wl, wh, wm = tuple(_as_f32c(t, "weight") for t in (w_low, w_high, w_mlp))
+        x = x[:, :f_in].contiguous() if zero_padded else x      # saved for K5 (dWcat = X^T dZ)
+        if four:
+            s_local, s_gath = _struc_rows(ops, struc_low, n)
+        vecs, lnw, lnb, mix = _head_params(cfg, (v_low, v_high, v_mlp, v_struc), att_mix, (lnw_low, lnw_high, lnw_mlp, lnw_struc),
+                                           (lnb_low, lnb_high, lnb_mlp, lnb_struc))
+        out = torch.empty(n, f, dtype=_F32, device=dev)
+        att = torch.empty(n, 4, dtype=_F32, device=dev)
+        zlh = torch.empty(n, 2 * f, dtype=_F32, device=dev)
+        zi = torch.empty(n, f, dtype=_F32, device=dev)
+        pre = torch.empty(n, (k - 1) * f, dtype=_F32, device=dev)
+        p = _lib.ConvAcmiiFwd()
+        p.f_in, p.f_pad, p.f_out, p.layernorm, p.scale = f_in, fp, f, int(cfg.layernorm), cfg.scale
+        p.n_channels = k
+        if four:                                  # ps = A_low S: one F-wide single-channel gather of the parameter
+            ps = spmm(ops.low, s_gath, row_scale=ops.row_scale if ops.implicit else None, bf16=cfg.gather_bf16)
+            p.ps, p.ld_ps = ps.data_ptr(), ps.stride(0)
+            p.ss, p.ld_ss = s_local.data_ptr(), s_local.stride(0)
+            p.deg = ops.deg.data_ptr()
+        p.xg, p.ld_xg = xg.data_ptr(), xg.stride(0)
+        p.xs, p.ld_xs = xpad.data_ptr(), xpad.stride(0)
+        p.w_low, p.w_high, p.w_mlp, p.ld_w = wl.data_ptr(), wh.data_ptr(), wm.data_ptr(), f
+        p.att_vec, p.ln_weight, p.ln_bias = _ptr_array(vecs), _ptr_array(lnw), _ptr_array(lnb)
+        p.att_mix = mix.data_ptr()
+        p.out, p.ld_out = out.data_ptr(), out.stride(0)
+        p.pre, p.ld_pre = pre.data_ptr(), pre.stride(0)
+        p.att = att.data_ptr()
+        p.zlh, p.ld_zlh = zlh.data_ptr(), zlh.stride(0)
+        p.zi, p.ld_zi = zi.data_ptr(), zi.stride(0)
+        if ops.implicit:
+            p.row_scale = ops.row_scale.data_ptr()
+        _set_post(p, ctx.post_relu, ctx.post_scale, ctx.post_drop, ops.row_offset)
+        ws = _workspace(lib, dev, "acm_conv_acmii_fwd_workspace_bytes", ops.low.handle)
+        # The mask form (acm_conv_acmii_v.hip): relu(x_j W) = m_j * (x_j W), so the aggregate is W contracted with
+        # V_i = sum_j m_j (x) x_j -- a product over the neighbour index on the bf16 matrix pipe, exact operands -- and the
+        # weight gradients are the same V contracted with dH: no transposed product for them (the structure channel's
+        # parameter keeps its one F-wide transposed product).  A pattern-only operator over this process's own rows, no
+        # gradient into x.
+        ctx.mask_table = None
+        st = 4
+        if (ops.implicit and not ctx.needs_input_grad[0] and n > 0 and xg.shape[0] == ops.low.n_cols
+                and (tuning.HOST.rewrites & tuning.REWRITE_ACMII_MASK) != 0
+                and (getattr(ops.low, "item_stream_waves", 0) > 0         # one-off per operator (synchronises: never
+                     or (not _capturing(dev) and ops.low.build_item_streams()))):     # inside a capture, whose warm-up built them)
+            # the table covers every column of the operator: this process's rows, or (row-sharded) the all-gathered input --
+            # each rank evaluates the masks of its halo itself, and its backward then needs NO all-gather of gradients
+            ng = xg.shape[0]
+            tb = C.c_size_t()
+            _lib.check(lib.acm_acmii_table_bytes(ng, C.byref(tb)), "acm_acmii_table_bytes")
+            table = torch.empty(tb.value // 4, dtype=torch.int32, device=dev)
+            with _device_ctx(dev), _Timed(f"acmii_table/{ng}x{f_in}"):
+                st = lib.acm_acmii_table(ng, f_in, xg.data_ptr(), xg.stride(0), wl.data_ptr(), wh.data_ptr(), f,
+                                         table.data_ptr(), tb.value, _stream())
+            if st == 0:
+                if ops.low.n_long_rows == 0:          # only the fix-up of long rows reads zlh (its high-pass half)
+                    p.zlh, p.ld_zlh = None, 0
+                with _device_ctx(dev), _Timed(f"conv_acmii_v_fwd/F{f}i{f_in}"):
+                    st = lib.acm_conv_acmii_v_fwd(ops.low.handle, C.byref(p), table.data_ptr(), _vp(ws), ws.numel() * 4, _stream())
+                if st == 0:
+                    ctx.mask_table, ctx.mask_x = table, xpad
+                    ctx.mask_self_offset = 0
+                    if ops.sharded:                   # this rank's rows inside the gathered numbering (_gather_rows)
+                        import torch.distributed as dist
+                        ctx.mask_self_offset = dist.get_rank(ops.group) * (ops.n_gathered // dist.get_world_size(ops.group))
+                else:
+                    p.zlh, p.ld_zlh = zlh.data_ptr(), zlh.stride(0)
+            if st not in (0, 4):                      # 4 = ACM_EUNSUPPORTED: the fp32 kernel below
+                _lib.check(st, "acm_conv_acmii_v_fwd")
+        if ctx.mask_table is None:
+            with _device_ctx(dev), _Timed(f"conv_acmii_fwd/F{f}i{f_in}"):
+                st = lib.acm_conv_acmii_fwd(ops.low.handle, C.byref(p), _vp(ws), ws.numel() * 4, _stream())
+            _lib.check(st, "acm_conv_acmii_fwd")
+        ctx.ops, ctx.cfg = ops, cfg
+        ctx.tail, ctx.sparse_x, ctx.hops, ctx.fb = None, None, 1, f        # (what _literal_backward reads)
+        ctx.save_for_backward(x, *w3, zlh, zi, pre, mix, *vecs, *lnw, *lnb)
+        ctx.mark_non_differentiable(att)
+        return out, att
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_att):
+        if grad_out is None:
+            return _NO_GRADS
+        if ctx.mask_table is None:
+            return _literal_backward(ctx, grad_out)
+        # the mask form's backward: dW_L, dW_H straight from dH_L, dH_H (K3's g) over the FORWARD operator and the
+        # forward's table, and the row-local dW_I = X^T dZ_I in the same launch
+        lib = _lib.load()
+        ops, defer = ctx.ops, ctx.call.defer
+        _, w3, _, s = _k3_backward(ctx, grad_out)
+        g, dz, flat = s["g"], s["dz"], s["flat"]
+        f_in, f = w3[0].shape
+        d_wcat = flat[:s["nw"]].view(3, f_in, f)
+        xt = ctx.mask_x
+        b = _lib.ConvAcmiiBwd()
+        b.f_in, b.table = f_in, ctx.mask_table.data_ptr()
+        b.g_low, b.ld_g_low = g.data_ptr(), g.stride(0)
+        b.g_high, b.ld_g_high = g.data_ptr() + 4 * ctx.fb, g.stride(0)
+        b.g_mlp, b.ld_g_mlp = dz.data_ptr() + 8 * f, dz.stride(0)
+        b.x, b.ld_x = xt.data_ptr(), xt.stride(0)
+        b.self_offset = ctx.mask_self_offset
+        b.row_scale = ops.row_scale.data_ptr()
+        b.d_w_low, b.d_w_high, b.d_w_mlp, b.ld_dw = d_wcat[0].data_ptr(), d_wcat[1].data_ptr(), d_wcat[2].data_ptr(), f
+        b.defer = defer.pointer() if defer is not None else None
+        wsb = _workspace(lib, dz.device, "acm_conv_acmii_v_bwd_workspace_bytes", ops.low.handle)
+        with _device_ctx(dz.device), _Timed(f"conv_acmii_v_bwd/F{f}i{f_in}"):
+            st = lib.acm_conv_acmii_v_bwd(ops.low.handle, C.byref(b), _vp(wsb), wsb.numel() * 4, _stream())
+        _lib.check(st, "acm_conv_acmii_v_bwd")
+        if defer is not None:
+            defer.hold(wsb, [d_wcat[0], d_wcat[1], d_wcat[2]], keep=[flat, ctx.mask_table, g, dz, xt])
+        # (pattern-only: K3 left G_S unscaled)
+        d_struc = _struc_grad(ops, ctx.cfg, s["gs"]) if ctx.cfg.n_channels == 4 else None
+        _reduce_replicated(flat, ops, defer)
+        return _grads(None, (d_wcat[0], d_wcat[1], d_wcat[2]), s["d_vec"], d_struc, s["d_mix"], s["d_lnw"], s["d_lnb"])
+
+
+def _literal_project(ctx, x, w3, ops, cfg):
+    """K1 of the literal form: Z = X [W_L | W_H | W_I] (ReLU'd for ACMII), with the caller's input dropout drawn in the operand
+    load where the projection can (else applied here first), then the k-hop chain's low-pass products.  Returns
+    (x as saved for the backward, [Z_L | Z_H], Z_I, the gathered [Z_L | Z_H] or [A_low^(k-1) Z_L | Z_H]); sets ctx.fb."""
+    call, hops = ctx.call, ctx.hops
+    sparse_x = isinstance(x, SparseFeatures)
+    n, dev = x.shape[0], w3[0].device
+    f_in, f = w3[0].shape
+    four = cfg.n_channels == 4
+    # narrow dense layers (F <= 5) project with the streaming kernel straight from the three weights; everything
+    # else packs [W_L | W_H | W_I] for the MFMA GEMM / the CSR-feature product
+    use_proj = (not sparse_x and f <= 5 and f_in <= 64     # wider inputs: the MFMA GEMM is the faster stream
+                and w3[0].stride(0) == w3[1].stride(0) == w3[2].stride(0))
+    fb = ctx.fb = _chan_block(f)                  # column distance of the two gathered channels
+    # Row pitch of Z: for narrow layers the gathered block [Z_L | Z_H] (2F floats) must be
+    # one aligned vector fetch, so rows are padded to a multiple of that block.
+    ldz = 3 * f
+    if f in (2, 4, 8):
+        ldz = -(-3 * f // (2 * f)) * (2 * f)
+    elif fb != f:
+        ldz = -(-(2 * fb + f) // 4) * 4
+    pre = _take_pre_proj(call, x, w3, cfg.relu_before) if use_proj else None
+    drop_spec = _drop_spec(ctx.in_drop, ops.row_offset) if ctx.in_drop is not None else None
+    # [Z_L | Z_H] as a compact table of its own (what a narrow gather / the k-hop chain walks: 16-byte-block rows at
+    # their own pitch instead of [Z_L | Z_H | Z_I | pad] rows), Z_I next to it
+    two_tables = (use_proj or f in (2, 4, 8) or hops > 1) and not sparse_x
+    # four channels of two columns: [Z_L | Z_H] and the gathered struc_low rows share 32-byte rows (_narrow_tables)
+    pack4 = four and f == 2 and fb == 2 and two_tables and not ops.sharded and not getattr(ops, "general", False)
+    done3 = False
+    if pre is None and not sparse_x:
+        # tall dense inputs of 32..128 features: the three weight matrices in place on the split-bf16 kernel (no cat)
+        if two_tables:
+            zlh, _ = _narrow_tables(n, fb, f, dev, pack4)
+            zi = torch.empty(n, f, dtype=_F32, device=dev)
+            done3 = proj3(x, w3, fb, zlh, zi, relu=cfg.relu_before, x_drop=drop_spec)
+        else:
+            z = torch.empty(n, ldz, dtype=_F32, device=dev)[:, : 2 * fb + f]
+            done3 = proj3(x, w3, fb, z, relu=cfg.relu_before, x_drop=drop_spec)
+            zlh, zi = z[:, : 2 * fb], z[:, 2 * fb:]
+        if done3:
+            ctx.in_drop_used = drop_spec is not None
+    if (not done3 and drop_spec is not None
+            and (pre is not None or use_proj or two_tables or sparse_x or not gemm_drop_supported(n, f_in, 2 * fb + f))):
+        # the caller left its input dropout to this layer (in_drop) but the projection about to run cannot draw
+        # the mask in its operand load (the two-table / k-hop GEMM, the narrow streaming projection, shapes outside
+        # acm_gemm_drop): apply it here, same counter-based mask, and save the DROPPED input for the backward
+        if sparse_x:
+            raise NotImplementedError("in_drop with CSR features: the caller applies the dropout to the values")
+        x, pre = _drop_now(x, drop_spec), None
+        drop_spec = None
+    if done3:
+        pass                                       # [Z_L | Z_H], Z_I are written
+    elif pre is not None:
+        zlh, zi = pre                              # computed in the preceding layer's epilogue
+    elif use_proj:
+        zlh, _ = _narrow_tables(n, fb, f, dev, pack4)
+        zi = torch.empty(n, f, dtype=_F32, device=dev)
+        proj_fwd(x, w3, zlh, zi, relu=cfg.relu_before, h_col=fb)
+    else:
+        if fb != f:                        # [W_L 0 | W_H 0 | W_I]: the product lands in channel blocks of fb columns
+            zpad = w3[0].new_zeros(w3[0].shape[0], fb - f)
+            wcat = torch.cat((w3[0], zpad, w3[1], zpad, w3[2]), dim=1).contiguous()
+        else:
+            wcat = torch.cat(w3, dim=1).contiguous()                            # [F_in, 3F]
+        if two_tables:                            # one GEMM with a two-matrix output
+            zlh, _ = _narrow_tables(n, fb, f, dev, pack4)
+            zi = torch.empty(n, f, dtype=_F32, device=dev)
+            gemm_split(x, wcat, zlh, zi, relu=cfg.relu_before)
+        else:
+            z = torch.empty(n, ldz, dtype=_F32, device=dev)[:, : 2 * fb + f]
+            if sparse_x:                              # Z = X_csr Wcat: nnz(X) * 3F FMAs
+                spmm_v(x.csr, x.values, wcat, relu=cfg.relu_before, out=z)
+            else:
+                gemm(x, wcat, relu=cfg.relu_before, out=z, a_drop=drop_spec)        # [n, 3F] view
+                ctx.in_drop_used = drop_spec is not None
+            zlh, zi = z[:, : 2 * fb], z[:, 2 * fb:]
+    if hops > 2:
+        # [A_low^(k-1) Z_L | Z_H] in place: the last of the k - 1 >= 2 products reads a hop buffer and writes over
+        # Z_L (which nothing reads again: no ReLU mask in the k-hop layer) -- no copy of Z_H into a second table
+        t = zlh[:, :f]
+        for hop in range(hops - 1):
+            t = _low_product(ops, t, out=zlh[:, :f] if hop == hops - 2 else None)
+        zg = _gather_rows(ops, zlh) if ops.sharded else zlh
+    elif hops > 1:
+        zc = torch.empty(n, 2 * fb, dtype=_F32, device=dev)              # [A_low Z_L | Z_H]
+        _low_product(ops, zlh[:, :f], out=zc[:, :f])
+        zc[:, fb:fb + f] = zlh[:, fb:fb + f]
+        zg = _gather_rows(ops, zc)
+    else:
+        zg = _gather_rows(ops, zlh) if ops.sharded else zlh                 # gathered [Z_L|Z_H]
+    return x, zlh, zi, zg
+
+
+class _AcmLiteral(torch.autograd.Function):
+    """out, att = ACM layer in the reference's order, project then gather (arguments as _AcmAggFirst).
+
+    forward : K1 acm_gemm / acm_proj3 / acm_proj_fwd (X [W_L|W_H|W_I]) [-> the k-hop chain] -> K2 acm_conv_fwd
+              (or, for an output layer a training loop asked for it, acm_conv_fwd_tail: K2 + loss + K3 in one row pass)
+    backward: K3 acm_conv_bwd_local -> K4 acm_conv_bwd_spmm -> K5 acm_gemm (X^T dZ, dZ Wcat^T)"""
+
+    @staticmethod
+    def forward(ctx, x, w_low, w_high, w_mlp, v_low, v_high, v_mlp, v_struc, struc_low, att_mix, lnw_low, lnw_high, lnw_mlp,
+                lnw_struc, lnb_low, lnb_high, lnb_mlp, lnb_struc, ops, cfg, post_relu, post_scale, post_drop, call, tail_layer,
+                agg_holder, in_drop, pregathered):
+        lib = _lib.load()
+        x = _conv_prologue(ctx, x, w_low, ops, post_relu, post_scale, post_drop, call, in_drop)
+        call, post_scale = ctx.call, ctx.post_scale
+        sparse_x = isinstance(x, SparseFeatures)
+        dev, n = x.device, x.shape[0]
+        f_in, f = w_low.shape
+        k = cfg.n_channels
         four = k == 4
         general = bool(getattr(ops, "general", False))
         # k-hop low-pass channel (ACM-SGC, ACM-Pytorch/utils.py:631-637 materialises the dense A_low^k): here the
         # chain A_low (A_low (... Z_L)) with the 1-hop operator, adj_high stays 1-hop like the reference's
-        hops = int(getattr(ops, "hops", 1))
-        ctx.hops = hops
-        ctx.fb = f                               # set by the literal path below (_chan_block)
-        if hops > 1:
-            if cfg.relu_before or cfg.relu_after or four or general:
-                raise NotImplementedError("hops > 1 is the ACM-SGC chain: model_type 'acmsgc' only")
-            ctx.agg_first = False
-        if general:
-            if ops.sharded:
-                raise NotImplementedError("general operator pairs are not row-sharded")
-            ctx.agg_first = False
-        # ACMII first layer with a narrow input: gather the input rows and recompute relu(x_j [W_L | W_H]) per edge on
-        # the matrix pipe instead of gathering the 2F-wide projected rows (acm_conv_acmii_fwd = K1 + K2)
-        ctx.recompute = (cfg.relu_before and not cfg.relu_after and cfg.relu_mlp and f == 64 and f_in <= 8
-                         and not sparse_x and not general and hops == 1
-                         and (tuning.HOST.rewrites & tuning.REWRITE_ACMII_RECOMPUTE) != 0)
-        fb = f                                   # column distance of the two gathered channels (see _chan_block)
-        if ctx.agg_first or ctx.recompute:
-            if ctx.in_drop is not None:               # these forms gather the input itself: they need the dropped rows
-                x = _drop_now(x, _drop_spec(ctx.in_drop, ops.row_offset))
-                ctx.in_drop_materialised = True
-            fp = 4 if f_in <= 4 else (8 if f_in <= 8 else 16)
-            if ctx.recompute:
-                fp = 8
-            # (the pipeline's table is refilled in place through raw pointers -- no version bump: never through the holder;
-            #  ACMII recomputes per edge from the gathered rows: there is no P to keep)
-            if agg_holder is not None and (ops.sharded or call.pipe is not None or ctx.recompute or ctx.in_drop is not None):
-                agg_holder = None
-            if x.shape[1] == fp:
-                xpad = x
-            else:                                     # the zero-padded copy of a static input is kept with its P
-                xpad = agg_holder.get("xpad") if agg_holder is not None else None
-                if xpad is None or tuple(xpad.shape) != (n, fp):
-                    xpad = torch.nn.functional.pad(x[:, :f_in], (0, fp - f_in))
-                    if agg_holder is not None:
-                        agg_holder["xpad"] = xpad
-            agg_given = agg_holder.get("agg") if agg_holder is not None else None
-            if agg_given is not None and tuple(agg_given.shape) != (n, fp):
-                agg_given = None
-            # a training loop's input pipeline (InputPipeline): P for this step came out of the previous step's backward
-            pipe = call.pipe
-            ctx.pipe = None
-            if (pipe is not None and pipe.primed and ctx.agg_first and fp == 8 and f == 64 and ops is pipe.ops
-                    and xpad.data_ptr() == pipe.local_table().data_ptr() and agg_holder is None):   # (only a training step carries a pipe)
-                agg_given = pipe.agg()
-                ctx.pipe = pipe
-                pipe.adopted = True               # the loop may refill the table: this forward leaves its copies in ``saved``
-            if agg_given is not None:
-                xg = xpad                             # not read: P = A_low X comes from the holder
-            elif (pregathered is not None and pregathered[0].data_ptr() == xpad.data_ptr()
-                    and pregathered[1].shape[1] == fp and pregathered[1].shape[0] == ops.n_gathered):
-                xg = pregathered[1]                   # the caller already holds every node's (dropped) input
-            else:
-                xg = _gather_rows(ops, xpad)
-            wl, wh, wm = (_as_f32c(t, "weight") for t in (w_low, w_high, w_mlp))
-            if ctx.recompute:
-                w3 = (wl, wh, wm)
-                x = x[:, :f_in].contiguous() if zero_padded else x      # saved for K5 (dWcat = X^T dZ)
-        else:
-            if zero_padded:
-                x = x[:, :f_in].contiguous()
-            w3 = tuple(_as_f32c(t, "weight") for t in (w_low, w_high, w_mlp))
-            # narrow dense layers (F <= 5) project with the streaming kernel straight from the three weights; everything
-            # else packs [W_L | W_H | W_I] for the MFMA GEMM / the CSR-feature product
-            use_proj = (not sparse_x and f <= 5 and f_in <= 64     # wider inputs: the MFMA GEMM is the faster stream
-                        and w3[0].stride(0) == w3[1].stride(0) == w3[2].stride(0))
-            fb = ctx.fb = _chan_block(f)
-            # Row pitch of Z: for narrow layers the gathered block [Z_L | Z_H] (2F floats) must be
-            # one aligned vector fetch, so rows are padded to a multiple of that block.
-            ldz = 3 * f
-            if f in (2, 4, 8):
-                ldz = -(-3 * f // (2 * f)) * (2 * f)
-            elif fb != f:
-                ldz = -(-(2 * fb + f) // 4) * 4
-            pre = _take_pre_proj(call, x, w3, cfg.relu_before) if use_proj else None
-            drop_spec = _drop_spec(ctx.in_drop, ops.row_offset) if ctx.in_drop is not None else None
-            # [Z_L | Z_H] as a compact table of its own (what a narrow gather / the k-hop chain walks: 16-byte-block rows at
-            # their own pitch instead of [Z_L | Z_H | Z_I | pad] rows), Z_I next to it
-            two_tables = (use_proj or f in (2, 4, 8) or hops > 1) and not sparse_x
-            # four channels of two columns: [Z_L | Z_H] and the gathered struc_low rows share 32-byte rows (_narrow_tables)
-            pack4 = four and f == 2 and fb == 2 and two_tables and not ops.sharded and not general
-            done3 = False
-            if pre is None and not sparse_x:
-                # tall dense inputs of 32..128 features: the three weight matrices in place on the split-bf16 kernel (no cat)
-                if two_tables:
-                    zlh, _ = _narrow_tables(n, fb, f, dev, pack4)
-                    zi = torch.empty(n, f, dtype=_F32, device=dev)
-                    done3 = proj3(x, w3, fb, zlh, zi, relu=cfg.relu_before, x_drop=drop_spec)
-                else:
-                    z = torch.empty(n, ldz, dtype=_F32, device=dev)[:, : 2 * fb + f]
-                    done3 = proj3(x, w3, fb, z, relu=cfg.relu_before, x_drop=drop_spec)
-                    zlh, zi = z[:, : 2 * fb], z[:, 2 * fb:]
-                if done3:
-                    ctx.in_drop_used = drop_spec is not None
-            if (not done3 and drop_spec is not None
-                    and (pre is not None or use_proj or two_tables or sparse_x or not gemm_drop_supported(n, f_in, 2 * fb + f))):
-                # the caller left its input dropout to this layer (in_drop) but the projection about to run cannot draw
-                # the mask in its operand load (the two-table / k-hop GEMM, the narrow streaming projection, shapes outside
-                # acm_gemm_drop): apply it here, same counter-based mask, and save the DROPPED input for the backward
-                if sparse_x:
-                    raise NotImplementedError("in_drop with CSR features: the caller applies the dropout to the values")
-                x, pre = _drop_now(x, drop_spec), None
-                ctx.in_drop_materialised = True
-                drop_spec = None
-            if done3:
-                pass                                       # [Z_L | Z_H], Z_I are written
-            elif pre is not None:
-                zlh, zi = pre                              # computed in the preceding layer's epilogue
-            elif use_proj:
-                zlh, _ = _narrow_tables(n, fb, f, dev, pack4)
-                zi = torch.empty(n, f, dtype=_F32, device=dev)
-                proj_fwd(x, w3, zlh, zi, relu=cfg.relu_before, h_col=fb)
-            else:
-                if fb != f:                        # [W_L 0 | W_H 0 | W_I]: the product lands in channel blocks of fb columns
-                    zpad = w3[0].new_zeros(w3[0].shape[0], fb - f)
-                    wcat = torch.cat((w3[0], zpad, w3[1], zpad, w3[2]), dim=1).contiguous()
-                else:
-                    wcat = torch.cat(w3, dim=1).contiguous()                            # [F_in, 3F]
-                if two_tables:                            # one GEMM with a two-matrix output
-                    zlh, _ = _narrow_tables(n, fb, f, dev, pack4)
-                    zi = torch.empty(n, f, dtype=_F32, device=dev)
-                    gemm_split(x, wcat, zlh, zi, relu=cfg.relu_before)
-                else:
-                    z = torch.empty(n, ldz, dtype=_F32, device=dev)[:, : 2 * fb + f]
-                    if sparse_x:                              # Z = X_csr Wcat: nnz(X) * 3F FMAs
-                        spmm_v(x.csr, x.values, wcat, relu=cfg.relu_before, out=z)
-                    else:
-                        gemm(x, wcat, relu=cfg.relu_before, out=z, a_drop=drop_spec)        # [n, 3F] view
-                        ctx.in_drop_used = drop_spec is not None
-                    zlh, zi = z[:, : 2 * fb], z[:, 2 * fb:]
-            if hops > 2:
-                # [A_low^(k-1) Z_L | Z_H] in place: the last of the k - 1 >= 2 products reads a hop buffer and writes over
-                # Z_L (which nothing reads again: no ReLU mask in the k-hop layer) -- no copy of Z_H into a second table
-                t = zlh[:, :f]
-                for hop in range(hops - 1):
-                    t = _low_product(ops, t, out=zlh[:, :f] if hop == hops - 2 else None)
-                zg = _gather_rows(ops, zlh) if ops.sharded else zlh
-            elif hops > 1:
-                zc = torch.empty(n, 2 * fb, dtype=_F32, device=dev)              # [A_low Z_L | Z_H]
-                _low_product(ops, zlh[:, :f], out=zc[:, :f])
-                zc[:, fb:fb + f] = zlh[:, fb:fb + f]
-                zg = _gather_rows(ops, zc)
-            else:
-                zg = _gather_rows(ops, zlh) if ops.sharded else zlh                 # gathered [Z_L|Z_H]
+        hops = ctx.hops = int(getattr(ops, "hops", 1))
+        if hops > 1 and (cfg.relu_before or cfg.relu_after or four or general):
+            raise NotImplementedError("hops > 1 is the ACM-SGC chain: model_type 'acmsgc' only")
+        if general and ops.sharded:
+            raise NotImplementedError("general operator pairs are not row-sharded")
+        zero_padded = x.shape[1] != f_in
+        if zero_padded:
+            x = x[:, :f_in].contiguous()
+        w3 = tuple(_as_f32c(t, "weight") for t in (w_low, w_high, w_mlp))
+        x, zlh, zi, zg = _literal_project(ctx, x, w3, ops, cfg)
+        fb = ctx.fb
         if four and general:
             if ops.un is None:
                 raise RuntimeError("structure_info=1 needs adj_low_unnormalized")
             s_local = _as_f32c(struc_low, "struc_low")
         elif four:
-            if ops.deg is None:
-                raise RuntimeError("structure_info=1 needs adj_low_unnormalized")
-            s_local = _as_f32c(struc_low, "struc_low")
-            if s_local.shape[0] != n:
-                raise ValueError("struc_low rows != local nodes")
-            s_gath = _gather_rows(ops, s_local)
-        vecs = [_as_f32c(t, "att_vec") for t in ((v_low, v_high, v_mlp, v_struc) if four else (v_low, v_high, v_mlp))]
-        lnw = [_as_f32c(t, "ln") for t in (lnw_low, lnw_high, lnw_mlp, lnw_struc)[:k]] if cfg.layernorm else []
-        lnb = [_as_f32c(t, "ln") for t in (lnb_low, lnb_high, lnb_mlp, lnb_struc)[:k]] if cfg.layernorm else []
-        mix = _as_f32c(att_mix, "att_vec")
-        if tuple(mix.shape) != (k, k):
-            raise RuntimeError(f"att_vec is {tuple(mix.shape)} but the layer mixes {k} channels "
-                               "(structure_info is only valid with acmgcnp/acmgcnpp)")
+            s_local, s_gath = _struc_rows(ops, struc_low, n)
+        vecs, lnw, lnb, mix = _head_params(cfg, (v_low, v_high, v_mlp, v_struc), att_mix, (lnw_low, lnw_high, lnw_mlp, lnw_struc),
+                                           (lnb_low, lnb_high, lnb_mlp, lnb_struc))
         out = torch.empty(n, f, dtype=_F32, device=dev)
         att = torch.empty(n, 4, dtype=_F32, device=dev)
-        if ctx.recompute:
-            zlh = torch.empty(n, 2 * f, dtype=_F32, device=dev)
-            zi = torch.empty(n, f, dtype=_F32, device=dev)
-            pre = torch.empty(n, (k - 1) * f, dtype=_F32, device=dev)
-            p = _lib.ConvAcmiiFwd()
-            p.f_in, p.f_pad, p.f_out, p.layernorm, p.scale = f_in, fp, f, int(cfg.layernorm), cfg.scale
-            p.n_channels = k
-            if four:                                  # ps = A_low S: one F-wide single-channel gather of the parameter
-                ps = spmm(ops.low, s_gath, row_scale=ops.row_scale if ops.implicit else None, bf16=cfg.gather_bf16)
-                p.ps, p.ld_ps = ps.data_ptr(), ps.stride(0)
-                p.ss, p.ld_ss = s_local.data_ptr(), s_local.stride(0)
-                p.deg = ops.deg.data_ptr()
-            p.xg, p.ld_xg = xg.data_ptr(), xg.stride(0)
-            p.xs, p.ld_xs = xpad.data_ptr(), xpad.stride(0)
-            p.w_low, p.w_high, p.w_mlp, p.ld_w = wl.data_ptr(), wh.data_ptr(), wm.data_ptr(), f
-            p.att_vec, p.ln_weight, p.ln_bias = _ptr_array(vecs), _ptr_array(lnw), _ptr_array(lnb)
-            p.att_mix = mix.data_ptr()
-            p.out, p.ld_out = out.data_ptr(), out.stride(0)
-            p.pre, p.ld_pre = pre.data_ptr(), pre.stride(0)
-            p.att = att.data_ptr()
-            p.zlh, p.ld_zlh = zlh.data_ptr(), zlh.stride(0)
-            p.zi, p.ld_zi = zi.data_ptr(), zi.stride(0)
-            if ops.implicit:
-                p.row_scale = ops.row_scale.data_ptr()
-            set_post(p)
-            nbytes = C.c_size_t()
-            _lib.check(lib.acm_conv_acmii_fwd_workspace_bytes(ops.low.handle, C.byref(nbytes)), "acm_conv_acmii_fwd_workspace_bytes")
-            ws = torch.empty(max(nbytes.value // 4, 1), dtype=_F32, device=dev)
-            # The mask form (acm_conv_acmii_v.hip): relu(x_j W) = m_j * (x_j W), so the aggregate is W contracted with
-            # V_i = sum_j m_j (x) x_j -- a product over the neighbour index on the bf16 matrix pipe, exact operands -- and the
-            # weight gradients are the same V contracted with dH: no transposed product for them (the structure channel's
-            # parameter keeps its one F-wide transposed product).  A pattern-only operator over this process's own rows, no
-            # gradient into x.
-            ctx.mask_table = None
-            st = 4
-            if (ops.implicit and not ctx.needs_input_grad[0] and n > 0 and xg.shape[0] == ops.low.n_cols
-                    and (tuning.HOST.rewrites & tuning.REWRITE_ACMII_MASK) != 0
-                    and (getattr(ops.low, "item_stream_waves", 0) > 0         # one-off per operator (synchronises: never
-                         or (not _capturing(dev) and ops.low.build_item_streams()))):     # inside a capture, whose warm-up built them)
-                # the table covers every column of the operator: this process's rows, or (row-sharded) the all-gathered input --
-                # each rank evaluates the masks of its halo itself, and its backward then needs NO all-gather of gradients
-                ng = xg.shape[0]
-                tb = C.c_size_t()
-                _lib.check(lib.acm_acmii_table_bytes(ng, C.byref(tb)), "acm_acmii_table_bytes")
-                table = torch.empty(tb.value // 4, dtype=torch.int32, device=dev)
-                with _device_ctx(dev), _Timed(f"acmii_table/{ng}x{f_in}"):
-                    st = lib.acm_acmii_table(ng, f_in, xg.data_ptr(), xg.stride(0), wl.data_ptr(), wh.data_ptr(), f,
-                                             table.data_ptr(), tb.value, _stream())
-                if st == 0:
-                    if ops.low.n_long_rows == 0:          # only the fix-up of long rows reads zlh (its high-pass half)
-                        p.zlh, p.ld_zlh = None, 0
-                    with _device_ctx(dev), _Timed(f"conv_acmii_v_fwd/F{f}i{f_in}"):
-                        st = lib.acm_conv_acmii_v_fwd(ops.low.handle, C.byref(p), table.data_ptr(), _vp(ws), ws.numel() * 4, _stream())
-                    if st == 0:
-                        ctx.mask_table, ctx.mask_x = table, xpad
-                        ctx.mask_self_offset = 0
-                        if ops.sharded:                   # this rank's rows inside the gathered numbering (_gather_rows)
-                            import torch.distributed as dist
-                            ctx.mask_self_offset = dist.get_rank(ops.group) * (ops.n_gathered // dist.get_world_size(ops.group))
-                    else:
-                        p.zlh, p.ld_zlh = zlh.data_ptr(), zlh.stride(0)
-                if st not in (0, 4):                      # 4 = ACM_EUNSUPPORTED: the fp32 kernel below
-                    _lib.check(st, "acm_conv_acmii_v_fwd")
-            if ctx.mask_table is None:
-                with _device_ctx(dev), _Timed(f"conv_acmii_fwd/F{f}i{f_in}"):
-                    st = lib.acm_conv_acmii_fwd(ops.low.handle, C.byref(p), _vp(ws), ws.numel() * 4, _stream())
-                _lib.check(st, "acm_conv_acmii_fwd")
-            ctx.agg_first, ctx.tail, ctx.sparse_x = False, None, None
-            ctx.ops, ctx.cfg = ops, cfg
-            ctx.save_for_backward(x, *w3, zlh, zi, pre, mix, *vecs, *lnw, *lnb)
-            ctx.mark_non_differentiable(att)
-            return out, att
-        if ctx.agg_first:
-            p = _lib.ConvAggFwd()
-            p.f_in, p.f_pad, p.f_out = f_in, fp, f
-            p.relu_after, p.relu_mlp, p.layernorm, p.scale = int(cfg.relu_after), int(cfg.relu_mlp), int(cfg.layernorm), cfg.scale
-            p.xg, p.ld_xg = xg.data_ptr(), xg.stride(0)
-            p.xs, p.ld_xs = xpad.data_ptr(), xpad.stride(0)
-            p.w_low, p.w_high, p.w_mlp, p.ld_w = wl.data_ptr(), wh.data_ptr(), wm.data_ptr(), f
-            p.att_vec, p.ln_weight, p.ln_bias = _ptr_array(vecs), _ptr_array(lnw), _ptr_array(lnb)
-            p.att_mix = mix.data_ptr()
-            agg = agg_given if agg_given is not None else torch.empty(n, fp, dtype=_F32, device=dev)
-            p.agg_given = int(agg_given is not None)
-            refill = False
-            if ctx.pipe is not None:                  # the backward's operands: copies the row-local kernel leaves
-                p.agg_copy, p.ld_agg_copy = ctx.pipe.saved[1].data_ptr(), ctx.pipe.saved[1].stride(0)
-                p.xs_copy, p.ld_xs_copy = ctx.pipe.saved[0].data_ptr(), ctx.pipe.saved[0].stride(0)
-                # ... and (one device: the table IS this rank's rows) it refills the table with dropout_{t+1}(x) over the rows
-                # it has just copied: make_next()'s acm_dropout launch is gone
-                refill = ctx.pipe.refill_spec(p)
-            p.out, p.ld_out = out.data_ptr(), out.stride(0)
-            p.agg, p.ld_agg = agg.data_ptr(), agg.stride(0)
-            p.att = att.data_ptr()
-            p.n_channels = k
-            if ops.implicit:
-                p.row_scale = ops.row_scale.data_ptr()
-            extra = ()
-            if four:                                  # pre_S = deg * (A_low S) - S: one F-wide gather of S
-                ps = torch.empty(n, f, dtype=_F32, device=dev)
-                if cfg.gather_bf16 and f % 2 == 0 and f > 8:
-                    sgt = cast_bf16(s_gath)
-                    p.sg_bf16 = 1
-                else:
-                    sgt = s_gath
-                p.sg, p.ld_sg = sgt.data_ptr(), sgt.stride(0)
-                p.ss, p.ld_ss = s_local.data_ptr(), s_local.stride(0)
-                p.deg = ops.deg.data_ptr()
-                p.ps, p.ld_ps = ps.data_ptr(), ps.stride(0)
-                extra = (ps, s_local)
-            set_post(p)
-            # the row's head statistics (mean | rstd | sigmoid | alpha per channel): 16 k bytes per row that save
-            # the backward three 16-lane reductions per channel and row
-            stats = torch.empty(n, 4 * k, dtype=_F32, device=dev) if any(ctx.needs_input_grad) else None
-            if stats is not None:
-                p.head_stats, p.ld_head_stats = stats.data_ptr(), stats.stride(0)
-            ctx.head_stats = stats
-            # (the row-local stage is a kernel of its own when P is given, and always with the structure channel)
-            nxt = _next_proj_request(call, f, dev, row_local_only=f == 64 and (agg_given is not None or four))
-            if nxt is not None:
-                n_w3, n_relu, f2, n_pack = nxt
-                n_zlh, _ = _narrow_tables(n, f2, f2, dev, n_pack)
-                n_zi = torch.empty(n, f2, dtype=_F32, device=dev)
-                p.next_w_low, p.next_w_high, p.next_w_mlp = (w.data_ptr() for w in n_w3)
-                p.next_ld_w, p.next_f, p.next_relu = n_w3[0].stride(0), f2, int(n_relu)
-                p.next_zlh, p.ld_next_zlh = n_zlh.data_ptr(), n_zlh.stride(0)
-                p.next_zi, p.ld_next_zi = n_zi.data_ptr(), n_zi.stride(0)
-            ws = ops.low.workspace(max(fp, f) if four else fp)
-            with _device_ctx(dev), _Timed(f"conv_agg_{'epi' if agg_given is not None else 'fwd'}/F{f}k{k}i{f_in}"):
-                st = lib.acm_conv_agg_fwd(ops.low.handle, C.byref(p), _vp(ws), ws.numel() * 4, _stream())
-            _lib.check(st, "acm_conv_agg_fwd")
-            if refill:
-                ctx.pipe.next_table_ready = True
-            if agg_holder is not None and agg_given is None:
-                agg_holder["agg"] = agg
-            if nxt is not None:
-                call.pre_proj = (out, n_zlh, n_zi, tuple(w.data_ptr() for w in n_w3), n_relu)
-            ctx.ops, ctx.cfg, ctx.f_in = ops, cfg, f_in
-            # with a fused ReLU the output itself records which elements the post-op let through: the backward reads it
-            # instead of regenerating the dropout mask (no extra memory: the next layer keeps the same tensor alive)
-            ctx.out_mask = bool(ctx.post_relu) and ctx.post_scale is None
-            if ctx.pipe is not None:
-                xpad, agg = ctx.pipe.saved[0], ctx.pipe.saved[1]
-            ctx.save_for_backward(xpad, agg, wl, wh, wm, mix, *vecs, *lnw, *lnb, *extra, *((out,) if ctx.out_mask else ()))
-            ctx.mark_non_differentiable(att)
-            return out, att
         pre = torch.empty(n, (k - 1) * f, dtype=_F32, device=dev)
         p = _lib.ConvFwd()
         p.f_out, p.n_channels = f, k
@@ -1850,7 +2148,7 @@ class AcmConvFunction(torch.autograd.Function):
                 p.g_struc, p.ld_g_struc = ps.data_ptr(), ps.stride(0)
                 p.s_struc, p.ld_s_struc = zero.data_ptr(), zero.stride(0)
                 p.deg = ones.data_ptr()
-            keep_alive = (pl, ph, zero) + ((ps, ones) if four else ())
+            keep_alive = (pl, ph, zero) + ((ps, ones) if four else ())      # noqa: F841  (until the launch below)
         else:
             if cfg.gather_bf16 and 8 < f <= 64 and f % 2 == 0:
                 # bf16 copy of the gathered operand(s): half the gather bytes, fp32 accumulation; the self rows
@@ -1884,43 +2182,17 @@ class AcmConvFunction(torch.autograd.Function):
         p.out, p.ld_out = out.data_ptr(), out.stride(0)
         p.pre, p.ld_pre = pre.data_ptr(), pre.stride(0)
         p.att = att.data_ptr()
-        set_post(p)
+        _set_post(p, ctx.post_relu, post_scale, ctx.post_drop, ops.row_offset)
         ws = graph.workspace((k - 1) * f)
         # output layer + loss + K3 in one row pass (acm_conv_fwd_tail) when a training loop asked for it
-        tail_req, layer_ok = call.tail, bool(tail_layer)
+        tail_req = call.tail
         ctx.tail = None
         st = None
-        if (tail_req is not None and tail_req.out is None and layer_ok and not general and k == 3 and f <= 8
+        if (tail_req is not None and tail_req.out is None and tail_layer and not general and k == 3 and f <= 8
                 and not cfg.gather_bf16 and not post_relu and post_scale is None and post_drop is None
                 and any(ctx.needs_input_grad) and tail_req.labels.numel() == n
                 and (graph.n_long_rows == 0 or 12.0 < graph.nnz / max(graph.n_rows, 1) <= 160.0)):
-            dlog = torch.empty(n, f, dtype=_F32, device=dev)
-            st3 = _k3_setup(cfg, ops, k, f, n, dev, w3[0].shape[0], pre, zi, vecs, lnw, lnb, mix, dlog, False, None, None,
-                            fb=fb)
-            loss = torch.empty((), dtype=_F32, device=dev)
-            lo = _lib.Loss()
-            lo.n_classes = f
-            y = tail_req.labels.to(torch.int64).contiguous().reshape(-1)
-            w_row = _as_f32c(tail_req.row_weight, "row_weight")
-            lo.labels, lo.row_weight = y.data_ptr(), w_row.data_ptr()
-            lo.loss, lo.dlogits, lo.ld_dlogits = loss.data_ptr(), dlog.data_ptr(), dlog.stride(0)
-            q = st3["q"]
-            q.defer = call.defer_ptr()
-            nbytes = C.c_size_t()
-            if lib.acm_conv_fwd_tail_workspace_bytes(n, f, k, C.byref(nbytes)) == 0:
-                wt = torch.empty(max(nbytes.value // 4, 1), dtype=_F32, device=dev)
-                with _device_ctx(dev), _Timed(f"conv_fwd_tail/F{f}k{k}"):
-                    st = lib.acm_conv_fwd_tail(graph.handle, C.byref(p), C.byref(lo), C.byref(q), _vp(ws), ws.numel() * 4,
-                                               _vp(wt), nbytes.value, _stream())
-                if st == 0:
-                    st3["keep"] = (y, w_row, wt)
-                    ctx.tail = st3
-                    tail_req.loss, tail_req.dz, tail_req.out = loss, dlog, out
-                    if call.defer is not None:
-                        call.defer.hold(wt, [loss, st3["d_mix"], *st3["d_vec"], *st3["d_lnw"], *st3["d_lnb"]],
-                                        keep=[loss, st3["flat"]])
-                elif st != 4:                       # ACM_EUNSUPPORTED: the layer does not qualify, three calls then
-                    _lib.check(st, "acm_conv_fwd_tail")
+            st = _fwd_tail(ctx, ops, cfg, graph, p, ws, tail_req, w3, pre, zi, vecs, lnw, lnb, mix, out)
         if st != 0:
             with _device_ctx(dev), _Timed(f"conv_fwd/F{f}k{k}"):
                 st = lib.acm_conv_fwd(graph.handle, C.byref(p), _vp(ws), ws.numel() * 4, _stream())
@@ -1943,8 +2215,6 @@ class AcmConvFunction(torch.autograd.Function):
         if (call.hidden_private is x and prod is not None and getattr(prod, "agg_first", False) and getattr(prod, "call", None) is call
                 and not zero_padded and hops == 1 and call.defer is not None):
             ctx.lazy_producer = prod
-        if ctx.in_drop is not None and not (getattr(ctx, "in_drop_used", False) or getattr(ctx, "in_drop_materialised", False)):
-            raise RuntimeError("acm_conv: the caller's input dropout (in_drop) was not applied by any projection path")
         ctx.save_for_backward(w3[0] if sparse_x else x, *w3, zlh, zi, pre, mix, *vecs, *lnw, *lnb)
         ctx.mark_non_differentiable(att)
         return out, att
@@ -1952,346 +2222,190 @@ class AcmConvFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out, _grad_att):
         if grad_out is None:
-            return (None,) * 27
-        lib = _lib.load()
-        ops, cfg = ctx.ops, ctx.cfg
-        defer = ctx.call.defer                    # the deferral list of the model call this backward belongs to
-        k = cfg.n_channels
-        saved = ctx.saved_tensors
-        if ctx.agg_first:
-            return AcmConvFunction._backward_agg(ctx, grad_out)
-        x, wl_, wh_, wm_, zlh, zi, pre, mix = saved[:8]
-        w3 = (wl_, wh_, wm_)
-        vecs = list(saved[8:8 + k])
-        lnw = list(saved[8 + k:8 + 2 * k]) if cfg.layernorm else []
-        lnb = list(saved[8 + 2 * k:8 + 3 * k]) if cfg.layernorm else []
-        dev = zlh.device
-        n, f = zlh.shape[0], wl_.shape[1]
-        grad_out = _as_f32c(grad_out, "grad_out")
-        four = k == 4
-
-        f_in_w = wl_.shape[0]
-        tail = getattr(ctx, "tail", None)
-        done = tail is not None and grad_out.data_ptr() == tail["grad_out"].data_ptr()
-        fb = getattr(ctx, "fb", f)
-        st3 = tail if done else _k3_setup(cfg, ops, k, f, n, dev, f_in_w, pre, zi, vecs, lnw, lnb, mix, grad_out,
-                                          ctx.post_relu, ctx.post_scale, ctx.post_drop, fb=fb)
-        q, g, dz, gs, flat, nw = st3["q"], st3["g"], st3["dz"], st3["gs"], st3["flat"], st3["nw"]
-        general, ones = st3["general"], st3["ones"]
-        if done:
-            ctx.tail = None
-        elif getattr(ctx, "mask_table", None) is not None:
-            q.g_scale = None                     # the mask form's backward scales by 1 / d_i itself: G_L, G_H as they are
-        d_vec, d_lnw, d_lnb, d_mix = _flat_views(flat, nw, k, f, cfg.layernorm)    # this call's own view objects
-        del st3, tail
-        if not done:                 # else: acm_conv_fwd_tail already ran K3 with exactly this gradient
-            nbytes = C.c_size_t()
-            _lib.check(lib.acm_conv_bwd_local_workspace_bytes(n, f, k, C.byref(nbytes)))
-            ws = torch.empty(max(nbytes.value // 4, 1), dtype=_F32, device=dev)
-            q.defer = defer.pointer() if defer is not None else None
-            with _device_ctx(dev), _Timed(f"conv_bwd_local/F{f}k{k}"):
-                st = lib.acm_conv_bwd_local(n, C.byref(q), _vp(ws), ws.numel() * 4, _stream())
-            _lib.check(st, "acm_conv_bwd_local")
-            if defer is not None:
-                defer.hold(ws, [d_mix, *d_vec, *d_lnw, *d_lnb], keep=[flat])
-
-        table = getattr(ctx, "mask_table", None)
-        if table is not None:
-            # the mask form's backward: dW_L, dW_H straight from dH_L, dH_H (K3's g) over the FORWARD operator and the
-            # forward's table, and the row-local dW_I = X^T dZ_I in the same launch
-            d_wcat = flat[:nw].view(3, f_in_w, f)
-            xt = ctx.mask_x
-            b = _lib.ConvAcmiiBwd()
-            b.f_in, b.table = f_in_w, table.data_ptr()
-            b.g_low, b.ld_g_low = g.data_ptr(), g.stride(0)
-            b.g_high, b.ld_g_high = g.data_ptr() + 4 * fb, g.stride(0)
-            b.g_mlp, b.ld_g_mlp = dz.data_ptr() + 8 * f, dz.stride(0)
-            b.x, b.ld_x = xt.data_ptr(), xt.stride(0)
-            b.self_offset = ctx.mask_self_offset
-            b.row_scale = ops.row_scale.data_ptr()
-            b.d_w_low, b.d_w_high, b.d_w_mlp, b.ld_dw = d_wcat[0].data_ptr(), d_wcat[1].data_ptr(), d_wcat[2].data_ptr(), f
-            b.defer = defer.pointer() if defer is not None else None
-            nbytes = C.c_size_t()
-            _lib.check(lib.acm_conv_acmii_v_bwd_workspace_bytes(ops.low.handle, C.byref(nbytes)), "acm_conv_acmii_v_bwd_workspace_bytes")
-            wsb = torch.empty(max(nbytes.value // 4, 1), dtype=_F32, device=dev)
-            with _device_ctx(dev), _Timed(f"conv_acmii_v_bwd/F{f}i{f_in_w}"):
-                st = lib.acm_conv_acmii_v_bwd(ops.low.handle, C.byref(b), _vp(wsb), wsb.numel() * 4, _stream())
-            _lib.check(st, "acm_conv_acmii_v_bwd")
-            if defer is not None:
-                defer.hold(wsb, [d_wcat[0], d_wcat[1], d_wcat[2]], keep=[flat, table, g, dz, xt])
-            d_struc = None
-            if four:                                  # dS = A_low^T (D G_S) - G_S = P G_S - G_S (pattern-only; K3 left G_S unscaled)
-                d_struc = torch.empty(n, f, dtype=_F32, device=dev)
-                low_t = ops.low_t
-                ws2 = low_t.workspace(f)
-                o = _lib.SpmmOpts()
-                o.sub, o.ld_sub = gs.data_ptr(), gs.stride(0)
-                gsg = _gather_rows(ops, gs)
-                if cfg.gather_bf16 and 8 < f <= 64 and f % 2 == 0:       # bf16 gathered operand (the self term stays fp32)
-                    gsg = cast_bf16(gsg)
-                    o.g_bf16 = 1
-                with _device_ctx(dev), _Timed(f"spmm_sub/{f}"):
-                    st = lib.acm_spmm_ex(low_t.handle, _vp(gsg), gsg.stride(0), f, _vp(d_struc), d_struc.stride(0),
-                                         C.byref(o), _vp(ws2), ws2.numel() * 4, _stream())
-                _lib.check(st, "acm_spmm_ex")
-            if ops.sharded:                             # replicated parameters: sum the row-shard partials
-                import torch.distributed as dist
-                if defer is not None:
-                    defer.allreduce(flat, ops.group)    # after the step's single flush (the all-reduce reads its sums)
-                else:
-                    dist.all_reduce(flat, group=ops.group)
-            none4 = [None] * 4
-            grads_vec = d_vec + [None] * (4 - k)
-            grads_lnw = (d_lnw + [None] * (4 - k)) if cfg.layernorm else none4
-            grads_lnb = (d_lnb + [None] * (4 - k)) if cfg.layernorm else none4
-            return (None, d_wcat[0], d_wcat[1], d_wcat[2], grads_vec[0], grads_vec[1], grads_vec[2], grads_vec[3],
-                    d_struc, d_mix, *grads_lnw, *grads_lnb, None, None, None, None, None, None, None, None, None)
-
-        d_struc = torch.empty(n, f, dtype=_F32, device=dev) if four else None
-        r = _lib.ConvBwdSpmm()
-        r.f_out, r.row_offset = f, ops.row_offset
-        if general:
-            # transposed products channel by channel, then the fused kernel over the identity operator applies the
-            # ACMII masks: dZ_L = m*(1*T_L), dZ_H = m*(T_H - 1*0), dS = 1*T_S - 0
-            t_l = spmm(ops.low.transpose(), g[:, :f])
-            t_h = spmm(ops.high.transpose(), g[:, fb:fb + f])
-            zero = ops.zeros(n, f)
-            low_t = ops.eye
-            r.g_low, r.ld_g_low = t_l.data_ptr(), t_l.stride(0)
-            r.g_high, r.ld_g_high = zero.data_ptr(), zero.stride(0)
-            r.s_high, r.ld_s_high = t_h.data_ptr(), t_h.stride(0)
-            if four:
-                t_s = spmm(ops.un.transpose(), gs)
-                r.g_struc, r.ld_g_struc = t_s.data_ptr(), t_s.stride(0)
-                r.s_struc, r.ld_s_struc = zero.data_ptr(), zero.stride(0)
-                r.inv_deg = ones.data_ptr()
-                r.d_struc, r.ld_d_struc = d_struc.data_ptr(), d_struc.stride(0)
-        else:
-            gg = _gather_rows(ops, g)
-            gsg = _gather_rows(ops, gs) if four else None
-            low_t = ops.low_t
-            if cfg.gather_bf16 and 8 < f <= 64 and f % 2 == 0 and fb == f:
-                # bf16 copies of the gathered gradient tables: half the bytes of the fabric-bound transposed products (the
-                # self terms and every sum stay fp32); opt-in, BASELINE config 3's tolerance
-                gb = cast_bf16(gg[:, : 2 * f])
-                r.gather_bf16 = 1
-                r.g_low, r.ld_g_low = gb.data_ptr(), gb.stride(0)
-                r.g_high, r.ld_g_high = gb.data_ptr() + 2 * f, gb.stride(0)
-                if four:
-                    gsb = cast_bf16(gsg)
-                    gsg = gsb
-            else:
-                r.g_low, r.ld_g_low = gg.data_ptr(), gg.stride(0)
-                r.g_high, r.ld_g_high = gg.data_ptr() + 4 * fb, gg.stride(0)
-            r.s_high, r.ld_s_high = g.data_ptr() + 4 * fb, g.stride(0)
-            if four:
-                r.g_struc, r.ld_g_struc = gsg.data_ptr(), gsg.stride(0)
-                r.s_struc, r.ld_s_struc = gs.data_ptr(), gs.stride(0)
-                r.inv_deg = None if ops.implicit else ops.inv_deg.data_ptr()
-                r.d_struc, r.ld_d_struc = d_struc.data_ptr(), d_struc.stride(0)
-            if ops.implicit:
-                r.self_scale = ops.self_scale.data_ptr()
-        if cfg.relu_before:                       # ACMII: ReLU mask of the projected features
-            r.mask_low, r.ld_mask_low = zlh.data_ptr(), zlh.stride(0)
-            r.mask_high, r.ld_mask_high = zlh.data_ptr() + 4 * fb, zlh.stride(0)
-        r.dz_low, r.ld_dz_low = dz.data_ptr(), dz.stride(0)
-        r.dz_high, r.ld_dz_high = dz.data_ptr() + 4 * f, dz.stride(0)
-        ws2 = low_t.workspace((k - 1) * f)
-        with _device_ctx(dev), _Timed(f"conv_bwd_spmm/F{f}k{k}"):
-            st = lib.acm_conv_bwd_spmm(low_t.handle, C.byref(r), _vp(ws2), ws2.numel() * 4, _stream())
-        _lib.check(st, "acm_conv_bwd_spmm")
-        if ctx.hops > 2 and ops.implicit:
-            # the remaining k - 1 >= 2 transposed hops of the low channel with a pattern-only operator:
-            # (P D^-1)^(k-1) t = P [D^-1 P]^(k-2) (D^-1 t) -- ONE input scaling, then k - 2 row-scaled products (the forward's
-            # form) and a final plain one written over dZ_L (it reads a hop buffer), instead of a scaling pass per hop
-            sc = _hop_buffer(dz, f)
-            torch.mul(dz[:, :f], ops.row_scale[:, None], out=sc)
-            for hop in range(ctx.hops - 2):
-                sc = spmm(ops.low_t, _gather_rows(ops, sc), out=_hop_buffer(dz, f), row_scale=ops.row_scale)
-            spmm(ops.low_t, _gather_rows(ops, sc), out=dz[:, :f])
-        elif ctx.hops > 1:                                # the remaining k-1 transposed hops of the low channel
-            t = dz[:, :f]
-            last = ctx.hops - 2
-            for hop in range(ctx.hops - 1):               # the last hop writes dZ_L in place unless it reads it
-                t = _low_product(ops, t, transpose=True, out=dz[:, :f] if (hop == last and hop > 0) else None)
-            if last == 0:
-                dz[:, :f] = t
-
-        if ctx.sparse_x is not None:                                          # dWcat = X_csr^T dZ
-            xs = ctx.sparse_x
-            xt = xs.csr_t
-            d_wcat = spmm_v(xt, xs.values.index_select(0, xt.src_pos), dz, out=flat[:nw].view(f_in_w, 3 * f))
-            d_x = None
-        elif (ctx.needs_input_grad[0] and proj_bwd_supported(3 * f)
-              and wl_.stride(0) == wh_.stride(0) == wm_.stride(0)):
-            d_wcat = flat[:nw].view(3, f_in_w, f)                             # narrow output layer: dX and dW in one
-            prod = getattr(ctx, "lazy_producer", None)
-            if (prod is not None and f <= 2 and f_in_w == 64 and x.shape[1] == 64 and getattr(prod, "lazy", None) is None
-                    and all(w.stride(0) == f and w.is_contiguous() for w in w3)):
-                # ... left to the producing layer's backward kernel: the placeholder is what autograd carries there
-                d_x = torch.empty(n, x.shape[1], dtype=_F32, device=dev)
-                prod.lazy = dict(dz=dz, w3=w3, d_w=d_wcat, x=x, placeholder=d_x)
-            else:
-                d_x = proj_bwd(x, dz, w3, d_wcat, defer=defer)                # pass over x (acm_proj_bwd)
-        else:
-            d_wcat = gemm(x, dz, trans_a=True, col_blocks=3,
-                          out=flat[:nw].view(3, f_in_w, f),                   # contiguous per weight
-                          a_drop=_drop_spec(ctx.in_drop, ops.row_offset) if getattr(ctx, "in_drop_used", False) else None)
-            d_x = gemm(dz, torch.cat(w3, dim=1), trans_b=True) if ctx.needs_input_grad[0] else None
-        if d_x is not None and d_x.shape[1] != ctx.x_width:
-            d_x = torch.nn.functional.pad(d_x, (0, ctx.x_width - d_x.shape[1]))
-        if ops.sharded:                             # replicated parameters: sum the row-shard partials
-            import torch.distributed as dist
-            if defer is not None:
-                defer.allreduce(flat, ops.group)    # after the step's single flush (the all-reduce reads its sums)
-            else:
-                dist.all_reduce(flat, group=ops.group)
-        if d_wcat.dim() == 3:
-            d_wl, d_wh, d_wm = d_wcat[0], d_wcat[1], d_wcat[2]
-        else:
-            d_wl, d_wh, d_wm = (d_wcat[:, i * f:(i + 1) * f] for i in range(3))
-        none4 = [None] * 4
-        grads_vec = d_vec + [None] * (4 - k)
-        grads_lnw = (d_lnw + [None] * (4 - k)) if cfg.layernorm else none4
-        grads_lnb = (d_lnb + [None] * (4 - k)) if cfg.layernorm else none4
-        return (d_x, d_wl, d_wh, d_wm, grads_vec[0], grads_vec[1], grads_vec[2], grads_vec[3],
-                d_struc, d_mix, *grads_lnw, *grads_lnb, None, None, None, None, None, None, None, None, None)
+            return _NO_GRADS
+        return _literal_backward(ctx, grad_out)
 
 
-def _backward_agg(ctx, grad_out):
-    """Backward of the aggregate-first forward: one row-local kernel and no SpMM for the three
-    filterbank channels; the structure channel (k = 4) adds one F-wide transposed product for
-    d struc_low.  Collectives: the all-reduce of the replicated-parameter gradients, plus the
-    all-gather of D*G_S when sharded with k = 4."""
-    lib = _lib.load()
-    ops, cfg, f_in = ctx.ops, ctx.cfg, ctx.f_in
-    k = cfg.n_channels
-    four = k == 4
-    saved = ctx.saved_tensors
-    out_fwd = None
-    if getattr(ctx, "out_mask", False):
-        out_fwd, saved = saved[-1], saved[:-1]
-    xpad, agg, wl, wh, wm, mix = saved[:6]
-    vecs = list(saved[6:6 + k])
-    nln = k if cfg.layernorm else 0
-    lnw = list(saved[6 + k:6 + k + nln])
-    lnb = list(saved[6 + k + nln:6 + k + 2 * nln])
-    dev = xpad.device
-    n, f, fp = xpad.shape[0], wl.shape[1], xpad.shape[1]
-    lazy, ctx.lazy = getattr(ctx, "lazy", None), None
-    if lazy is not None and (grad_out is not lazy["placeholder"] and grad_out.data_ptr() != lazy["placeholder"].data_ptr()):
-        raise RuntimeError("acm_conv: the hidden activation marked private (CallContext.hidden_private) received a gradient "
-                           "from somewhere else as well")
-    fuse_proj = (lazy is not None and fp == 8 and f == 64 and out_fwd is not None and ctx.post_scale is None
-                 and getattr(ctx, "head_stats", None) is not None)
-    if lazy is not None and not fuse_proj:            # the kernel cannot take it: materialise dX and dW' now
-        proj_bwd(lazy["x"], lazy["dz"], lazy["w3"], lazy["d_w"], defer=ctx.call.defer, dx_out=lazy["placeholder"])
-        lazy = None
-    grad_out = _as_f32c(grad_out, "grad_out")
-    npg = 3 * f_in * f + 3 * k * f + k * k
-    d_params = torch.empty(npg, dtype=_F32, device=dev)
-    q = _lib.ConvAggBwd()
-    q.f_in, q.f_pad, q.f_out = f_in, fp, f
-    q.relu_after, q.relu_mlp, q.layernorm, q.scale = int(cfg.relu_after), int(cfg.relu_mlp), int(cfg.layernorm), cfg.scale
-    q.grad_out, q.ld_grad_out = grad_out.data_ptr(), grad_out.stride(0)
-    if lazy is not None:                              # the following layer's projection backward rides this launch
-        dz2, w32 = lazy["dz"], lazy["w3"]
-        q.grad_out = None
-        q.proj_dz, q.ld_proj_dz = dz2.data_ptr(), dz2.stride(0)
-        q.proj_w_low, q.proj_w_high, q.proj_w_mlp = (w.data_ptr() for w in w32)
-        q.proj_ld_w, q.proj_f = w32[0].stride(0), w32[0].shape[1]
-        q.proj_d_w = lazy["d_w"].data_ptr()
-    q.agg, q.ld_agg = agg.data_ptr(), agg.stride(0)
-    if getattr(ctx, "head_stats", None) is not None:
-        q.head_stats, q.ld_head_stats = ctx.head_stats.data_ptr(), ctx.head_stats.stride(0)
-    q.xs, q.ld_xs = xpad.data_ptr(), xpad.stride(0)
-    q.w_low, q.w_high, q.w_mlp, q.ld_w = wl.data_ptr(), wh.data_ptr(), wm.data_ptr(), f
-    q.att_vec, q.ln_weight, q.ln_bias = _ptr_array(vecs), _ptr_array(lnw), _ptr_array(lnb)
-    q.att_mix = mix.data_ptr()
-    q.d_params = d_params.data_ptr()
-    q.post_relu = int(ctx.post_relu)
-    q.n_channels = k
-    if ctx.post_scale is not None:
-        q.post_scale, q.ld_post_scale = ctx.post_scale.data_ptr(), ctx.post_scale.stride(0)
-    spec = _drop_spec(ctx.post_drop, ops.row_offset)
-    if spec is not None:
-        q.post_drop = spec
-    if out_fwd is not None:
-        q.out, q.ld_out = out_fwd.data_ptr(), out_fwd.stride(0)
-    if four:
-        ps, s_local = saved[-2], saved[-1]
-        gs = torch.empty(n, f, dtype=_F32, device=dev)            # D * dL/dpre_S
-        q.ps, q.ld_ps = ps.data_ptr(), ps.stride(0)
-        q.ss, q.ld_ss = s_local.data_ptr(), s_local.stride(0)
-        q.deg = ops.deg.data_ptr()
-        q.g_struc, q.ld_g_struc = gs.data_ptr(), gs.stride(0)
-        q.g_struc_scale = None if ops.implicit else ops.deg.data_ptr()
+def _fwd_tail(ctx, ops, cfg, graph, p, ws, tail_req, w3, pre, zi, vecs, lnw, lnb, mix, out):
+    """acm_conv_fwd_tail: the output layer's K2, the loss the training loop asked for (call.tail) and K3 in one row pass;
+    returns its status (None: no workspace for it; 4 = ACM_EUNSUPPORTED: the layer does not qualify, three calls then)."""
+    lib, call = _lib.load(), ctx.call
+    (n, f), k, dev = out.shape, cfg.n_channels, out.device
+    dlog = torch.empty(n, f, dtype=_F32, device=dev)
+    st3 = _k3_setup(cfg, ops, k, f, n, dev, w3[0].shape[0], pre, zi, vecs, lnw, lnb, mix, dlog, False, None, None, fb=ctx.fb)
+    loss = torch.empty((), dtype=_F32, device=dev)
+    lo = _lib.Loss()
+    lo.n_classes = f
+    y = tail_req.labels.to(torch.int64).contiguous().reshape(-1)
+    w_row = _as_f32c(tail_req.row_weight, "row_weight")
+    lo.labels, lo.row_weight = y.data_ptr(), w_row.data_ptr()
+    lo.loss, lo.dlogits, lo.ld_dlogits = loss.data_ptr(), dlog.data_ptr(), dlog.stride(0)
+    q = st3["q"]
+    q.defer = call.defer_ptr()
     nbytes = C.c_size_t()
-    _lib.check(lib.acm_conv_agg_bwd_workspace_bytes(n, f_in, f, C.byref(nbytes)))
-    ws = torch.empty(max(nbytes.value // 4, 1), dtype=_F32, device=dev)
-    defer = ctx.call.defer
-    q.defer = defer.pointer() if defer is not None else None
-    pipe = getattr(ctx, "pipe", None)
-    carry = pipe is not None and pipe.next_table_ready and not pipe.next_agg_ready
-    if carry:                                     # the next step's P = A_low dropout(x) rides this launch
-        q.next_a = ops.low.handle
-        q.next_xg, q.ld_next_xg = pipe.table().data_ptr(), pipe.table().stride(0)
-        q.next_row_scale = ops.row_scale.data_ptr()
-        q.next_agg, q.ld_next_agg = pipe.agg().data_ptr(), pipe.agg().stride(0)
-    with _device_ctx(dev), _Timed(f"conv_agg_bwd{'+gather' if carry else ''}{'+proj' if lazy is not None else ''}/F{f}k{k}i{f_in}"):
-        st = lib.acm_conv_agg_bwd(n, C.byref(q), _vp(ws), ws.numel() * 4, _stream())
-    if st == 4 and (lazy is not None or carry):       # ACM_EUNSUPPORTED for this shape after all: the plain launch(es)
-        if lazy is not None:
-            proj_bwd(lazy["x"], lazy["dz"], lazy["w3"], lazy["d_w"], defer=defer, dx_out=lazy["placeholder"])
-            q.grad_out, q.proj_dz, lazy = grad_out.data_ptr(), None, None
-        if carry:                                     # the gather as its own launch, right here: the pipeline stays valid
-            q.next_a, q.next_xg, q.next_row_scale, q.next_agg = None, None, None, None          # (also inside a capture, where
-            spmm(ops.low, pipe.table(), out=pipe.agg(), row_scale=ops.row_scale)                 # nobody could prime() it again)
-        with _device_ctx(dev), _Timed(f"conv_agg_bwd/F{f}k{k}i{f_in}"):
-            st = lib.acm_conv_agg_bwd(n, C.byref(q), _vp(ws), ws.numel() * 4, _stream())
-    _lib.check(st, "acm_conv_agg_bwd")
-    if carry:
-        pipe.next_agg_ready = True
-    if defer is not None:
-        defer.hold(ws, [d_params] + ([lazy["d_w"]] if lazy is not None else []),
-                   keep=[d_params] + ([lazy["d_w"]._base if lazy["d_w"]._base is not None else lazy["d_w"]] if lazy is not None else []))
-    d_struc = None
-    if four:                                  # dS = A_low^T (D G_S) - G_S   (pattern-only: P G_S - G_S)
-        gsg = _gather_rows(ops, gs)
-        low_t = ops.low_t
-        d_struc = torch.empty(n, f, dtype=_F32, device=dev)
-        ws2 = low_t.workspace(f)
-        o = _lib.SpmmOpts()
-        o.sub, o.ld_sub = gs.data_ptr(), gs.stride(0)
-        o.sub_scale = None if ops.implicit else ops.inv_deg.data_ptr()
-        if cfg.gather_bf16 and 8 < f <= 64 and f % 2 == 0:       # bf16 gathered operand (the self term stays fp32)
-            gsg = cast_bf16(gsg)
-            o.g_bf16 = 1
-        with _device_ctx(dev), _Timed(f"spmm_sub/{f}"):
-            st = lib.acm_spmm_ex(low_t.handle, _vp(gsg), gsg.stride(0), f, _vp(d_struc), d_struc.stride(0),
-                                 C.byref(o), _vp(ws2), ws2.numel() * 4, _stream())
-        _lib.check(st, "acm_spmm_ex")
-    if ops.sharded:
-        import torch.distributed as dist
+    if lib.acm_conv_fwd_tail_workspace_bytes(n, f, k, C.byref(nbytes)) != 0:
+        return None
+    wt = torch.empty(max(nbytes.value // 4, 1), dtype=_F32, device=dev)
+    with _device_ctx(dev), _Timed(f"conv_fwd_tail/F{f}k{k}"):
+        st = lib.acm_conv_fwd_tail(graph.handle, C.byref(p), C.byref(lo), C.byref(q), _vp(ws), ws.numel() * 4,
+                                   _vp(wt), nbytes.value, _stream())
+    if st == 0:
+        st3["keep"] = (y, w_row, wt)
+        ctx.tail = st3
+        tail_req.loss, tail_req.dz, tail_req.out = loss, dlog, out
+        if call.defer is not None:
+            call.defer.hold(wt, [loss, st3["d_mix"], *st3["d_vec"], *st3["d_lnw"], *st3["d_lnb"]], keep=[loss, st3["flat"]])
+    elif st != 4:
+        _lib.check(st, "acm_conv_fwd_tail")
+    return st
+
+
+def _k3_backward(ctx, grad_out):
+    """First stage of the backward of the literal layout (_AcmLiteral, and _AcmAcmii's): its saved tensors, and K3
+    (acm_conv_bwd_local) into the G tables, dZ and the flat buffer of the replicated-parameter gradients -- unless
+    acm_conv_fwd_tail already ran it with exactly this gradient.  Returns (x, w3, zlh, st3): st3 as _k3_setup's, holding
+    this call's own gradient views."""
+    lib = _lib.load()
+    ops, cfg, defer = ctx.ops, ctx.cfg, ctx.call.defer
+    k = cfg.n_channels
+    saved = ctx.saved_tensors
+    x, wl, wh, wm, zlh, zi, pre, mix = saved[:8]
+    vecs = list(saved[8:8 + k])
+    lnw = list(saved[8 + k:8 + 2 * k]) if cfg.layernorm else []
+    lnb = list(saved[8 + 2 * k:8 + 3 * k]) if cfg.layernorm else []
+    dev = zlh.device
+    n, f = zlh.shape[0], wl.shape[1]
+    grad_out = _as_f32c(grad_out, "grad_out")
+    tail = ctx.tail
+    done = tail is not None and grad_out.data_ptr() == tail["grad_out"].data_ptr()
+    st3 = tail if done else _k3_setup(cfg, ops, k, f, n, dev, wl.shape[0], pre, zi, vecs, lnw, lnb, mix, grad_out,
+                                      ctx.post_relu, ctx.post_scale, ctx.post_drop, fb=ctx.fb)
+    if done:
+        ctx.tail = None
+    elif getattr(ctx, "mask_table", None) is not None:
+        st3["q"].g_scale = None              # the mask form's backward scales by 1 / d_i itself: G_L, G_H as they are
+    d_vec, d_lnw, d_lnb, d_mix = _flat_views(st3["flat"], st3["nw"], k, f, cfg.layernorm)    # this call's own view objects
+    st3.update(d_vec=d_vec, d_lnw=d_lnw, d_lnb=d_lnb, d_mix=d_mix)
+    if not done:                 # else: acm_conv_fwd_tail already ran K3 with exactly this gradient
+        ws = _workspace(lib, dev, "acm_conv_bwd_local_workspace_bytes", n, f, k)
+        q = st3["q"]
+        q.defer = defer.pointer() if defer is not None else None
+        with _device_ctx(dev), _Timed(f"conv_bwd_local/F{f}k{k}"):
+            st = lib.acm_conv_bwd_local(n, C.byref(q), _vp(ws), ws.numel() * 4, _stream())
+        _lib.check(st, "acm_conv_bwd_local")
         if defer is not None:
-            defer.allreduce(d_params, ops.group)
-        else:
-            dist.all_reduce(d_params, group=ops.group)
-    wsz = f_in * f
-    d_wl, d_wh, d_wm = (d_params[i * wsz:(i + 1) * wsz].view(f_in, f) for i in range(3))
-    base = 3 * wsz
-    pad = [None] * (4 - k)
-    d_vec = [d_params[base + c * f: base + (c + 1) * f].view(f, 1) for c in range(k)] + pad
-    if cfg.layernorm:
-        d_lnw = [d_params[base + (k + c) * f: base + (k + 1 + c) * f] for c in range(k)] + pad
-        d_lnb = [d_params[base + (2 * k + c) * f: base + (2 * k + 1 + c) * f] for c in range(k)] + pad
+            defer.hold(ws, [d_mix, *d_vec, *d_lnw, *d_lnb], keep=[st3["flat"]])
+    return x, (wl, wh, wm), zlh, st3
+
+
+def _literal_backward(ctx, grad_out):
+    """Backward of the literal layout: K3 (_k3_backward) -> K4 acm_conv_bwd_spmm (the transposed products; ACMII: with the
+    ReLU masks of the projected features) [-> the k-hop chain's remaining transposed hops] -> K5 (dWcat = X^T dZ, dX)."""
+    x, w3, zlh, s = _k3_backward(ctx, grad_out)
+    lib = _lib.load()
+    ops, cfg, defer = ctx.ops, ctx.cfg, ctx.call.defer
+    g, dz, gs, flat, nw, ones = s["g"], s["dz"], s["gs"], s["flat"], s["nw"], s["ones"]
+    k, fb, dev = cfg.n_channels, ctx.fb, dz.device
+    four = k == 4
+    n, (f_in_w, f) = dz.shape[0], w3[0].shape
+    d_struc = torch.empty(n, f, dtype=_F32, device=dev) if four else None
+    r = _lib.ConvBwdSpmm()
+    r.f_out, r.row_offset = f, ops.row_offset
+    if s["general"]:
+        # transposed products channel by channel, then the fused kernel over the identity operator applies the
+        # ACMII masks: dZ_L = m*(1*T_L), dZ_H = m*(T_H - 1*0), dS = 1*T_S - 0
+        t_l = spmm(ops.low.transpose(), g[:, :f])
+        t_h = spmm(ops.high.transpose(), g[:, fb:fb + f])
+        zero = ops.zeros(n, f)
+        low_t = ops.eye
+        r.g_low, r.ld_g_low = t_l.data_ptr(), t_l.stride(0)
+        r.g_high, r.ld_g_high = zero.data_ptr(), zero.stride(0)
+        r.s_high, r.ld_s_high = t_h.data_ptr(), t_h.stride(0)
+        if four:
+            t_s = spmm(ops.un.transpose(), gs)
+            r.g_struc, r.ld_g_struc = t_s.data_ptr(), t_s.stride(0)
+            r.s_struc, r.ld_s_struc = zero.data_ptr(), zero.stride(0)
+            r.inv_deg = ones.data_ptr()
+            r.d_struc, r.ld_d_struc = d_struc.data_ptr(), d_struc.stride(0)
     else:
-        d_lnw = d_lnb = [None] * 4
-    d_mix = d_params[base + 3 * k * f:].view(k, k)
-    return (None, d_wl, d_wh, d_wm, *d_vec, d_struc, d_mix, *d_lnw, *d_lnb, None, None, None, None, None, None, None, None, None)
+        gg = _gather_rows(ops, g)
+        gsg = _gather_rows(ops, gs) if four else None
+        low_t = ops.low_t
+        if cfg.gather_bf16 and 8 < f <= 64 and f % 2 == 0 and fb == f:
+            # bf16 copies of the gathered gradient tables: half the bytes of the fabric-bound transposed products (the
+            # self terms and every sum stay fp32); opt-in, BASELINE config 3's tolerance
+            gb = cast_bf16(gg[:, : 2 * f])
+            r.gather_bf16 = 1
+            r.g_low, r.ld_g_low = gb.data_ptr(), gb.stride(0)
+            r.g_high, r.ld_g_high = gb.data_ptr() + 2 * f, gb.stride(0)
+            if four:
+                gsg = cast_bf16(gsg)
+        else:
+            r.g_low, r.ld_g_low = gg.data_ptr(), gg.stride(0)
+            r.g_high, r.ld_g_high = gg.data_ptr() + 4 * fb, gg.stride(0)
+        r.s_high, r.ld_s_high = g.data_ptr() + 4 * fb, g.stride(0)
+        if four:
+            r.g_struc, r.ld_g_struc = gsg.data_ptr(), gsg.stride(0)
+            r.s_struc, r.ld_s_struc = gs.data_ptr(), gs.stride(0)
+            r.inv_deg = None if ops.implicit else ops.inv_deg.data_ptr()
+            r.d_struc, r.ld_d_struc = d_struc.data_ptr(), d_struc.stride(0)
+        if ops.implicit:
+            r.self_scale = ops.self_scale.data_ptr()
+    if cfg.relu_before:                       # ACMII: ReLU mask of the projected features
+        r.mask_low, r.ld_mask_low = zlh.data_ptr(), zlh.stride(0)
+        r.mask_high, r.ld_mask_high = zlh.data_ptr() + 4 * fb, zlh.stride(0)
+    r.dz_low, r.ld_dz_low = dz.data_ptr(), dz.stride(0)
+    r.dz_high, r.ld_dz_high = dz.data_ptr() + 4 * f, dz.stride(0)
+    ws2 = low_t.workspace((k - 1) * f)
+    with _device_ctx(dev), _Timed(f"conv_bwd_spmm/F{f}k{k}"):
+        st = lib.acm_conv_bwd_spmm(low_t.handle, C.byref(r), _vp(ws2), ws2.numel() * 4, _stream())
+    _lib.check(st, "acm_conv_bwd_spmm")
+    if ctx.hops > 2 and ops.implicit:
+        # the remaining k - 1 >= 2 transposed hops of the low channel with a pattern-only operator:
+        # (P D^-1)^(k-1) t = P [D^-1 P]^(k-2) (D^-1 t) -- ONE input scaling, then k - 2 row-scaled products (the forward's
+        # form) and a final plain one written over dZ_L (it reads a hop buffer), instead of a scaling pass per hop
+        sc = _hop_buffer(dz, f)
+        torch.mul(dz[:, :f], ops.row_scale[:, None], out=sc)
+        for hop in range(ctx.hops - 2):
+            sc = spmm(ops.low_t, _gather_rows(ops, sc), out=_hop_buffer(dz, f), row_scale=ops.row_scale)
+        spmm(ops.low_t, _gather_rows(ops, sc), out=dz[:, :f])
+    elif ctx.hops > 1:                                # the remaining k-1 transposed hops of the low channel
+        t = dz[:, :f]
+        last = ctx.hops - 2
+        for hop in range(ctx.hops - 1):               # the last hop writes dZ_L in place unless it reads it
+            t = _low_product(ops, t, transpose=True, out=dz[:, :f] if (hop == last and hop > 0) else None)
+        if last == 0:
+            dz[:, :f] = t
 
-
-AcmConvFunction._backward_agg = staticmethod(_backward_agg)
+    if ctx.sparse_x is not None:                                          # dWcat = X_csr^T dZ
+        xs = ctx.sparse_x
+        xt = xs.csr_t
+        d_wcat = spmm_v(xt, xs.values.index_select(0, xt.src_pos), dz, out=flat[:nw].view(f_in_w, 3 * f))
+        d_x = None
+    elif (ctx.needs_input_grad[0] and proj_bwd_supported(3 * f)
+          and w3[0].stride(0) == w3[1].stride(0) == w3[2].stride(0)):
+        d_wcat = flat[:nw].view(3, f_in_w, f)                             # narrow output layer: dX and dW in one
+        prod = getattr(ctx, "lazy_producer", None)
+        if (prod is not None and f <= 2 and f_in_w == 64 and x.shape[1] == 64 and getattr(prod, "lazy", None) is None
+                and all(w.stride(0) == f and w.is_contiguous() for w in w3)):
+            # ... left to the producing layer's backward kernel: the placeholder is what autograd carries there
+            d_x = torch.empty(n, x.shape[1], dtype=_F32, device=dev)
+            prod.lazy = dict(dz=dz, w3=w3, d_w=d_wcat, x=x, placeholder=d_x)
+        else:
+            d_x = proj_bwd(x, dz, w3, d_wcat, defer=defer)                # pass over x (acm_proj_bwd)
+    else:
+        d_wcat = gemm(x, dz, trans_a=True, col_blocks=3,
+                      out=flat[:nw].view(3, f_in_w, f),                   # contiguous per weight
+                      a_drop=_drop_spec(ctx.in_drop, ops.row_offset) if getattr(ctx, "in_drop_used", False) else None)
+        d_x = gemm(dz, torch.cat(w3, dim=1), trans_b=True) if ctx.needs_input_grad[0] else None
+    if d_x is not None and d_x.shape[1] != ctx.x_width:
+        d_x = torch.nn.functional.pad(d_x, (0, ctx.x_width - d_x.shape[1]))
+    _reduce_replicated(flat, ops, defer)
+    if d_wcat.dim() == 3:
+        d_w3 = (d_wcat[0], d_wcat[1], d_wcat[2])
+    else:
+        d_w3 = tuple(d_wcat[:, i * f:(i + 1) * f] for i in range(3))
+    return _grads(d_x, d_w3, s["d_vec"], d_struc, s["d_mix"], s["d_lnw"], s["d_lnb"])
 
 
 # --------------------------------------------------------------------------
@@ -2344,8 +2458,9 @@ class _AcmAggWide(torch.autograd.Function):
               tensor): acm_conv_bwd_local (K3) -> 2 x acm_gemm TN ([P^T G_L | P^T G_H], [Xd^T G_H | Xd^T G_I])"""
 
     @staticmethod
-    def forward(ctx, x, w_low, w_high, w_mlp, v_low, v_high, v_mlp, att_mix, lnw_low, lnw_high, lnw_mlp, lnb_low, lnb_high,
-                lnb_mlp, ops, cfg, post_relu, post_scale, post_drop, call, in_drop, agg_holder=None):
+    def forward(ctx, x, w_low, w_high, w_mlp, v_low, v_high, v_mlp, v_struc, struc_low, att_mix, lnw_low, lnw_high, lnw_mlp,
+                lnw_struc, lnb_low, lnb_high, lnb_mlp, lnb_struc, ops, cfg, post_relu, post_scale, post_drop, call, tail_layer,
+                agg_holder, in_drop, pregathered):
         lib = _lib.load()
         ctx.set_materialize_grads(False)
         call = ctx.call = _call_or_ambient(call)
@@ -2385,10 +2500,8 @@ class _AcmAggWide(torch.autograd.Function):
             if agg_holder is not None:
                 agg_holder["agg"] = agg
         w3 = [_as_f32c(w, "weight") for w in (w_low, w_high, w_mlp)]
-        vecs = [_as_f32c(t, "att_vec") for t in (v_low, v_high, v_mlp)]
-        lnw = [_as_f32c(t, "ln") for t in (lnw_low, lnw_high, lnw_mlp)] if cfg.layernorm else []
-        lnb = [_as_f32c(t, "ln") for t in (lnb_low, lnb_high, lnb_mlp)] if cfg.layernorm else []
-        mix = _as_f32c(att_mix, "att_vec")
+        vecs, lnw, lnb, mix = _head_params(cfg, (v_low, v_high, v_mlp), att_mix, (lnw_low, lnw_high, lnw_mlp),
+                                           (lnb_low, lnb_high, lnb_mlp))
         if post_scale is not None:
             post_scale = _as_f32c(post_scale, "post_scale")
         ctx.post_relu, ctx.post_scale = bool(post_relu), post_scale
@@ -2406,12 +2519,7 @@ class _AcmAggWide(torch.autograd.Function):
         p.out, p.ld_out = out.data_ptr(), out.stride(0)
         p.pre, p.ld_pre = pre.data_ptr(), pre.stride(0)
         p.att = att.data_ptr()
-        p.post_relu = int(ctx.post_relu)
-        if post_scale is not None:
-            p.post_scale, p.ld_post_scale = post_scale.data_ptr(), post_scale.stride(0)
-        dspec = _drop_spec(ctx.post_drop, ops.row_offset)
-        if dspec is not None:
-            p.post_drop = dspec
+        _set_post(p, ctx.post_relu, post_scale, ctx.post_drop, ops.row_offset)
         same_pitch = w3[0].stride(0) == w3[1].stride(0) == w3[2].stride(0)
         if (tuning.HOST.rewrites & tuning.REWRITE_AGGW_FUSED) and same_pitch:
             # projections + head behind the gather as ONE row-local kernel: pre_L = P W_L, pre_H = (Xd - P) W_H, Z_I = Xd W_I
@@ -2442,7 +2550,7 @@ class _AcmAggWide(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out, _grad_att):
         if grad_out is None:
-            return (None,) * 22
+            return _NO_GRADS
         lib = _lib.load()
         ops, cfg, f_in, fp = ctx.ops, ctx.cfg, ctx.f_in, ctx.fp
         xd, agg, zi, pre, mix, *rest = ctx.saved_tensors
@@ -2467,9 +2575,7 @@ class _AcmAggWide(torch.autograd.Function):
         elif (tuning.HOST.rewrites & tuning.REWRITE_AGGW_FUSED) and ctx.post_scale is None:
             # K3 and the three weight gradients in ONE kernel: [G_L | G_H | G_I] never reach memory
             q.g_low = q.g_high = q.g_mlp = None
-            nbytes = C.c_size_t()
-            _lib.check(lib.acm_conv_aggw_bwd_workspace_bytes(n, fp, C.byref(nbytes)), "acm_conv_aggw_bwd_workspace_bytes")
-            ws = torch.empty(max(nbytes.value // 4, 1), dtype=_F32, device=dev)
+            ws = _workspace(lib, dev, "acm_conv_aggw_bwd_workspace_bytes", n, fp)
             with _device_ctx(dev), _Timed(f"conv_aggw_bwd/F{f}k{k}i{f_in}"):
                 st = lib.acm_conv_aggw_bwd(n, f_in, fp, _vp(agg), agg.stride(0), _vp(xd), xd.stride(0), C.byref(q), _vp(dw[0]),
                                            _vp(dw[1]), _vp(dw[2]), f, _vp(ws), ws.numel() * 4, _stream())
@@ -2483,9 +2589,7 @@ class _AcmAggWide(torch.autograd.Function):
             q.g_low, q.ld_g_low = gcat.data_ptr(), gcat.stride(0)
             q.g_high, q.ld_g_high = gcat.data_ptr() + 4 * f, gcat.stride(0)
             q.g_mlp, q.ld_g_mlp = gcat.data_ptr() + 8 * f, gcat.stride(0)
-            nbytes = C.c_size_t()
-            _lib.check(lib.acm_conv_bwd_local_workspace_bytes(n, f, k, C.byref(nbytes)))
-            ws = torch.empty(max(nbytes.value // 4, 1), dtype=_F32, device=dev)
+            ws = _workspace(lib, dev, "acm_conv_bwd_local_workspace_bytes", n, f, k)
             with _device_ctx(dev), _Timed(f"conv_bwd_local/F{f}k{k}"):
                 st = lib.acm_conv_bwd_local(n, C.byref(q), _vp(ws), ws.numel() * 4, _stream())
             _lib.check(st, "acm_conv_bwd_local")
@@ -2497,36 +2601,28 @@ class _AcmAggWide(torch.autograd.Function):
             dw[0].copy_(a1[0][:f_in])
             torch.sub(a2[0][:f_in], a1[1][:f_in], out=dw[1])
             dw[2].copy_(a2[1][:f_in])
-        d_wl, d_wh, d_wm = dw[0], dw[1], dw[2]
-        if ops.sharded:
-            # replicated parameters: the weight gradients sit with the head's in the layer's flat buffer, ONE all-reduce sums the
-            # row-shard partials (after the step's single flush when the second phases are deferred)
-            import torch.distributed as dist
-            if defer is not None:
-                defer.allreduce(flat, ops.group)
-            else:
-                dist.all_reduce(flat, group=ops.group)
-        none3 = [None] * 3
-        return (None, d_wl, d_wh, d_wm, d_vec[0], d_vec[1], d_vec[2], d_mix,
-                *(d_lnw if cfg.layernorm else none3), *(d_lnb if cfg.layernorm else none3), None, None, None, None, None, None, None,
-                None)
+        # the weight gradients sit with the head's in the layer's flat buffer: ONE all-reduce when row-sharded
+        _reduce_replicated(flat, ops, defer)
+        return _grads(None, (dw[0], dw[1], dw[2]), d_vec, None, d_mix, d_lnw, d_lnb)
 
 
 def in_drop_supported(x, ops, cfg, f_in, f_out):
-    """Whether a layer can take its caller's input dropout into its dense projection (AcmConvFunction ``in_drop``): the
+    """Whether a layer can take its caller's input dropout into its dense projection (acm_conv ``in_drop``): the
     literal form on the MFMA GEMM (not aggregate-first, not the narrow streaming projection, not CSR features), an input
-    that needs no gradient, shapes the row-panel GEMMs cover."""
+    that needs no gradient, shapes the row-panel GEMMs cover.  (By shape alone, whatever the tuning switches say: a layer
+    then takes the same launches under any of them.)"""
     if isinstance(x, SparseFeatures) or not isinstance(x, torch.Tensor) or x.requires_grad or x.dim() != 2:
         return False
     if x.shape[1] != f_in or x.dtype != _F32 or not x.is_contiguous():
         return False
-    agg_first = not cfg.relu_before and f_in <= 16 and f_in < f_out and f_out <= 64
-    recompute = cfg.relu_before and f_out == 64 and f_in <= 8
     narrow = f_out <= 5 and f_in <= 64
-    if agg_first or recompute or narrow or f_out in (2, 4, 8):
+    if _agg_first_shape(cfg, f_in, f_out) or _acmii_shape(cfg, f_in, f_out) or narrow or f_out in (2, 4, 8):
         return False
     fb = _chan_block(f_out)
     return gemm_drop_supported(x.shape[0], f_in, 2 * fb + f_out)
+
+
+_ROUTES = {"wide": _AcmAggWide, "agg": _AcmAggFirst, "acmii": _AcmAcmii, "literal": _AcmLiteral}
 
 
 def acm_conv(x, params, ops, cfg, post_relu=False, post_scale=None, post_drop=None, call=None, tail_layer=False,
@@ -2535,17 +2631,17 @@ def acm_conv(x, params, ops, cfg, post_relu=False, post_scale=None, post_drop=No
     post_relu / post_scale: optional fused ``relu(out) * post_scale`` (the caller's inter-layer
     ReLU + dropout; post_scale = keep_mask / (1 - p)).  post_drop = (p, tag, DropoutState): the same
     dropout with the mask generated in registers (acm_dropout_t) instead of read from a tensor.
-    call / tail_layer / agg_holder: see AcmConvFunction.forward."""
+    call: the model call's CallContext (default: the thread's ambient one); tail_layer: the caller is an output layer without
+    post-op working in the operator's numbering (it may take call.tail); agg_holder: layers.GraphConvolution's {"agg": P-or-None}
+    of a pass over a static input; in_drop = (p, tag, DropoutState): the caller's input dropout, left to this layer
+    (in_drop_supported).  The layer runs as the autograd Function of its route (_conv_route)."""
     p = params
-    if agg_wide_supported(x, ops, cfg, p["weight_low"].shape[0], p["weight_low"].shape[1], post_scale, call, tail_layer):
-        return _run(_AcmAggWide, x, p["weight_low"], p["weight_high"], p["weight_mlp"], p["att_vec_low"], p["att_vec_high"],
-                                 p["att_vec_mlp"], p["att_vec"], p["layer_norm_low.weight"], p["layer_norm_high.weight"],
-                                 p["layer_norm_mlp.weight"], p["layer_norm_low.bias"], p["layer_norm_high.bias"],
-                                 p["layer_norm_mlp.bias"], ops, cfg, post_relu, post_scale, post_drop, call, in_drop, agg_holder)
+    fn = _ROUTES[_conv_route(x, ops, cfg, p["weight_low"].shape[0], p["weight_low"].shape[1], post_scale, call, tail_layer)]
+    pregathered, ops._pregathered = getattr(ops, "_pregathered", None), None     # one-shot hand-over from models.GCN
     return _run(
-        AcmConvFunction, x, p["weight_low"], p["weight_high"], p["weight_mlp"], p["att_vec_low"], p["att_vec_high"],
+        fn, x, p["weight_low"], p["weight_high"], p["weight_mlp"], p["att_vec_low"], p["att_vec_high"],
         p["att_vec_mlp"], p["att_struc_low"], p["struc_low"], p["att_vec"],
         p["layer_norm_low.weight"], p["layer_norm_high.weight"], p["layer_norm_mlp.weight"],
         p["layer_norm_struc_low.weight"], p["layer_norm_low.bias"], p["layer_norm_high.bias"],
         p["layer_norm_mlp.bias"], p["layer_norm_struc_low.bias"], ops, cfg, post_relu, post_scale, post_drop,
-        call, tail_layer, agg_holder, in_drop)
+        call, tail_layer, agg_holder, in_drop, pregathered)

@@ -6,7 +6,7 @@ same constructor signature, parameter names (``state_dict`` compatible),
 initialisation scheme, ``forward(input, adj_low, adj_high, adj_low_unnormalized)``
 signature, ``att_low/att_high/att_mlp[/att_struc_vec_low]`` attributes after a
 forward, and ``__repr__``.  The arithmetic is the fused HIP path in
-``functional.AcmConvFunction``; nothing here falls back to torch ops.
+``functional.acm_conv`` (one autograd Function per route); nothing here falls back to torch ops.
 
 One thing the reference decides implicitly is made explicit (SURVEY.md quirk
 Q1): whether LayerNorm feeds the attention logits of ``acmgcnp``/``acmgcnpp``.

@@ -288,7 +288,7 @@ def _worker(rank, world, port, cfg, ret):
                               "wide-aggregate-first-dropout", "wide-aggregate-first-work-plan"])
 def test_row_shard_equals_single_process(cfg, monkeypatch, tune):
     """world_size = 2, 4 and 8 (the node's GPU count) over gloo: the sharded forward/backward (halo all-gathers + parameter-gradient
-    all-reduce issued by functional.AcmConvFunction) must reproduce the 1-process result -- with equal blocks and
+    all-reduce issued by functional.acm_conv's Functions) must reproduce the 1-process result -- with equal blocks and
     with the work-balanced plan (blocks of different lengths, padded halo numbering)."""
     import torch.multiprocessing as mp
     import torch.nn.functional as F

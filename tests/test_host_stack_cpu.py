@@ -303,7 +303,7 @@ def test_snowball_model_matches_the_reference_wiring(variant, nlayers, monkeypat
 
 @pytest.mark.parametrize("f_in,s_info", [(7, 0), (3, 0), (7, 1)])
 def test_acmii_recompute_host_path_equals_literal(f_in, s_info, monkeypatch, tune):
-    """Host plumbing of the ACMII recompute-on-gather route (functional.AcmConvFunction -> acm_conv_acmii_fwd, then the
+    """Host plumbing of the ACMII recompute-on-gather route (functional._AcmAcmii -> acm_conv_acmii_fwd, then the
     literal backward on the tensors that call saved) against the literal route and the oracle."""
     fake_lib.install(monkeypatch)
     from oracle import acm_oracle as oracle
