@@ -144,6 +144,42 @@ struct CsrView {
 int acm_reduce_emit(acm_reduce_list_t* defer, const acm_reduce_seg_t* segs, int n, hipStream_t st);
 int acm_reduce_check_segment(const acm_reduce_seg_t& sg, int index);      // ACM_OK or ACM_EINVAL (+ message)
 
+// ---- functions one source defines and another calls (not part of the ABI): declared here and nowhere else
+// acm_spmm.hip: acm_spmm_ex for callers inside the library (defer_fixup: see the definition)
+int acm_spmm_internal(const acm_csr* a, const void* G, int64_t ldg, int width, float* Y, int64_t ldy,
+                      const acm_spmm_opts_t* o, void* workspace, size_t workspace_bytes, acm_stream_t stream,
+                      bool* defer_fixup);
+// acm_conv_bwd.hip: second phase of K3, the per-block parameter-gradient partials -> their destinations
+int acm_bwd_local_reduce(const acm_conv_bwd_local_t* p, const float* partial, int nblk, hipStream_t st);
+// acm_conv_local16.hip: K3 at F = 64, k = 3 with sixteen rows per wave (blocks launched; 0: not its case; < 0: error)
+int acm_bwd_local16(const acm_conv_bwd_local_t* p, int64_t n_rows, float* partial, int max_blocks, hipStream_t s);
+// acm_conv_agg16.hip: the row-local forward stage in the transposed matrix-core layout (-1: not its case)
+int acm_agg_epi16(const acm_conv_agg_fwd_t* p, int64_t n_rows, bool* next_done, hipStream_t s);
+struct GatherRole;   // (acm_stream_device.h) ... and the row-local backward (blocks launched; 0: not its case; < 0: error)
+int acm_agg_bwd16(const acm_conv_agg_bwd_t* p, int64_t n_rows, float* partial, int max_blocks, hipStream_t s, const GatherRole* gr,
+                  int gather_blocks);
+// acm_conv_acmii.hip: the fix-up launch of acm_conv_acmii_fwd (also behind acm_conv_acmii_v_fwd)
+int acm_acmii_fixup_launch(const acm_csr_t* a, const acm_conv_acmii_fwd_t* p, const float* partial, hipStream_t s);
+// acm_gemm_rows.hip: row-panel kernels for n >> K, N (X read once, optional input dropout in the tile load)
+bool acm_gemm_rows_nn_ok(int64_t M, int64_t N, int64_t K, const float* B, int64_t ldb);
+int acm_gemm_rows_nn(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
+                     int64_t ldc, int relu, const acm_dropout_t* drop, hipStream_t st);
+bool acm_gemm_rows_tn_ok(int64_t n_rows, int64_t K, int64_t N);
+int acm_gemm_rows_tn_blocks(int64_t n_rows);
+int acm_gemm_rows_tn(int64_t n_rows, int64_t K, int64_t N, const float* X, int64_t ldx, const float* Dz, int64_t lddz,
+                     float* slabs, int blocks, const acm_dropout_t* drop, hipStream_t st);
+// acm_gemm_bx3.hip: the same products on the bf16 matrix pipe at fp32 accuracy (three-way split operands), K <= 128
+bool acm_gemm_bx3_nn_ok(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda);
+int acm_gemm_bx3_nn(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
+                    int64_t ldc, int relu, const acm_dropout_t* drop, hipStream_t st);
+bool acm_gemm_bx3_tn_ok(int64_t n_rows, int64_t K, int64_t N);
+int acm_gemm_bx3_tn_blocks(int64_t n_rows, int64_t K);
+int acm_gemm_bx3_tn(int64_t n_rows, int64_t K, int64_t N, const float* X, int64_t ldx, const float* Dz, int64_t lddz,
+                    float* slabs, int blocks, const acm_dropout_t* drop, hipStream_t st);
+int acm_linear_fwd_narrow(int64_t n_rows, int64_t f_in, int64_t f_out, const float* X, int64_t ldx, const float* W, int64_t ldw,
+                          const float* bias, int relu, const acm_dropout_t* drop, float* Y, int64_t ldy, hipStream_t s,
+                          const float* add, int64_t ld_add);   // acm_linear.hip
+
 static inline CsrView acm_view(const acm_csr* a) {
     CsrView v;
     v.items = a->items;

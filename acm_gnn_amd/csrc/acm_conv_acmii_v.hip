@@ -530,10 +530,6 @@ static VStreamView stream_view(const AcmItemStreams* t) {
 // read (the table replaces it), p->zlh may be NULL (only its high-pass half would be written).  Long rows: the pieces' partial
 // sums are combined by acm_conv_acmii_fwd's fix-up launch, which reads zlh's high-pass half -- so zlh is required with long rows.
 extern "C" int acm_conv_acmii_v_fwd(const acm_csr_t* a, const acm_conv_acmii_fwd_t* p, const void* table, void* workspace,
-                                    size_t workspace_bytes, acm_stream_t stream);
-int acm_acmii_fixup_launch(const acm_csr_t* a, const acm_conv_acmii_fwd_t* p, const float* partial, hipStream_t s);   // acm_conv_acmii.hip
-
-extern "C" int acm_conv_acmii_v_fwd(const acm_csr_t* a, const acm_conv_acmii_fwd_t* p, const void* table, void* workspace,
                                     size_t workspace_bytes, acm_stream_t stream) {
     ACM_REQUIRE(p, ACM_EINVAL, "acm_conv_acmii_v_fwd: NULL argument");
     const int st = acmii_v_check_operator(a, table, "acm_conv_acmii_v_fwd");

@@ -13,17 +13,6 @@
 #include "acm_conv_device.h"
 #include "acm_stream_device.h"
 
-// defined in acm_conv.hip
-int acm_spmm_internal(const acm_csr* a, const void* G, int64_t ldg, int width, float* Y, int64_t ldy,
-                      const acm_spmm_opts_t* o, void* workspace, size_t workspace_bytes, acm_stream_t stream,
-                      bool* defer_fixup);
-// defined in acm_conv_agg16.hip: the row-local forward stage in the transposed matrix-core layout (-1: not its case)
-int acm_agg_epi16(const acm_conv_agg_fwd_t* p, int64_t n_rows, bool* next_done, hipStream_t s);
-// ... and the row-local backward (blocks launched; 0: not its case; < 0: error)
-struct GatherRole;
-int acm_agg_bwd16(const acm_conv_agg_bwd_t* p, int64_t n_rows, float* partial, int max_blocks, hipStream_t s, const GatherRole* gr,
-                  int gather_blocks);
-
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -1,4 +1,4 @@
-// Device-side building blocks shared by the ACM layer kernels (acm_conv.hip, acm_conv_agg.hip):
+// Device-side building blocks shared by the ACM layer kernels (acm_conv*.hip, acm_gather_device.h):
 // lane layouts, the adaptive-mixing head (LayerNorm -> att_vec dot -> sigmoid -> k x k mix ->
 // softmax) and the parameter-gradient accumulators of its backward.
 #pragma once
@@ -290,6 +290,151 @@ __device__ __forceinline__ void acm_head_backward(const L& lay, int F, int layer
             }
         }
     }
+}
+
+// ---- K3, the row-local backward of one row (acm_conv_bwd.hip: conv_bwd_local_kernel; acm_conv.hip: the fused output-layer tail)
+template <class L, int K>
+__device__ __forceinline__ void conv_bwd_row(const acm_conv_bwd_local_t& p, int row, bool active,
+                                             const L& lay, ParamAcc<L>& pa) {
+    constexpr int NV = L::NV;
+    constexpr int k = K;
+    const int F = p.f_out;
+    float H[4][NV], hn[4][NV], xhat[4][NV], dO[NV];
+    bool pos[4][NV];
+    const float dg = (k == 4 && active && p.deg) ? p.deg[row] : 1.f;
+    const float gsc = (active && p.g_scale) ? p.g_scale[row] : 1.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int col = lay.col(i);
+        const bool ok = active && col < F;
+        const float* pr = p.pre + (long)row * p.ld_pre;
+        const float p0 = ok ? pr[col] : 0.f;
+        const float p1 = ok ? pr[F + col] : 0.f;
+        const float p3 = (ok && k == 4) ? pr[2 * F + col] : 0.f;
+        const float zi = ok ? p.s_mlp[(long)row * p.ld_s_mlp + col] : 0.f;
+        dO[i] = ok ? p.grad_out[(long)row * p.ld_grad_out + col] : 0.f;
+        pos[0][i] = p.relu_after ? (p0 > 0.f) : true;
+        pos[1][i] = p.relu_after ? (p1 > 0.f) : true;
+        pos[2][i] = p.relu_mlp ? (zi > 0.f) : true;
+        pos[3][i] = p3 > 0.f;
+        H[0][i] = pos[0][i] ? p0 : 0.f;
+        H[1][i] = pos[1][i] ? p1 : 0.f;
+        H[2][i] = pos[2][i] ? zi : 0.f;
+        H[3][i] = pos[3][i] ? p3 : 0.f;
+    }
+    HeadOut ho;
+    const HeadParams hp = acm_head_params(p);
+    acm_head<L, K>(lay, F, p.layernorm, hp, H, hn, xhat, ho);
+
+    if (p.post_relu || p.post_scale || p.post_drop.p > 0.f) {   // undo the fused post-op of the forward on the incoming gradient
+        const AcmDropCtx dc = acm_drop_ctx(p.post_drop);
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int col = lay.col(i);
+            const bool ok = active && col < F;
+            float raw = 0.f;
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (c < K) raw += ho.alpha[c] * H[c][i];
+            if (p.post_relu && !(raw * p.scale > 0.f)) dO[i] = 0.f;
+            if (p.post_scale && ok) dO[i] *= p.post_scale[(long)row * p.ld_post_scale + col];
+            if (dc.on && ok) dO[i] *= acm_drop1(dc, row, col);
+        }
+    }
+    float dH[4][NV];
+    acm_head_backward<L, K>(lay, F, p.layernorm, hp, p.scale, H, hn, xhat, ho, dO, active ? 1.f : 0.f, pa, dH);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        if (c >= k) continue;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int col = lay.col(i);
+            if (!(active && col < F)) continue;
+            const float gval = pos[c][i] ? dH[c][i] : 0.f;
+            if (c == 0) p.g_low[(long)row * p.ld_g_low + col] = gsc * gval;
+            if (c == 1) p.g_high[(long)row * p.ld_g_high + col] = gsc * gval;
+            if (c == 2) p.g_mlp[(long)row * p.ld_g_mlp + col] = gval;
+            if (c == 3) p.g_struc[(long)row * p.ld_g_struc + col] = dg * gval;
+        }
+    }
+}
+
+// Block-level deterministic reduction of the per-lane parameter-gradient accumulators of K3:
+// the RPW row-groups of a wave (shuffles) -> LDS slab [4 waves][npg] -> sum over the waves -> out[npg].
+template <class L, int RPW, int K>
+__device__ __forceinline__ void bwd_local_block_reduce(ParamAcc<L>& pa, const L& lay, int F, float* lds,
+                                                       float* __restrict__ out) {
+    constexpr int k = K;
+    const int npg = 3 * k * F + k * k;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    // combine the RPW row-groups of this wave.  One row per lane (RPW = 64: the thread-per-row kernels of the narrow
+    // layers) sums all 64 lanes with the DPP / permlane tree of acm_group_sum -- the xor butterfly below lowers to one
+    // ds_bpermute + s_waitcnt per step, 6 steps x (12 NV + 16) values per block: it was most of the fused output-layer
+    // tail's 18 us
+    if (RPW == 64) {
+#pragma unroll
+        for (int c = 0; c < k; ++c)
+#pragma unroll
+            for (int i = 0; i < L::NV; ++i) {
+                pa.dv[c][i] = acm_group_sum<64>(pa.dv[c][i]);
+                pa.dgam[c][i] = acm_group_sum<64>(pa.dgam[c][i]);
+                pa.dbet[c][i] = acm_group_sum<64>(pa.dbet[c][i]);
+            }
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+            if ((q >> 2) < k && (q & 3) < k) pa.dmix[q] = acm_group_sum<64>(pa.dmix[q]);
+    } else if (RPW == 8) {                       // eight lanes per row: lanes l, l ^ 8 (DPP row_ror:8), then the four 16-lane rows
+#pragma unroll
+        for (int c = 0; c < k; ++c)
+#pragma unroll
+            for (int i = 0; i < L::NV; ++i) {
+                pa.dv[c][i] = acm_cross_row_sum(pa.dv[c][i] + acm_dpp<0x128>(pa.dv[c][i]));
+                pa.dgam[c][i] = acm_cross_row_sum(pa.dgam[c][i] + acm_dpp<0x128>(pa.dgam[c][i]));
+                pa.dbet[c][i] = acm_cross_row_sum(pa.dbet[c][i] + acm_dpp<0x128>(pa.dbet[c][i]));
+            }
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+            if ((q >> 2) < k && (q & 3) < k) pa.dmix[q] = acm_cross_row_sum(pa.dmix[q] + acm_dpp<0x128>(pa.dmix[q]));
+    } else if (RPW > 1) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int i = 0; i < L::NV; ++i) {
+                for (int m = 64 / RPW; m < 64; m <<= 1) {
+                    pa.dv[c][i] += __shfl_xor(pa.dv[c][i], m, 64);
+                    pa.dgam[c][i] += __shfl_xor(pa.dgam[c][i], m, 64);
+                    pa.dbet[c][i] += __shfl_xor(pa.dbet[c][i], m, 64);
+                }
+            }
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+            for (int m = 64 / RPW; m < 64; m <<= 1) pa.dmix[q] += __shfl_xor(pa.dmix[q], m, 64);
+    }
+    float* slab = lds + wv * npg;
+    const bool writer = (RPW == 1) || (lane < 64 / RPW);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        if (c >= k) continue;
+#pragma unroll
+        for (int i = 0; i < L::NV; ++i) {
+            const int col = lay.col(i);
+            if (writer && col < F) {
+                slab[(0 * k + c) * F + col] = pa.dv[c][i];
+                slab[(1 * k + c) * F + col] = pa.dgam[c][i];
+                slab[(2 * k + c) * F + col] = pa.dbet[c][i];
+            }
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (c < k && j < k) slab[3 * k * F + c * k + j] = pa.dmix[c * 4 + j];
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < npg; q += 256)
+        out[q] = (lds[q] + lds[npg + q]) + (lds[2 * npg + q] + lds[3 * npg + q]);
 }
 
 // =====================================================================================

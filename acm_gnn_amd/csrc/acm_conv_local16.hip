@@ -1,7 +1,7 @@
 // K3 of the literal ACM layer at the reference's hidden width (three channels, F = 64) with SIXTEEN rows per wave
 // (ACM-Geometric/layers.py:57-63,101-108 backwards: the autograd replay of attention3 + LayerNorm + the mix, train.py:135).
 //
-// The older kernel (acm_conv.hip: conv_bwd_local_grouped_kernel) gives a row to a 16-lane group, columns m + 16 i: every load
+// The older kernel (acm_conv_bwd.hip: conv_bwd_local_grouped_kernel) gives a row to a 16-lane group, columns m + 16 i: every load
 // and store is a dword per lane, every reduction of the head a 16-lane DPP tree per row, every per-row scalar computed 16
 // times.  It moves 1.8 KB per row (pre_L, pre_H, Z_I, grad_out in; G_L, G_H, G_I out) at 3.0 TB/s.  Here lane (g, m) holds
 // columns 16 t + 4 g + r of row m (the layout of acm_conv_agg16.hip): 16-byte loads and stores, head sums = 15 in-lane adds +

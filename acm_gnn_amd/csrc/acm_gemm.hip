@@ -12,28 +12,6 @@
 // contiguous, with the next K-slab prefetched into registers while the current one feeds MFMA.
 #include "acm_common.h"
 
-// acm_gemm_rows.hip: row-panel kernels for n >> K, N (X read once, optional input dropout in the tile load)
-bool acm_gemm_rows_nn_ok(int64_t M, int64_t N, int64_t K, const float* B, int64_t ldb);
-int acm_gemm_rows_nn(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
-                     int64_t ldc, int relu, const acm_dropout_t* drop, hipStream_t st);
-bool acm_gemm_rows_tn_ok(int64_t n_rows, int64_t K, int64_t N);
-int acm_gemm_rows_tn_blocks(int64_t n_rows);
-int acm_gemm_rows_tn(int64_t n_rows, int64_t K, int64_t N, const float* X, int64_t ldx, const float* Dz, int64_t lddz,
-                     float* slabs, int blocks, const acm_dropout_t* drop, hipStream_t st);
-
-// acm_gemm_bx3.hip: the same products on the bf16 matrix pipe at fp32 accuracy (three-way split operands), K <= 128
-bool acm_gemm_bx3_nn_ok(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda);
-int acm_gemm_bx3_nn(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
-                    int64_t ldc, int relu, const acm_dropout_t* drop, hipStream_t st);
-bool acm_gemm_bx3_tn_ok(int64_t n_rows, int64_t K, int64_t N);
-int acm_gemm_bx3_tn_blocks(int64_t n_rows, int64_t K);
-int acm_gemm_bx3_tn(int64_t n_rows, int64_t K, int64_t N, const float* X, int64_t ldx, const float* Dz, int64_t lddz,
-                    float* slabs, int blocks, const acm_dropout_t* drop, hipStream_t st);
-
-int acm_linear_fwd_narrow(int64_t n_rows, int64_t f_in, int64_t f_out, const float* X, int64_t ldx, const float* W, int64_t ldw,
-                          const float* bias, int relu, const acm_dropout_t* drop, float* Y, int64_t ldy, hipStream_t s,
-                          const float* add, int64_t ld_add);   // acm_linear.hip
-
 namespace {
 
 constexpr int BK = 32;

@@ -94,7 +94,7 @@ def test_bf16_gather_tolerance(name, model_type, variant, s, f_out):
 
 @pytest.mark.parametrize("model_type,variant,s", [("acmgcnp", 0, 0), ("acmgcnp", 1, 1)])
 def test_bf16_forward_forms_agree(model_type, variant, s):
-    """The two kernels a bf16 wide gather under the fused head can take (acm_conv.hip: the four-neighbour vector form on
+    """The two kernels a bf16 wide gather under the fused head can take (acm_gather_device.h: the four-neighbour vector form on
     cache-resident tables, the pair kernel once the tables outgrow the Infinity Cache -- pokec / snap-patents sizes) read the
     same bf16 tables and differ in fp32 summation order only: same output and gradients on the Squirrel structure."""
     from conftest import tune_now as tune
