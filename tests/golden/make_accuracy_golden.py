@@ -21,6 +21,16 @@ exact same experiment on the MI355X.
                                                                     # small-graph step (acm_small_step + FusedAdam, masks
                                                                     # drawn inside the kernels) replays on the MI355X
 
+    python tests/golden/make_accuracy_golden.py twitch_syn --dialect geometric --philox [--b]
+                                                                    # ~7 min (run b: ~3 min): the ACM-GEOMETRIC dialect (sparse
+                                                                    # A_low, attention LayerNorm live, AdamW, test accuracy at the
+                                                                    # first maximum of the validation accuracy) on a seeded
+                                                                    # 32 768-node heavy-tailed graph, variant 0 and variant 1 ->
+                                                                    # graph_twitch_syn.npz, accuracy_twitch_syn_v{0,1}[_b]_philox.npz:
+                                                                    # the run the headline path (degree relabelling, input
+                                                                    # pipeline, FusedAdamW, captured step) replays on the MI355X
+                                                                    # (tests/test_gpu_accuracy_headline.py); see main_geometric()
+
 Splits already recorded in accuracy_<name>.npz are kept (the run is merged into the file).
 
 Run "b" measures the reference's own run-to-run band: identical data, splits, seeded init, dropout
@@ -49,7 +59,7 @@ warnings.filterwarnings("ignore")
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))       # oracle/philox.py (the --philox masks)
-from replay import PhiloxDropout, SeededDropout  # noqa: E402
+from replay import PhiloxDropout, SeededDropout, degree_order, load_twitch_syn  # noqa: E402
 
 PHILOX_SEED = 0x5EED0ACC00000000          # + split: the DropoutState seed of the replay (tests/test_gpu_accuracy.py)
 
@@ -70,6 +80,61 @@ CONFIGS = {
     "chameleon_syn": dict(dataset="chameleon_syn", model="acmgcnp", structure_info=1, variant=0, hidden=64, lr=0.05,
                           weight_decay=1e-4, dropout=0.7, epochs=200, early_stopping=200, splits=list(range(10))),
 }
+
+# ACM-Geometric dialect (main_geometric): models.GCN as parse.py builds it for the script's default method acmgcnp -- hidden 64,
+# 2 layers, structure_info 0, dropout 0.1 -- under AdamW (train.py:116) lr 0.05, weight decay 1e-3 (parse.py's default)
+CONFIGS_GEOMETRIC = {
+    f"twitch_syn_v{v}": dict(dataset="twitch_syn", model="acmgcnp", structure_info=0, variant=v, hidden=64, num_layers=2, lr=0.05,
+                             weight_decay=1e-3, dropout=0.1, epochs=120, splits=[0, 1, 2])
+    for v in (0, 1)}
+
+
+def make_twitch_syn():
+    """graph_twitch_syn.npz: a seeded Chung-Lu graph of exactly 32 768 nodes (the size from which graph._want_relabel relabels;
+    ids fit in uint16) -- Pareto weights, 8 n sampled pairs, symmetrised, simple.  Heavy-tailed (a hub of ~1 000 neighbours: split
+    into several work-list pieces at the operator's chunk of 128), a few isolated nodes, 12 n < nnz(I + A) <= 160 n (the regime
+    functional.InputPipeline.eligible accepts).  The weights are drawn per id, so the ids are in random order with respect to the
+    degree.  Two planted classes (own coin + a vote of the neighbours' coins + noise); seven positive real-valued features, log-normal
+    around a class-dependent pattern, quantised to 1/32 (one byte each) -- learnable, not separable.  Three fixed 50/25/25 splits.
+    Stored: the upper triangle (per-row counts + column ids, uint16), feature codes, labels and masks as packed bits.
+    The file is rewritten only when its content changes."""
+    n, f_in = 32768, 7
+    rng = np.random.default_rng(3276807)
+    w = rng.pareto(1.6, n) + 1.0
+    pairs = rng.choice(n, size=(8 * n, 2), p=w / w.sum())
+    pairs = pairs[pairs[:, 0] != pairs[:, 1]]
+    lo, hi = pairs.min(1), pairs.max(1)
+    keys = np.unique(lo.astype(np.int64) * n + hi)
+    lo, hi = keys // n, keys % n                                   # sorted by (row, column): the upper triangle in CSR order
+    a = sp.coo_matrix((np.ones(len(lo), np.float32), (lo, hi)), shape=(n, n)).tocsr()
+    a = (a + a.T).tocsr()
+    deg = np.diff(a.indptr)
+    nnz_low = int(a.nnz + n)
+    assert 12 * n < nnz_low <= 160 * n, nnz_low
+    assert deg.max() > 4 * 128 and (deg == 0).sum() >= 1, (deg.max(), (deg == 0).sum())
+    perm, _ = degree_order(deg)
+    assert not np.array_equal(perm, np.arange(n))
+    coin = rng.integers(0, 2, n)
+    votes = np.asarray(a @ (2.0 * coin - 1.0)) / np.maximum(deg, 1)
+    labels = ((2.0 * coin - 1.0) + 0.8 * votes + 0.5 * rng.standard_normal(n) > 0).astype(np.int64)
+    pattern = np.array([1.0, -1.0, 1.0, -1.0, 1.0, -1.0, 0.0])
+    x = np.exp(0.22 * np.outer(2.0 * labels - 1.0, pattern) + 0.8 * rng.standard_normal((n, f_in)))
+    codes = np.clip(np.rint(32.0 * x), 1, 255).astype(np.uint8)
+    rec = {"n": np.int64(n), "tri_count": np.bincount(lo, minlength=n).astype(np.uint16), "tri_cols": hi.astype(np.uint16),
+           "feat_codes": codes, "feat_scale": np.float32(1.0 / 32.0), "labels_bits": np.packbits(labels.astype(bool)),
+           "n_splits": np.int64(3)}
+    for s in range(3):
+        order = np.random.default_rng(500 + s).permutation(n)
+        for k, (b, e) in zip(("train", "val", "test"), ((0, n // 2), (n // 2, 3 * n // 4), (3 * n // 4, n))):
+            m = np.zeros(n, bool)
+            m[order[b:e]] = True
+            rec[f"{k}_mask_{s}"] = np.packbits(m)
+    path = os.path.join(HERE, "graph_twitch_syn.npz")
+    if os.path.exists(path):
+        with np.load(path, allow_pickle=False) as f:
+            if set(f.files) == set(rec) and all(np.array_equal(f[k], rec[k]) for k in rec):
+                return
+    np.savez_compressed(path, **rec)
 
 
 def make_chameleon_syn():
@@ -219,6 +284,117 @@ def main(name, only=None, run_b=False, philox=False):
     print(f"{name}: {100 * np.mean(accs):.2f} +- {100 * np.std(accs):.2f} over splits {sorted(accs_by_split)}")
 
 
+def main_geometric(name, only=None, run_b=False, philox=True):
+    """ACM-Geometric dialect.  The loop follows ACM-Geometric/train.py:66-81 (row-normalised features, A_low = D^-1 (I + A),
+    A_high = I - A_low as sparse tensors), :111-139 (AdamW; model.train(), zero_grad, log_softmax + NLLLoss on the training
+    rows, backward, step; data_utils.evaluate_acmgcn with eval_acc after every step) and logger.py:17-35 (the test accuracy at
+    the FIRST maximum of the validation accuracy).  models.GCN and evaluate_acmgcn are imported from the reference; dgl,
+    torch_sparse, torch_geometric and google_drive_downloader -- none installed, none called by the code that runs -- are
+    stubbed.  Masks: the library's counter-based ones (replay.PhiloxDropout, dense input), by the row the library's degree
+    relabelling gives each node (degree_order).  hist_<split> columns: training loss, validation NLL (of the ``out``
+    evaluate_acmgcn returns), test / train / validation accuracy.  Run "b": both sparse operands in CSR layout, 3 threads."""
+    assert philox, "the ACM-Geometric run is recorded with the library's masks only (--philox)"
+    if name == "twitch_syn":
+        for nm in sorted(CONFIGS_GEOMETRIC):
+            main_geometric(nm, only, run_b, philox)
+        return
+    cfg = dict(CONFIGS_GEOMETRIC[name])
+    if run_b:
+        torch.set_num_threads(3)
+    if only:
+        cfg["splits"] = only
+    dataset = cfg.pop("dataset")
+    for m in ("dgl", "dgl.function", "dgl.utils", "dgl.nn", "dgl.nn.pytorch", "torch_geometric", "torch_geometric.utils"):
+        sys.modules.setdefault(m, types.ModuleType(m))
+    sys.modules["dgl"].function, sys.modules["dgl"].utils = sys.modules["dgl.function"], sys.modules["dgl.utils"]
+    sys.modules["dgl"].nn = sys.modules["dgl.nn"]
+    sys.modules["dgl.nn"].pytorch = sys.modules["dgl.nn.pytorch"]
+    sys.modules.setdefault("torch_sparse", types.SimpleNamespace(SparseTensor=object, matmul=None))
+    sys.modules.setdefault("google_drive_downloader", types.SimpleNamespace(GoogleDriveDownloader=object))
+    ref_dir = os.path.join(REF, "ACM-Geometric")
+    if ref_dir not in sys.path:
+        sys.path.insert(0, ref_dir)
+    import torch.nn.functional as F
+    from models import GCN
+    from data_utils import eval_acc, evaluate_acmgcn
+    from utils import normalize_tensor, sparse_mx_to_torch_sparse_tensor
+
+    make_twitch_syn()
+    n, a, x_raw, labels_np, masks = load_twitch_syn(os.path.join(HERE, "graph_twitch_syn.npz"))
+    x = torch.tensor(normalize_tensor(x_raw).todense())               # train.py:72-73
+    assert x.dtype == torch.float32
+    low = normalize_tensor(sp.identity(n) + a)                        # train.py:77-80
+    high = sp.identity(n) - low
+    adj_low, adj_high = sparse_mx_to_torch_sparse_tensor(low), sparse_mx_to_torch_sparse_tensor(high)
+    if run_b:                                                         # same matrices, CSR layout: torch.spmm takes another kernel
+        adj_low, adj_high = adj_low.coalesce().to_sparse_csr(), adj_high.coalesce().to_sparse_csr()
+    labels = torch.from_numpy(labels_np)
+    dataset_obj = types.SimpleNamespace(label=labels.unsqueeze(1))    # train.py:33-34
+    _, inv = degree_order(np.diff(a.indptr))
+    path = os.path.join(HERE, f"accuracy_{name}{'_b' if run_b else ''}_philox.npz")
+    out, accs_by_split = {}, {}
+    if os.path.exists(path):                                          # keep what an earlier run recorded
+        with np.load(path, allow_pickle=False) as f:
+            old_cfg = json.loads(str(f["cfg"]))
+            for si, s_ in enumerate(old_cfg["splits"]):
+                out[f"hist_{s_}"] = f[f"hist_{s_}"]
+                accs_by_split[s_] = float(f["test_acc"][si])
+    for split in cfg["splits"]:
+        if split in accs_by_split:
+            continue
+        split_idx = {k: torch.from_numpy(np.nonzero(m)[0]) for k, m in zip(("train", "valid", "test"), masks[split])}
+        train_idx = split_idx["train"]
+        torch.manual_seed(1000 + split)
+        model = GCN(nfeat=x.shape[1], nhid=cfg["hidden"], nclass=int(labels.max()) + 1, nlayers=cfg["num_layers"], nnodes=n,
+                    dropout=cfg["dropout"], model_type=cfg["model"], structure_info=cfg["structure_info"],
+                    variant=cfg["variant"])
+        with torch.no_grad():                                         # never initialised, never used (models.py:41)
+            model.fea_param.zero_()
+            model.xX_param.zero_()
+        opt = torch.optim.AdamW(model.parameters(), lr=cfg["lr"], weight_decay=cfg["weight_decay"])
+        drop = PhiloxDropout(PHILOX_SEED + split, x, dense=True, rows=inv)
+        real = F.dropout
+        F.dropout = drop
+        criterion = torch.nn.NLLLoss()
+        hist = []
+        try:
+            for epoch in range(cfg["epochs"]):
+                drop.next_epoch()
+                model.train()
+                opt.zero_grad()
+                o = F.log_softmax(model(x, adj_low, adj_high, None), dim=1)
+                loss = criterion(o[train_idx], labels[train_idx])
+                loss.backward()
+                opt.step()
+                with torch.no_grad():
+                    tr_acc, va_acc, te_acc, o = evaluate_acmgcn(model, x, adj_low, adj_high, None, dataset_obj, split_idx, eval_acc)
+                    val_nll = float(F.nll_loss(F.log_softmax(o, dim=1)[split_idx["valid"]], labels[split_idx["valid"]]))
+                hist.append((float(loss), val_nll, te_acc, tr_acc, va_acc))
+        finally:
+            F.dropout = real
+        hist = np.asarray(hist, dtype=np.float64)
+        k = int(np.argmax(hist[:, 4]))                                # logger.py:20,33-34: the first maximum
+        accs_by_split[split] = float(hist[k, 2])
+        out[f"hist_{split}"] = hist
+        print(f"{name} split {split}: test acc {hist[k, 2]:.4f} at epoch {k} of {len(hist)}", flush=True)
+        done = sorted(accs_by_split)
+        out["cfg"] = json.dumps(dict(cfg, splits=done, dataset=dataset, dialect="geometric", attn_layernorm=1, optimizer="adamw",
+                                     selection="max_val_acc", hist_columns=["train_loss", "val_nll", "test_acc", "train_acc", "val_acc"],
+                                     **({"run": "b: CSR sparse operands, 3 threads"} if run_b else {}),
+                                     masks="philox", philox_seed=PHILOX_SEED, mask_rows="degree order"))
+        out["test_acc"] = np.asarray([accs_by_split[s_] for s_ in done])
+        np.savez_compressed(path, **out)
+    accs = list(accs_by_split.values())
+    print(f"{name}: {100 * np.mean(accs):.2f} +- {100 * np.std(accs):.2f} over splits {sorted(accs_by_split)}")
+
+
 if __name__ == "__main__":
-    args = [a for a in sys.argv[2:] if a not in ("--b", "--philox")]
-    main(sys.argv[1], [int(v) for v in args] or None, run_b="--b" in sys.argv[2:], philox="--philox" in sys.argv[2:])
+    argv = sys.argv[2:]
+    dialect = "pytorch"
+    if "--dialect" in argv:
+        i = argv.index("--dialect")
+        dialect = argv[i + 1]
+        del argv[i:i + 2]
+    args = [a for a in argv if a not in ("--b", "--philox")]
+    run = {"pytorch": main, "geometric": main_geometric}[dialect]
+    run(sys.argv[1], [int(v) for v in args] or None, run_b="--b" in argv, philox="--philox" in argv)

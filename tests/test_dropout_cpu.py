@@ -107,3 +107,77 @@ def test_train_step_advances_the_counter_once_per_step(monkeypatch):
     assert torch.equal(model(x, ops), model(x, ops))            # eval: no dropout
     off = T.TrainStep(GCN(7, 16, 2, 2, x.shape[0], 0.5, "acmgcnp", 0), opt, x, ops, y, w, fused_dropout=False)
     assert not off.model.fused_dropout
+
+
+def test_philox_replay_masks_dense_input_in_relabelled_rows(monkeypatch):
+    """tests/replay.PhiloxDropout(dense=True, rows=inv_perm) -- what the recorder of the ACM-Geometric run patches into the
+    reference -- hands node i the factors the library draws for row inv_perm[i]: both sites against oracle.philox directly and
+    against the library's dropout (test double) applied in the relabelled numbering and translated back, over several steps."""
+    fake_lib.install(monkeypatch)
+    from acm_gnn_amd import functional as AF
+    from oracle.philox import dropout_factors
+    from replay import PhiloxDropout, degree_order
+    n, p, seed = 300, 0.1, 0x5EED0ACC00000000 + 2
+    rng = np.random.default_rng(4)
+    perm, inv = degree_order(rng.integers(0, 9, n))              # many ties: the order among them is by id
+    assert not np.array_equal(perm, np.arange(n)) and np.array_equal(perm[inv], np.arange(n))
+    x = torch.from_numpy(rng.standard_normal((n, 7)).astype(np.float32))
+    h = torch.from_numpy(rng.standard_normal((n, 64)).astype(np.float32))
+    drop = PhiloxDropout(seed, x, dense=True, rows=inv)
+    st = AF.DropoutState("cpu", seed=seed)
+    pt, it = torch.from_numpy(perm), torch.from_numpy(inv)
+    for step in range(3):
+        drop.next_epoch()
+        got_x, got_h = drop(x, p, training=True), drop(h, p, training=True)
+        f0 = dropout_factors(seed, step, 0, p, n, 7, rows=inv)
+        f1 = dropout_factors(seed, step, 1, p, n, 64, rows=inv)
+        assert torch.equal(got_x, x * torch.from_numpy(f0).float()) and torch.equal(got_h, h * torch.from_numpy(f1).float())
+        assert 0.8 < (f1 > 0).mean() < 0.97 and not np.array_equal(f1, dropout_factors(seed, step, 1, p, n, 64))
+        # the library, in its own numbering: row r holds node perm[r]
+        lib_x = AF.dropout(x.index_select(0, pt), p, st, tag=0, pad_to=8)
+        lib_h = AF.dropout(h.index_select(0, pt), p, st, tag=1)
+        assert torch.equal(lib_x[:, :7].index_select(0, it), got_x) and not lib_x[:, 7].any()
+        assert torch.equal(lib_h.index_select(0, it), got_h)
+        assert torch.equal(drop(x, p, training=False), x)
+        st.advance()
+    # identity rows = the plain (row, column) keying; a CSR-keyed input takes no rows
+    plain = PhiloxDropout(seed, x, dense=True)
+    plain.next_epoch()
+    assert torch.equal(plain(x, p), x * torch.from_numpy(dropout_factors(seed, 0, 0, p, n, 7)).float())
+    with pytest.raises(AssertionError):
+        PhiloxDropout(seed, x, rows=inv)
+
+
+def test_recorded_graph_fixture_and_its_host_degree_order(monkeypatch):
+    """tests/golden/graph_twitch_syn.npz has what the headline replay needs (size at the relabelling threshold, the input
+    pipeline's density window, a hub of several work-list pieces, isolated nodes, 50/25/25 splits), and the host permutation the
+    masks were recorded by (replay.degree_order) is graph.relabel_by_degree's on it."""
+    import os
+    import scipy.sparse as sp
+    from conftest import GOLDEN
+    from replay import degree_order, load_twitch_syn
+    fake_lib.install(monkeypatch)
+    from acm_gnn_amd import graph
+    from acm_gnn_amd.graph import CsrGraph, FilterOperators
+    from oracle import acm_oracle as O
+    path = os.path.join(GOLDEN, "graph_twitch_syn.npz")
+    assert os.path.getsize(path) < (1 << 20)
+    n, a, x, labels, masks = load_twitch_syn(path)
+    deg = np.diff(a.indptr)
+    assert n == 32768 and graph._want_relabel(n) and not graph._want_relabel(n - 1)
+    assert (a != a.T).nnz == 0 and a.diagonal().sum() == 0 and a.data.min() == 1.0 and a.data.max() == 1.0
+    assert 12 * n < a.nnz + n <= 160 * n
+    assert deg.max() > 4 * 128 and (deg == 0).sum() >= 1                  # (128: the operator's chunk at this size)
+    assert x.shape == (n, 7) and x.dtype == np.float32 and x.min() > 0 and len(np.unique(x)) > 100
+    assert set(np.unique(labels)) == {0, 1} and 0.4 < labels.mean() < 0.6
+    assert len(masks) >= 3
+    for tr, va, te in masks:
+        assert (tr.sum(), va.sum(), te.sum()) == (n // 2, n // 4, n // 4) and np.all(tr.astype(int) + va + te == 1)
+    perm, inv = degree_order(deg)
+    assert not np.array_equal(perm, np.arange(n)) and np.array_equal(perm[inv], np.arange(n))
+    d = deg[perm]
+    assert np.all(np.diff(d) <= 0) and np.all((np.diff(d) < 0) | (np.diff(perm) > 0))     # by degree, ties by id
+    low = sp.csr_matrix(O.row_normalize_sp(sp.identity(n) + a).astype(np.float32))
+    ops = graph.relabel_by_degree(graph.as_implicit(FilterOperators(CsrGraph.from_scipy(low, "cpu"))))
+    assert ops.perm is not None
+    assert np.array_equal(ops.perm.numpy(), perm) and np.array_equal(ops.inv_perm.numpy(), inv)

@@ -218,9 +218,14 @@ def test_fixed_split_accuracy_matches_reference_run(name):
     _judge_replay(name, rec, results, f"accuracy_replay_{name}.json")
 
 
-def _judge_replay(name, rec, results, out_name, path_label="general path", bounds=None):
+def _judge_replay(name, rec, results, out_name, path_label="general path", bounds=None, selection="min_val_loss",
+                  early_rtol=(2e-4, 1e-3), extra=None):
     """The parity criterion of a replayed reference run (``results``: {split: (selected test acc, val-loss curve, test-acc
     curve)}) against the recorded one (``rec``); writes the evidence file gpurun_out/<out_name>."""
+    # ``selection``: the rule the recorded run selected its epoch by -- "min_val_loss" (ACM-Pytorch/train.py:129-139: hist column 1)
+    # or "max_val_acc" (ACM-Geometric/logger.py:17-35: the first maximum of hist column 4, the validation accuracy).
+    # ``early_rtol``: the bounds on the first 5 / first 10 epochs of the validation-loss curve (the project constants unless the
+    # caller derived others from the reference's own second run); ``extra``: more items for the evidence file.
     cfg = rec["cfg"]
     dataset = cfg.get("dataset", name)
     got, ref, curve_gap, curves, at_ref_epoch = [], [], [], [], []
@@ -233,17 +238,18 @@ def _judge_replay(name, rec, results, out_name, path_label="general path", bound
         hist = rec[f"hist_{split}"]
         m = min(len(vals), len(hist))
         curves.append({"split": int(split), "val_loss": [round(v, 6) for v in vals], "test_acc": [round(a, 5) for a in accs]})
-        k_ref = int(np.argmin(hist[:, 1]))                 # the epoch the reference run selected
+        # the epoch the reference run selected
+        k_ref = int(np.argmin(hist[:, 1])) if selection == "min_val_loss" else int(np.argmax(hist[:, 4]))
         at_ref_epoch.append(accs[min(k_ref, len(accs) - 1)] - float(hist[k_ref, 2]))
         # same init + same masks: the validation-loss curve tracks the reference's (tightly at first, then within
         # fp32 chaos) and so does the per-epoch test accuracy
-        np.testing.assert_allclose(vals[:5], hist[:5, 1], rtol=2e-4)
+        np.testing.assert_allclose(vals[:5], hist[:5, 1], rtol=early_rtol[0])
         # Film trains without dropout at lr 0.05: the loss curve has isolated spikes whose height is chaotic
         # (and so does the synthetic-label Chameleon run: lr 0.05 under dropout 0.7 -- its curve follows the reference's to six
         # digits for ten epochs, then to 13 % while the loss wanders around its minimum)
         np.testing.assert_allclose(vals[:m], hist[:m, 1], rtol=0.12 if dataset == "film" else (0.2 if cfg["lr"] >= 0.05 else 3e-2))
         if cfg["lr"] >= 0.05:
-            np.testing.assert_allclose(vals[:10], hist[:10, 1], rtol=1e-3)
+            np.testing.assert_allclose(vals[:10], hist[:10, 1], rtol=early_rtol[1])
         curve_gap.append(float(np.mean(accs[m // 2:m]) - np.mean(hist[m // 2:m, 2])))
     got, ref = np.asarray(got), np.asarray(ref)
     print(f"\n{name} ({path_label}): reference-run {100 * ref.mean():.2f} +- {100 * ref.std():.2f}  |  MI355X {100 * got.mean():.2f} "
@@ -259,7 +265,7 @@ def _judge_replay(name, rec, results, out_name, path_label="general path", bound
                    "reference_run_b_minus_a_pp": None if band0 is None else (100 * band0[1]).tolist(),
                    "mean_diff_pp": float(100 * (got.mean() - ref.mean())), "curve_gap_pp": (100 * np.asarray(curve_gap)).tolist(),
                    "at_reference_epoch_diff_pp": (100 * np.asarray(at_ref_epoch)).tolist(),
-                   "curves": curves}, fh)
+                   "curves": curves, **(extra or {})}, fh)
     print(f"   test accuracy at the epoch the reference selected, per split: {np.round(100 * np.asarray(at_ref_epoch), 2).tolist()} pp "
           f"(mean {100 * np.mean(at_ref_epoch):+.2f})")
     # Parity criterion (+-0.2 pp), in three strengths:
