@@ -25,8 +25,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 #define ACM_E16_NEXT_LDS (64 * 8)
 
 
@@ -145,7 +143,7 @@ __device__ __forceinline__ void epi16_body(const acm_conv_agg_fwd_t& p, int n_ro
                 for (int t = 0; t < 4; ++t)
                     D[c][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[c][kb][t], op[c], kb == 0 ? (f32x4){0.f, 0.f, 0.f, 0.f} : D[c][t], 0, 0, 0);
         }
-        // ---- head: statistics and attention scalars of row m (four lanes per row)
+        // ---- head of row m (four lanes per row): mirrors rows16_head, which moved registers / SGPR spills in 6 of 24 instantiations here
         float mean[NC], rstd[NC], gs[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -511,7 +509,7 @@ __device__ __forceinline__ void bwd16_body(const acm_conv_agg_bwd_t& p, int n_ro
 #pragma unroll
             for (int c = 0; c < NC; ++c) mean[c] = hv[c], rstd[c] = hv[NC + c], gsig[c] = hv[2 * NC + c], al[c] = hv[3 * NC + c];
         }
-        // ---- mix / softmax / sigmoid backward: ds_c = dL/ds_c per row
+        // ---- mix / softmax / sigmoid backward: ds_c = dL/ds_c per row (then as K3 of bwd_local16_kernel; no shared helper survived there)
         float dal[NC], ds[NC];
         if (NC == 4) {                               // H_S dot dO (the rows are read again in the channel's own pass)
             float part = 0.f;

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(512, 2) void aggw_head_kernel(int n_rows, int K, in
             }
         }
     }
-    // u_c = gamma_c (.) att_vec_c (LayerNorm folded into the attention vector, as in acm_conv_agg16.hip)
+    // u_c = gamma_c (.) att_vec_c (LayerNorm folded into the attention vector: rows16_head)
 #pragma unroll
     for (int c = 0; c < 3; ++c) {                  // (compile-time channel indices only: see acm_conv_agg16.hip)
         if (wv == c) {
@@ -175,68 +175,12 @@ __global__ __launch_bounds__(512, 2) void aggw_head_kernel(int n_rows, int K, in
                 *reinterpret_cast<f32x4*>(zi + rr * ld_zi + 16 * t + 4 * g) = D[2][t];
             }
         }
-        // ---- head: statistics and attention scalars of row m (four lanes per row), as acm_conv_agg16.hip: epi16_body
+        // ---- head: statistics and attention scalars of row m (four lanes per row)
         const int gq = acm_opaque(g);
-        float rstd[3], gs[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float lo = c < 2 ? lo_a : lo_m;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) D[c][t][r] = fmaxf(D[c][t][r], lo);
-            float dot = 0.f;
-            if (LN) {
-                float s = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) s += (D[c][t][0] + D[c][t][1]) + (D[c][t][2] + D[c][t][3]);
-                const float mu = row4_sum(s) * (1.0f / 64.0f);
-                float q = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const f32x4 u = *reinterpret_cast<const f32x4*>(ulds + c * 64 + 16 * t + 4 * gq);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float d = D[c][t][r] - mu;
-                        q = fmaf(d, d, q);
-                        dot = fmaf(d, u[r], dot);
-                    }
-                }
-                rstd[c] = acm_rsqrt(row4_sum(q) * (1.0f / 64.0f) + ACM_LN_EPS);
-                dot = fmaf(rstd[c], row4_sum(dot), c0[c]);
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const f32x4 u = *reinterpret_cast<const f32x4*>(ulds + c * 64 + 16 * t + 4 * gq);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) dot = fmaf(D[c][t][r], u[r], dot);
-                }
-                dot = row4_sum(dot);
-            }
-            gs[c] = acm_rcp(1.0f + acm_exp(-dot));
-        }
-        float al[3];
-        {
-            float lg[3], mx = -INFINITY, den = 0.f;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                float a = 0.f;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) a = fmaf(gs[c], mixm[c * 3 + j], a);
-                lg[j] = a * (1.0f / 3.0f);
-                mx = fmaxf(mx, lg[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                lg[j] = acm_exp(lg[j] - mx);
-                den += lg[j];
-            }
-            const float inv = acm_rcp(den);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) al[j] = lg[j] * inv;
-        }
+        float mean[3], rstd[3], gs[3], al[3];
+        rows16_head<3, LN>(D, ulds, gq, c0, mixm, lo_a, lo_m, mean, rstd, gs, al);
         if (valid && g == 1) *reinterpret_cast<float4*>(p.att + (size_t)rr * 4) = make_float4(al[0], al[1], al[2], 0.f);
-        // ---- mix, post-op, store
+        // ---- mix, post-op, store (the arithmetic of acm_conv_agg16.hip: epi16_body, written out again)
         const float a0 = al[0] * p.scale, a1 = al[1] * p.scale, a2 = al[2] * p.scale;
         f32x4 o[4];
 #pragma unroll
@@ -280,7 +224,6 @@ __global__ __launch_bounds__(512, 2) void aggw_head_kernel(int n_rows, int K, in
 //       for the whole launch: dW[c][16 w + 4 g + r][16 t + j].
 // At the end a workgroup leaves ONE partial of the weight gradients (groups of 32 elements: whole 128-byte lines for the second
 // phase) and one of the head-parameter sums; acm_reduce_emit finishes both (deferred: inside the optimizer's launch).
-constexpr int AWB_NPG = 3 * 3 * 64 + 9;            // head-parameter partial vector (the layout of bwd_local16_kernel)
 constexpr int AWB_SLAB = 64;                       // rows per slab = 4 producer waves x 16
 constexpr int AWB_GS = 2 * 2 * 3 * AW_TILES * 64;  // u32x4 entries of the G operand buffers: [buffer 2][sub 2][part 3][tile 12][lane 64]
 
@@ -309,28 +252,8 @@ __global__ __launch_bounds__(512, 2) void aggw_bwd_kernel(acm_conv_bwd_local_t p
     float* hl = reinterpret_cast<float*>(Gs + AWB_GS);             // [att_vec | gamma | beta][c][col]
     float* ul = hl + 576;                                           // u_c = att_vec_c (.) gamma_c
     const int lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4, wv = threadIdx.x >> 6;
-    for (int idx = threadIdx.x; idx < 576; idx += 512) {
-        const int arr = idx / 192, c = (idx / 64) % 3, col = idx & 63;
-        float v;
-        if (arr == 0) v = p.att_vec[c][col];
-        else if (LN) v = arr == 1 ? p.ln_weight[c][col] : p.ln_bias[c][col];
-        else v = arr == 1 ? 1.f : 0.f;
-        hl[idx] = v;
-    }
-    if (threadIdx.x < 192) {
-        const int c = threadIdx.x >> 6, col = threadIdx.x & 63;
-        float u = p.att_vec[c][col];
-        if (LN) u *= p.ln_weight[c][col];
-        ul[threadIdx.x] = u;
-    }
     float c1[3], c0[3];                    // mean_col(u_c); sum_col beta_c v_c
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float u = p.att_vec[c][lane];
-        c0[c] = LN ? acm_group_sum<64>(p.ln_bias[c][lane] * u) : 0.f;
-        if (LN) u *= p.ln_weight[c][lane];
-        c1[c] = acm_group_sum<64>(u) * (1.0f / 64.0f);
-    }
+    rows16_stage_head_params<3, LN>(p, 512, lane, hl, ul, c0, c1);
     float mixm[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) mixm[q] = p.att_mix[q];
@@ -385,66 +308,9 @@ __global__ __launch_bounds__(512, 2) void aggw_bwd_kernel(acm_conv_bwd_local_t p
 #pragma unroll
         for (int t = 0; t < 4; ++t) dO[t] = ndO[t];
         float mean[3], rstd[3], gsig[3], al[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float lo = c < 2 ? lo_a : lo_m;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) D[c][t][r] = fmaxf(D[c][t][r], lo);
-            float dot = 0.f;
-            if (LN) {
-                float s = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) s += (D[c][t][0] + D[c][t][1]) + (D[c][t][2] + D[c][t][3]);
-                const float mu = row4_sum(s) * (1.0f / 64.0f);
-                float q = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const f32x4 u = *reinterpret_cast<const f32x4*>(ul + c * 64 + 16 * t + 4 * gq);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float d = D[c][t][r] - mu;
-                        q = fmaf(d, d, q);
-                        dot = fmaf(d, u[r], dot);
-                    }
-                }
-                mean[c] = mu;
-                rstd[c] = acm_rsqrt(row4_sum(q) * (1.0f / 64.0f) + ACM_LN_EPS);
-                dot = fmaf(rstd[c], row4_sum(dot), c0[c]);
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const f32x4 u = *reinterpret_cast<const f32x4*>(ul + c * 64 + 16 * t + 4 * gq);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) dot = fmaf(D[c][t][r], u[r], dot);
-                }
-                mean[c] = 0.f;
-                rstd[c] = 1.f;
-                dot = row4_sum(dot);
-            }
-            gsig[c] = acm_rcp(1.0f + acm_exp(-dot));
-        }
-        {
-            float lg[3], mx = -INFINITY, den = 0.f;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                float a = 0.f;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) a = fmaf(gsig[c], mixm[c * 3 + j], a);
-                lg[j] = a * (1.0f / 3.0f);
-                mx = fmaxf(mx, lg[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                lg[j] = acm_exp(lg[j] - mx);
-                den += lg[j];
-            }
-            const float inv = acm_rcp(den);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) al[j] = lg[j] * inv;
-        }
+        rows16_head<3, LN>(D, ul, gq, c0, mixm, lo_a, lo_m, mean, rstd, gsig, al);
         // undo the forward's fused post-op on the incoming gradient: ReLU of the mixed row (recomputed), dropout (regenerated)
+        // (from here to the end of the channel loop the arithmetic of bwd_local16_kernel, acm_conv_local16.hip, written out again)
         if (p.post_relu) {
 #pragma unroll
             for (int t = 0; t < 4; ++t)
@@ -543,7 +409,7 @@ __global__ __launch_bounds__(512, 2) void aggw_bwd_kernel(acm_conv_bwd_local_t p
             }
             aw_lds_barrier();                      // slab `it` is in its buffer; the other buffer is free again
         }
-    // ---- head-parameter sums (as bwd_local16_kernel): value i = 4 t + r of lane (g, m = i) is column 16 t + 4 g + r
+    // ---- head-parameter sums (written out as in bwd_local16_kernel): value i = 4 t + r of lane (g, m = i) is column 16 t + 4 g + r
     const int mycol = 16 * (m >> 2) + 4 * g + (m & 3);
     float dv[3], dgam[3], dbet[3];
 #pragma unroll
@@ -557,7 +423,7 @@ __global__ __launch_bounds__(512, 2) void aggw_bwd_kernel(acm_conv_bwd_local_t p
 #pragma unroll
     for (int q = 0; q < 9; ++q) dmix[q] = acm_group_sum<64>(dmix[q]);
         // (the last barrier of the loop: every consumer is done with the operand buffers these slabs alias)
-        float* slabv = lds + wv * AWB_NPG;
+        float* slabv = lds + wv * ROWS16_NPG;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             slabv[(0 * 3 + c) * 64 + mycol] = dv[c];
@@ -663,11 +529,11 @@ __global__ __launch_bounds__(512, 2) void aggw_bwd_kernel(acm_conv_bwd_local_t p
     }
     }
     __syncthreads();
-    for (int q = threadIdx.x; q < AWB_NPG; q += 512) {
+    for (int q = threadIdx.x; q < ROWS16_NPG; q += 512) {
         float sum = 0.f;
 #pragma unroll
-        for (int w8 = 0; w8 < 4; ++w8) sum += lds[w8 * AWB_NPG + q];            // (the four producer waves)
-        part_head[(long)blockIdx.x * AWB_NPG + q] = sum;
+        for (int w8 = 0; w8 < 4; ++w8) sum += lds[w8 * ROWS16_NPG + q];            // (the four producer waves)
+        part_head[(long)blockIdx.x * ROWS16_NPG + q] = sum;
     }
 }
 
@@ -732,7 +598,7 @@ extern "C" int acm_conv_aggw_bwd_workspace_bytes(int64_t n_rows, int64_t f_pad, 
     ACM_REQUIRE(bytes, ACM_EINVAL, "acm_conv_aggw_bwd_workspace_bytes: NULL argument");
     ACM_REQUIRE(n_rows >= 0 && f_pad > 0 && f_pad <= 128, ACM_ESHAPE, "acm_conv_aggw_bwd_workspace_bytes: bad shape");
     const int nblk = aggw_bwd_blocks(n_rows);
-    *bytes = ((size_t)nblk * AWB_NPG + (size_t)nblk * 3 * aggw_feature_tiles(f_pad) * 16 * 64) * sizeof(float);
+    *bytes = ((size_t)nblk * ROWS16_NPG + (size_t)nblk * 3 * aggw_feature_tiles(f_pad) * 16 * 64) * sizeof(float);
     return ACM_OK;
 }
 
@@ -789,9 +655,9 @@ extern "C" int acm_conv_aggw_bwd(int64_t n_rows, int64_t f_in, int64_t f_pad, co
     for (int which = 0; which < 3; ++which)
         for (int c = 0; c < 3; ++c) {
             float* dst = which == 0 ? p->d_att_vec[c] : (which == 1 ? p->d_ln_weight[c] : p->d_ln_bias[c]);
-            if (dst) segs[n++] = {part_head, nblk, AWB_NPG, (which * 3 + c) * 64, 64, dst, 64, 0, 0, 0, 0, 0};
+            if (dst) segs[n++] = {part_head, nblk, ROWS16_NPG, (which * 3 + c) * 64, 64, dst, 64, 0, 0, 0, 0, 0};
         }
-    segs[n++] = {part_head, nblk, AWB_NPG, 9 * 64, 9, p->d_att_mix, 9, 0, 0, 0, 0, 0};
+    segs[n++] = {part_head, nblk, ROWS16_NPG, 9 * 64, 9, p->d_att_mix, 9, 0, 0, 0, 0, 0};
     float* dws[3] = {d_w_low, d_w_high, d_w_mlp};
     for (int c = 0; c < 3; ++c)
         segs[n++] = {part_w, nblk, 32, c * kt * 16 * 64, (int32_t)(f_in * 64), dws[c], 64, 0, ld_dw, 0, (int32_t)((int64_t)nblk * 32), 0};

@@ -11,37 +11,14 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 template <bool LN>
 __global__ __launch_bounds__(256) void bwd_local16_kernel(acm_conv_bwd_local_t p, int n_rows, float* __restrict__ partial) {
-    constexpr int NPG = 3 * 3 * 64 + 9;
-    __shared__ __attribute__((aligned(16))) float lds[4 * NPG];
+    __shared__ __attribute__((aligned(16))) float lds[4 * ROWS16_NPG];
     const int lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4, wv = threadIdx.x >> 6;
     float* hl = lds;                       // [att_vec | gamma | beta][c][col]: 576 floats
     float* ul = lds + 576;                 // u_c = att_vec_c (.) gamma_c: 192 floats   (both dead before the slabs alias them)
-    for (int idx = threadIdx.x; idx < 576; idx += 256) {
-        const int arr = idx / 192, c = (idx / 64) % 3, col = idx & 63;
-        float v;
-        if (arr == 0) v = p.att_vec[c][col];
-        else if (LN) v = arr == 1 ? p.ln_weight[c][col] : p.ln_bias[c][col];
-        else v = arr == 1 ? 1.f : 0.f;
-        hl[idx] = v;
-    }
-    if (threadIdx.x < 192) {
-        const int c = threadIdx.x >> 6, col = threadIdx.x & 63;
-        float u = p.att_vec[c][col];
-        if (LN) u *= p.ln_weight[c][col];
-        ul[threadIdx.x] = u;
-    }
     float c1[3], c0[3];                    // mean_col(u_c); sum_col beta_c v_c
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float u = p.att_vec[c][lane];
-        c0[c] = LN ? acm_group_sum<64>(p.ln_bias[c][lane] * u) : 0.f;
-        if (LN) u *= p.ln_weight[c][lane];
-        c1[c] = acm_group_sum<64>(u) * (1.0f / 64.0f);
-    }
+    rows16_stage_head_params<3, LN>(p, 256, lane, hl, ul, c0, c1);
     float mixm[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) mixm[q] = p.att_mix[q];
@@ -70,67 +47,8 @@ __global__ __launch_bounds__(256) void bwd_local16_kernel(acm_conv_bwd_local_t p
             D[2][t] = *reinterpret_cast<const f32x4*>(p.s_mlp + r1 * ld_zi + 16 * t + 4 * g);
             dO[t] = *reinterpret_cast<const f32x4*>(p.grad_out + r1 * ld_go + 16 * t + 4 * g);
         }
-        // ---- the head again: statistics and attention scalars of row m
-        float mean[3], rstd[3], gsig[3], al[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float lo = c < 2 ? lo_a : lo_m;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) D[c][t][r] = fmaxf(D[c][t][r], lo);
-            float dot = 0.f;
-            if (LN) {
-                float s = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) s += (D[c][t][0] + D[c][t][1]) + (D[c][t][2] + D[c][t][3]);
-                const float mu = row4_sum(s) * (1.0f / 64.0f);
-                float q = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const f32x4 u = *reinterpret_cast<const f32x4*>(ul + c * 64 + 16 * t + 4 * gq);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float d = D[c][t][r] - mu;
-                        q = fmaf(d, d, q);
-                        dot = fmaf(d, u[r], dot);
-                    }
-                }
-                mean[c] = mu;
-                rstd[c] = acm_rsqrt(row4_sum(q) * (1.0f / 64.0f) + ACM_LN_EPS);
-                dot = fmaf(rstd[c], row4_sum(dot), c0[c]);
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const f32x4 u = *reinterpret_cast<const f32x4*>(ul + c * 64 + 16 * t + 4 * gq);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) dot = fmaf(D[c][t][r], u[r], dot);
-                }
-                mean[c] = 0.f;
-                rstd[c] = 1.f;
-                dot = row4_sum(dot);
-            }
-            gsig[c] = acm_rcp(1.0f + acm_exp(-dot));
-        }
-        {
-            float lg[3], mx = -INFINITY, den = 0.f;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                float a = 0.f;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) a = fmaf(gsig[c], mixm[c * 3 + j], a);
-                lg[j] = a * (1.0f / 3.0f);
-                mx = fmaxf(mx, lg[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                lg[j] = acm_exp(lg[j] - mx);
-                den += lg[j];
-            }
-            const float inv = acm_rcp(den);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) al[j] = lg[j] * inv;
-        }
+        float mean[3], rstd[3], gsig[3], al[3];       // the head again: statistics and attention scalars of row m
+        rows16_head<3, LN>(D, ul, gq, c0, mixm, lo_a, lo_m, mean, rstd, gsig, al);
         // ---- undo the forward's fused post-op on the incoming gradient: ReLU of the mixed row (recomputed), dropout (regenerated)
         if (p.post_relu) {
 #pragma unroll
@@ -238,7 +156,7 @@ __global__ __launch_bounds__(256) void bwd_local16_kernel(acm_conv_bwd_local_t p
 #pragma unroll
     for (int q = 0; q < 9; ++q) dmix[q] = acm_group_sum<64>(dmix[q]);
     __syncthreads();                               // every wave is done with the staged parameters
-    float* slab = lds + wv * NPG;
+    float* slab = lds + wv * ROWS16_NPG;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         slab[(0 * 3 + c) * 64 + mycol] = dv[c];
@@ -252,8 +170,8 @@ __global__ __launch_bounds__(256) void bwd_local16_kernel(acm_conv_bwd_local_t p
         slab[9 * 64 + lane] = v;
     }
     __syncthreads();
-    for (int q = threadIdx.x; q < NPG; q += 256)
-        partial[(long)blockIdx.x * NPG + q] = (lds[q] + lds[NPG + q]) + (lds[2 * NPG + q] + lds[3 * NPG + q]);
+    for (int q = threadIdx.x; q < ROWS16_NPG; q += 256)
+        partial[(long)blockIdx.x * ROWS16_NPG + q] = (lds[q] + lds[ROWS16_NPG + q]) + (lds[2 * ROWS16_NPG + q] + lds[3 * ROWS16_NPG + q]);
 }
 
 }  // namespace
