@@ -1,0 +1,26 @@
+"""Operator-level host code: thin wrappers over the C ABI and the autograd
+Functions that make the HIP kernels differentiable.
+
+Every function here launches HIP kernels from libacm_hip.so on the current
+torch stream.  There is deliberately no eager/torch fallback: a CPU tensor or a
+missing library is an error.
+
+Beside the three device seams (``_device_ctx`` / ``_require_cuda`` / ``_stream``: ``_launch`` looks them up HERE at call
+time, so that a test double replaces them in one place) and ``_gather_rows`` (the routes call it through this namespace, where
+a test counts halo exchanges), this file only re-exports what the project and the tests reach as ``functional.NAME``: ``_launch`` (the launch block, its
+timing and argument marshalling), ``_context`` (step- and call-scoped state), ``ops`` (single-kernel operators), ``linear`` (the
+residual branch), ``conv`` (the layer's entry point) over ``_conv_shared``, ``conv_agg`` and ``conv_literal`` (its four routes).
+"""
+from .. import _lib, tuning  # noqa: F401
+from ..graph import CsrGraph, FilterOperators, SparseFeatures, _device_ctx, _require_cuda, _stream  # noqa: F401  (the seams)
+from ._launch import KernelTimer, _Timed, set_kernel_timer  # noqa: F401
+from ._context import (CallContext, DeferredReductions, InputPipeline, Tape, TapeBroken, _ambient,  # noqa: F401
+                       deferred_reductions, deferred_reductions_as, fused_loss_tail, input_pipeline, on_tape)
+from .ops import (DropoutState, _drop_spec, agg_pad_width, cast_bf16, dropout, eval_metrics, eval_metrics_buffers,  # noqa: F401
+                  gemm, gemm_drop_supported, gemm_split, masked_nll, mm, nll_loss_and_grad, proj3, proj_bwd,
+                  proj_bwd_supported, proj_fwd, spmm, spmm_v)
+from .linear import residual_add_linear, residual_add_supported, residual_linear  # noqa: F401
+from ._conv_shared import AcmConfig, _flat_views, _gather_rows, _ptr_array  # noqa: F401
+from .conv_agg import AGG_WIDE_MIN_DEGREE, _AcmAggWide, agg_wide_supported  # noqa: F401
+from .conv_literal import _AcmAcmii  # noqa: F401
+from .conv import _conv_route, acm_conv, in_drop_supported  # noqa: F401

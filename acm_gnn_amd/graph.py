@@ -706,7 +706,8 @@ def operators_for(adj_low, adj_high=None, adj_low_unnormalized=None, verify=True
         # General operator pair: the filters are not (A_low, I - A_low[, D A_low - I]) -- e.g. the
         # reference's k-hop ACM-SGC passes A_low^k with an un-powered adj_high
         # (ACM-Pytorch/utils.py:631-637).  Each channel then gets its own plain SpMM and the fused
-        # kernels run over the identity operator as row-local epilogues (functional._forward_general).
+        # kernels run over the identity operator as row-local epilogues (the ``general`` branches of
+        # functional/conv_literal.py: _AcmLiteral.forward, _literal_backward).
         ops = FilterOperators(low, None)
         ops.general = True
         ops.high = CsrGraph.from_torch(adj_high) if adj_high is not None else None
