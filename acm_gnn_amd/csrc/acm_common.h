@@ -268,6 +268,32 @@ __device__ __forceinline__ float acm_nll_row(int C, const float* zi, int yi, flo
     return wi * (lse - zy);
 }
 
+// One row of the masked BCE-with-logits against the one-hot of yi (acm_bce_loss): di = (wi / C) (sigmoid(zi) - [c == yi]);
+// returns (wi / C) sum_c (max(z, 0) - z [c == yi] + log1p(exp(-|z|))) -- exp never sees a positive argument.  The target is
+// formed by comparison: yi outside [0, C) is the all-zero target and indexes nothing.  wi == 0: zero gradient, no loss, yi
+// not looked at.  di == NULL: loss only.
+__device__ __forceinline__ float acm_bce_row(int C, const float* zi, int64_t yi, float wi, float* di) {
+    if (wi == 0.f) {
+        if (di)
+            for (int c = 0; c < C; ++c) di[c] = 0.f;
+        return 0.f;
+    }
+    const float s = wi / (float)C;
+    float acc = 0.f;
+    for (int c = 0; c < C; ++c) {
+        const float z = zi[c];
+        const bool hit = (int64_t)c == yi;
+        const float e = expf(-fabsf(z));                 // in (0, 1]
+        acc += fmaxf(z, 0.f) - (hit ? z : 0.f) + log1pf(e);
+        if (di) {
+            const float r = 1.0f / (1.0f + e);
+            const float sig = z >= 0.f ? r : e * r;
+            di[c] = s * (sig - (hit ? 1.f : 0.f));
+        }
+    }
+    return s * acc;
+}
+
 // ------------------------------------------------------------------ counter-based dropout (acm_dropout_t)
 struct AcmDropCtx {
     unsigned k0, k1, c2, c3, thresh, tag16;

@@ -15,6 +15,7 @@ SHAPES = {
     "arxiv-year": (169_343, 1_166_243, 128, 5),
     "penn94": (41_554, 1_362_229, 4_814, 2),
     "squirrel": (5_201, 198_353, 2_089, 5),
+    "genius": (421_961, 984_979, 12, 2),                  # trained with BCE-with-logits, scored by ROC-AUC (train.py:86-92)
     "tiny": (2_000, 20_000, 7, 2),
 }
 
@@ -80,7 +81,7 @@ def synthetic_dataset(name, seed=0, uniform=False, pad_to=1):
     ``pad_to`` > 1 appends isolated dummy nodes so that n is a multiple of it (row sharding)."""
     n, e, f_in, c = SHAPES[name]
     max_deg = {"twitch-gamer": 35_000, "arxiv-year": 13_000, "penn94": 4_400, "squirrel": 1_900,
-               "tiny": 300}[name]
+               "genius": 3_000, "tiny": 300}[name]
     adj = chung_lu_graph(n, e, max_deg, seed=seed, uniform=uniform)
     rng = np.random.default_rng(seed + 1)
     if name == "penn94":                                   # one-hot style sparse binary features

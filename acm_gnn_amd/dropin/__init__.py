@@ -225,27 +225,40 @@ def install_fast_evaluate():
     (``acm_eval_metrics``, weights 1 on a split's rows: exact counts) and ONE four-byte-per-number copy, WHERE IT APPLIES:
     ``eval_func`` is the module's own ``eval_acc``, integer labels of shape [n] / [n, 1] on the GPU, fp32 logits of <= 64 classes.
     Same return value ``(train_acc, valid_acc, test_acc, out)`` -- the accuracies are count / len in float64 exactly as the
-    reference forms them.  Anything else (``eval_rocauc``, multi-label targets, a precomputed ``result``) runs the reference's
-    own function.  Returns the function that was bound before (None when there is no ``data_utils.evaluate_acmgcn``)."""
+    reference forms them.
+
+    ``eval_func is data_utils.eval_rocauc`` (genius, twitch-e, yelp-chi, ``--rocauc``; data_utils.py:128-151: softmax, three
+    copies of the scores to the host, three ``sklearn.metrics.roc_auc_score`` calls) takes the same route under the same
+    conditions plus ``2 <= C <= 64``: the forward, then the ROC-AUC launches over three 0/1 weight rows (``AF.eval_rocauc``:
+    softmax(out)[:, 1] scores, one ``torch.sort``, the exact integer Mann-Whitney statistic with ties at one half) and ONE copy of
+    nine integers; ``AUC = U2 / (2 npos nneg)`` is formed from them in Python.  A split where an AUC is undefined (one class only)
+    or that holds a label other than 0 / 1 is handed to the reference's function with ``result=out``, which raises or averages
+    exactly as it always did.
+
+    Anything else (multi-label targets, a precomputed ``result``) runs the reference's own function.  Returns the function that
+    was bound before (None when there is no ``data_utils.evaluate_acmgcn``)."""
     try:
         du = importlib.import_module("data_utils")
     except ImportError:
         return None
     ref, ref_acc = getattr(du, "evaluate_acmgcn", None), getattr(du, "eval_acc", None)
+    ref_auc = getattr(du, "eval_rocauc", None)
     if ref is None or ref_acc is None or getattr(ref, "_acm_fused", False):
         return None
     import torch
-    cache = []                                      # [(split_idx, label, labels_flat, weights, sizes, buffers)], newest last
+    cache = []                                      # [(split_idx, label, labels_flat, weights, sizes, buffers, auc)], newest last
 
     def evaluate_acmgcn(model, x, adj_low, adj_high, adj_low_unnormalized, dataset, split_idx, eval_func, result=None):
         label = getattr(dataset, "label", None)
-        ok = (result is None and eval_func is ref_acc and isinstance(label, torch.Tensor) and _ON_DEVICE(label)
+        ok = (result is None and (eval_func is ref_acc or (ref_auc is not None and eval_func is ref_auc))
+              and isinstance(label, torch.Tensor) and _ON_DEVICE(label)
               and label.dtype == torch.int64 and (label.dim() == 1 or (label.dim() == 2 and label.shape[1] == 1))
               and isinstance(split_idx, dict) and all(isinstance(split_idx.get(k), torch.Tensor) for k in ("train", "valid", "test")))
         if not ok:
             return ref(model, x, adj_low, adj_high, adj_low_unnormalized, dataset, split_idx, eval_func, result)
         try:
-            return fast(model, x, adj_low, adj_high, adj_low_unnormalized, dataset, split_idx, eval_func, label)
+            res = fast(model, x, adj_low, adj_high, adj_low_unnormalized, dataset, split_idx, eval_func, label)
+            handed_over = len(res) == 1
         except Exception as exc:                 # noqa: BLE001 -- a binding must never break the script it serves
             why = f"{type(exc).__name__}: {exc}"
             if why not in _WARNED:
@@ -253,15 +266,20 @@ def install_fast_evaluate():
                 import warnings
                 warnings.warn(f"acm_gnn_amd.dropin: data_utils.evaluate_acmgcn stays the reference's own ({why})", stacklevel=2)
             return ref(model, x, adj_low, adj_high, adj_low_unnormalized, dataset, split_idx, eval_func, result)
+        if handed_over:                          # the reference's function on the logits of the pass, OUTSIDE the guard: what it
+            return ref(model, x, adj_low, adj_high, adj_low_unnormalized, dataset, split_idx, eval_func, res[0])   # raises is its answer
+        return res
 
     def fast(model, x, adj_low, adj_high, adj_low_unnormalized, dataset, split_idx, eval_func, label):
         with torch.no_grad():
             model.eval()
             out = model(x, adj_low, adj_high, adj_low_unnormalized)
-            if not (out.dim() == 2 and out.shape[1] <= 64 and out.dtype == torch.float32 and _ON_DEVICE(out) and out.stride(1) == 1):
+            auc = eval_func is not ref_acc
+            if not (out.dim() == 2 and out.shape[1] <= 64 and out.dtype == torch.float32 and _ON_DEVICE(out) and out.stride(1) == 1
+                    and (not auc or out.shape[1] >= 2)):
                 return ref(model, x, adj_low, adj_high, adj_low_unnormalized, dataset, split_idx, eval_func, out)
             from .. import functional as AF
-            entry = next((e for e in cache if e[0] is split_idx and e[1] is label), None)
+            entry = next((e for e in cache if e[0] is split_idx and e[1] is label and e[6] == auc), None)
             if entry is None:
                 n = label.shape[0]
                 w = torch.zeros(3, n, dtype=torch.float32, device=label.device)
@@ -271,10 +289,18 @@ def install_fast_evaluate():
                     idx = idx.nonzero().view(-1) if idx.dtype == torch.bool else idx.long()
                     w[q].index_fill_(0, idx, 1.0)                    # (weight 1: the sums are exact counts below 2^24)
                     sizes.append(int(idx.numel()))
-                entry = (split_idx, label, label.reshape(-1).contiguous(), w, sizes, AF.eval_metrics_buffers(n, 3, label.device))
+                bufs = AF.rocauc_buffers(n, 3, label.device) if auc else AF.eval_metrics_buffers(n, 3, label.device)
+                entry = (split_idx, label, label.reshape(-1).contiguous(), w, sizes, bufs, auc)
                 cache.append(entry)
                 del cache[:-4]
-            _, _, flat, w, sizes, bufs = entry
+            _, _, flat, w, sizes, bufs, _ = entry
+            if auc:
+                triples = AF.eval_rocauc(out, flat, w, bufs, return_counts=True)[1].tolist()      # the one synchronising copy
+                if any(npos == 0 or nneg == 0 or npos + nneg != sizes[q] for q, (_, npos, nneg) in enumerate(triples)):
+                    # undefined on a split, or labels the score does not cover: the reference decides (it raises, or averages)
+                    return (out,)
+                aucs = [u2 / (2 * npos * nneg) for u2, npos, nneg in triples]
+                return aucs[0], aucs[1], aucs[2], out
             counts = AF.eval_metrics(out, flat, w, 1, bufs).tolist()          # the one synchronising copy of the pass
         accs = [float(counts[q]) / sizes[q] if sizes[q] else float("nan") for q in range(3)]
         return accs[0], accs[1], accs[2], out

@@ -16,9 +16,9 @@ from ..graph import CsrGraph, FilterOperators, SparseFeatures, _device_ctx, _req
 from ._launch import KernelTimer, _Timed, set_kernel_timer  # noqa: F401
 from ._context import (CallContext, DeferredReductions, InputPipeline, Tape, TapeBroken, _ambient,  # noqa: F401
                        deferred_reductions, deferred_reductions_as, fused_loss_tail, input_pipeline, on_tape)
-from .ops import (DropoutState, _drop_spec, agg_pad_width, cast_bf16, dropout, eval_metrics, eval_metrics_buffers,  # noqa: F401
-                  gemm, gemm_drop_supported, gemm_split, masked_nll, mm, nll_loss_and_grad, proj3, proj_bwd,
-                  proj_bwd_supported, proj_fwd, spmm, spmm_v)
+from .ops import (DropoutState, _drop_spec, agg_pad_width, bce_loss, bce_loss_and_grad, cast_bf16, dropout, eval_metrics,  # noqa: F401
+                  eval_metrics_buffers, eval_rocauc, gemm, gemm_drop_supported, gemm_split, masked_bce, masked_nll, mm, nll_loss_and_grad, proj3, proj_bwd,
+                  proj_bwd_supported, proj_fwd, rocauc_buffers, spmm, spmm_v)
 from .linear import residual_add_linear, residual_add_supported, residual_linear  # noqa: F401
 from ._conv_shared import AcmConfig, _flat_views, _gather_rows, _ptr_array  # noqa: F401
 from .conv_agg import AGG_WIDE_MIN_DEGREE, _AcmAggWide, agg_wide_supported  # noqa: F401

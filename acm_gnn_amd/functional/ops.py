@@ -1,5 +1,5 @@
-"""The single-kernel operators: the gemm family, the narrow projections, spmm, the bf16 cast, the masked NLL, the evaluation
-metrics and the counter-based dropout -- raw launches and, where a model differentiates through them, their autograd
+"""The single-kernel operators: the gemm family, the narrow projections, spmm, the bf16 cast, the masked NLL and BCE, the evaluation
+metrics (accuracy / NLL, ROC-AUC) and the counter-based dropout -- raw launches and, where a model differentiates through them, their autograd
 Functions."""
 import ctypes as C
 
@@ -287,6 +287,123 @@ def eval_metrics(logits, labels, weights, loss_set, buffers=None):
     launch("acm_eval_metrics", f"eval_metrics/{n}x{c}k{k}", logits.device, n, c, _vp(logits), logits.stride(0), _vp(labels), _vp(weights),
            weights.stride(0), k, int(loss_set), _vp(res), _vp(ws), ws.numel() * 4)
     return res
+
+
+# ---- the second protocol: masked BCE-with-logits on one-hot labels, ROC-AUC (ACM-Geometric/train.py:86-92, 123-131) ----
+def _check_rows(who, logits, labels, n_classes_min=1):
+    """The public entry points below take their operands as they are -- fp32 logits [n, C] with unit column stride, int64
+    labels [n], contiguous, on the logits' device -- and say so instead of converting or reading something else."""
+    _check_device(logits, "logits")
+    _check_device(labels, "labels")
+    if logits.dim() != 2 or logits.dtype != _F32 or logits.shape[1] < n_classes_min or logits.stride(1) != 1 \
+            or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]):
+        raise ValueError(f"{who}: logits must be fp32 [n, C >= {n_classes_min}] with stride(1) == 1")
+    if logits.shape[1] > 64:
+        raise ValueError(f"{who}: {logits.shape[1]} classes > 64")
+    if labels.dtype != torch.int64 or labels.dim() != 1 or labels.shape[0] != logits.shape[0] or not labels.is_contiguous():
+        raise ValueError(f"{who}: labels must be a contiguous int64 [n] tensor")
+    if labels.device != logits.device:
+        raise ValueError(f"{who}: labels are on {labels.device}, logits on {logits.device}")
+
+
+def _check_weights(who, weights, shape, dev):
+    _check_device(weights, "weights")
+    if weights.dtype != _F32 or tuple(weights.shape) != tuple(shape) or weights.stride(-1) != 1 or weights.device != dev \
+            or (weights.dim() == 2 and weights.shape[0] > 1 and weights.stride(0) < weights.shape[1]):
+        raise ValueError(f"{who}: weights must be fp32 {list(shape)} with contiguous rows on {dev}")
+
+
+def _bce_launch(z, y, w, defer, dz):
+    """acm_bce_loss on checked operands; ``dz`` None = loss only.  Returns the loss scalar."""
+    n, c = z.shape
+    loss = torch.empty((), dtype=_F32, device=z.device)
+    ws = _workspace(z.device, "acm_bce_loss_workspace_bytes", n)
+    launch("acm_bce_loss", f"bce_loss/{n}x{c}", z.device, n, c, _vp(z), z.stride(0), _vp(y), _vp(w), _vp(loss), _vp(dz),
+           dz.stride(0) if dz is not None else 0, _vp(ws), ws.numel() * 4, defer.pointer() if defer is not None else None)
+    if defer is not None:
+        defer.hold(ws, [loss])
+    return loss
+
+
+class _MaskedBce(torch.autograd.Function):
+    """loss = sum_i w_i / C * sum_c bce(z_ic, [c == y_i]) with its gradient from the same pass (acm_bce_loss)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, row_weight, defer=None, out=None):
+        _check_rows("masked_bce", logits, labels)
+        _check_weights("masked_bce", row_weight, (logits.shape[0],), logits.device)
+        if out is None:
+            dz = torch.empty(logits.shape, dtype=_F32, device=logits.device)
+        else:
+            dz = out
+            if dz.dtype != _F32 or dz.shape != logits.shape or dz.stride(1) != 1 or dz.device != logits.device \
+                    or (dz.shape[0] > 1 and dz.stride(0) < dz.shape[1]):
+                raise ValueError("masked_bce: out must be fp32 with the logits' shape, stride(1) == 1, on their device")
+        loss = _bce_launch(logits, labels, row_weight, defer, dz)
+        ctx.save_for_backward(dz)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        (dz,) = ctx.saved_tensors
+        return dz * grad_loss, None, None, None, None
+
+
+def masked_bce(logits, labels, row_weight):
+    """nn.BCEWithLogitsLoss() against the one-hot of ``labels`` over the rows with non-zero weight (weights = 1/|train| on
+    the training rows -- train.row_weights -- reproduce ``criterion(out[train_idx], F.one_hot(label)[train_idx].float())``,
+    ACM-Geometric/train.py:86-92, 123-131).  Rows of weight 0 may carry the label -1."""
+    return _run(_MaskedBce, logits, labels, row_weight, _ambient().defer, None)
+
+
+def bce_loss_and_grad(logits, labels, row_weight, defer=None, out=None):
+    """(loss, dloss/dlogits) of the masked BCE in one launch, outside autograd (see nll_loss_and_grad).  ``out``: an fp32
+    buffer for the gradient (any row pitch).  ``defer``: see proj_bwd."""
+    if defer is None:
+        defer = _ambient().defer
+    with torch.no_grad():
+        ctx = _NoCtx()
+        loss = _MaskedBce.forward(ctx, logits.detach(), labels, row_weight, defer, out)
+    return loss, ctx.saved[0]
+
+
+def bce_loss(logits, labels, row_weight):
+    """The masked BCE alone (acm_bce_loss with a NULL gradient): the validation loss of an evaluation pass."""
+    _check_rows("bce_loss", logits, labels)
+    _check_weights("bce_loss", row_weight, (logits.shape[0],), logits.device)
+    return _bce_launch(logits.detach(), labels, row_weight, None, None)
+
+
+def rocauc_buffers(n_rows, n_sets, device):
+    """(scores fp32 [n], counts int64 [k, 3], auc float64 [k], workspace) for :func:`eval_rocauc`: made once by a caller whose
+    pass is captured (the addresses are baked in).  Nothing needs initialising."""
+    nbytes = _workspace_bytes("acm_rocauc_workspace_bytes", int(n_rows), int(n_sets))
+    return (torch.empty(int(n_rows), dtype=_F32, device=device), torch.empty(int(n_sets), 3, dtype=torch.int64, device=device),
+            torch.empty(int(n_sets), dtype=torch.float64, device=device),
+            torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device))
+
+
+def eval_rocauc(logits, labels, weights, buffers=None, return_counts=False):
+    """ROC-AUC of softmax(logits)[:, 1] against ``labels`` on every index set, on the device (data_utils.eval_rocauc for
+    single-column labels, ACM-Geometric/data_utils.py:128-151, without its three copies to the host): acm_rocauc_scores, ONE
+    ``torch.sort`` of the n scores for all sets, acm_rocauc.  ``weights`` [k, n]: non-zero on a set's rows (k <= 8); of those
+    the rows labelled 0 / 1 are the set's negatives / positives, any other label is skipped.  Returns the float64 device
+    tensor [k] of AUCs -- NaN where a set lacks a class -- and with ``return_counts`` also the exact int64 [k, 3] triples
+    (U2, npos, nneg), AUC = U2 / (2 npos nneg).  Both are views of ``buffers`` when given."""
+    _check_rows("eval_rocauc", logits, labels, n_classes_min=2)
+    n, c = logits.shape
+    if weights.dim() != 2 or not 1 <= weights.shape[0] <= 8:
+        raise ValueError("eval_rocauc: weights must be [k, n] with 1 <= k <= 8 index sets")
+    k = weights.shape[0]
+    _check_weights("eval_rocauc", weights, (k, n), logits.device)
+    scores, counts, auc, ws = buffers if buffers is not None else rocauc_buffers(n, k, logits.device)
+    if scores.shape[0] != n or counts.shape[0] != k:
+        raise ValueError("eval_rocauc: buffers were made for another shape (rocauc_buffers(n_rows, n_sets, device))")
+    launch("acm_rocauc_scores", f"rocauc_scores/{n}x{c}", logits.device, n, c, _vp(logits), logits.stride(0), _vp(scores))
+    ranked, order = torch.sort(scores)                  # the one device primitive of the pass that is not this library's
+    launch("acm_rocauc", f"rocauc/{n}k{k}", logits.device, n, _vp(ranked), _vp(order), _vp(labels), _vp(weights), weights.stride(0), k,
+           _vp(counts), _vp(auc), _vp(ws), ws.numel() * 8)
+    return (auc, counts) if return_counts else auc
 
 
 # ---- counter-based dropout (acm_dropout_t) ----

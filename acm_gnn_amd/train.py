@@ -3,12 +3,13 @@
 utils.py:547-574), restated so the op can be trained and measured where the reference's Python
 cannot run.
 
-* ``TrainStep``      one full-batch step: forward, fused masked NLL (acm_nll_loss), backward,
+* ``TrainStep``      one full-batch step: forward, fused masked NLL (acm_nll_loss) or -- the reference's second
+                     protocol, ``criterion="bce"`` -- masked BCE-with-logits on the one-hot labels (acm_bce_loss), backward,
                      optimizer update; optionally captured once in a HIP graph and replayed
                      (every launch of the step is stream-ordered and allocation-free, so the
                      whole step is one graph launch instead of ~60 kernel launches).
-* ``evaluate``       eval-mode forward + accuracy on index sets, on device (the reference pulls the
-                     predictions to the host three times per epoch, data_utils.py:117-118).
+* ``evaluate``       eval-mode forward + accuracy (or, ``metric="rocauc"``, ROC-AUC) on index sets, on device (the
+                     reference pulls the predictions to the host three times per epoch, data_utils.py:117-118, 132-135).
 * ``fit``            the two model-selection rules of the reference.
 """
 import torch
@@ -18,6 +19,14 @@ from . import functional as AF
 from .graph import FilterOperators, SparseFeatures, operators_for
 
 _TORCH_DROPOUT = F.dropout          # to notice a patched F.dropout (mask replay in tests): see TrainStep
+CRITERIA = ("nll", "bce")           # log_softmax + NLLLoss | BCEWithLogitsLoss on one-hot labels (ACM-Geometric/train.py:86-92)
+METRICS = ("acc", "rocauc")         # eval_acc | eval_rocauc (data_utils.py:115-151)
+
+
+def _checked(value, allowed, what):
+    if value not in allowed:
+        raise ValueError(f"{what} must be one of {allowed}, not {value!r}")
+    return value
 
 
 def row_weights(train_idx, n_rows, n_train_total=None, device=None):
@@ -78,8 +87,14 @@ def _capture_mode():
 
 class TrainStep:
     def __init__(self, model, optimizer, x, adj, labels, weights, adj_high=None, adj_un=None, use_graph=False,
-                 fused_dropout=None, pipeline_input=None, steps_per_graph=1, flush_in_optimizer=True, small_step=None, tape=True):
-        """``tape``: eager steps record this package's Functions on a functional.Tape and replay them backwards themselves
+                 fused_dropout=None, pipeline_input=None, steps_per_graph=1, flush_in_optimizer=True, small_step=None, tape=True,
+                 criterion="nll"):
+        """``criterion``: "nll" = log_softmax + NLLLoss on the weighted rows (acm_nll_loss, fused into the output layer where it
+        qualifies); "bce" = nn.BCEWithLogitsLoss() against the one-hot labels (acm_bce_loss: ACM-Geometric/train.py:86-92,
+        123-131 -- genius, twitch-e, yelp-chi, ``--rocauc``), always a launch of its own and never on the fused small-graph step
+        (acm_conv_fwd_tail and acm_small_step compute the NLL).  The same row weights serve both.
+
+        ``tape``: eager steps record this package's Functions on a functional.Tape and replay them backwards themselves
         instead of building an autograd graph (no Function.apply, no AccumulateGrad nodes, no engine hand-off: the host side of
         an eager step); a model with torch operations between its layers falls back to autograd on its first step, for good.
 
@@ -97,6 +112,7 @@ class TrainStep:
         step (fresh counter-based masks: the step counters live on the device); a loop that looks at the model between two
         steps (train.fit's evaluation pass) keeps the default of one."""
         self.model, self.opt = model, optimizer
+        self.criterion = _checked(criterion, CRITERIA, "criterion")
         self.steps_per_call = max(int(steps_per_graph), 1) if use_graph else 1
         self.losses = []
         self.x, self.adj, self.adj_high, self.adj_un = x, adj, adj_high, adj_un
@@ -165,7 +181,8 @@ class TrainStep:
         self.small, self.small_refused = None, "not requested"
         if small_step is not False:
             from .small import SmallPlan
-            why = "the loop advances the dropout counter by hand" if self._manual_advance else \
+            why = 'criterion="bce" (the fused step computes the masked NLL)' if self.criterion != "nll" else \
+                "the loop advances the dropout counter by hand" if self._manual_advance else \
                 SmallPlan.why_not(model, self.x, self.adj, optimizer)
             if why is None and getattr(model, "dropout", 0) > 0 and not getattr(model, "fused_dropout", False):
                 why = "F.dropout masks (counter-based dropout only)"
@@ -268,6 +285,8 @@ class TrainStep:
         """Forward and fused loss: (loss, dloss/dlogits, logits).  The model's output layer is asked to run its row
         phase, the loss and its own row-local backward as one kernel (AF.fused_loss_tail); when it does not qualify
         (wide output, structure channel, a wrapper around the output) the loss is its own launch."""
+        if self.criterion == "bce":
+            return self._forward_bce(call)
         tail = call.tail = AF.fused_loss_tail(self.labels, self.weights)
         kw = {"call": call} if self._takes_call else {}
         if self._permuted:
@@ -281,6 +300,19 @@ class TrainStep:
         if tail.matches(out):
             return tail.loss, tail.dz, out
         loss, dz = AF.nll_loss_and_grad(out, self.labels, self.weights, defer=call.defer)   # = masked_nll(...).backward(), two launches less
+        return loss, dz, out
+
+    def _forward_bce(self, call):
+        """The same forward without a loss-tail request (the fused tail computes the NLL), then acm_bce_loss."""
+        kw = {"call": call} if self._takes_call else {}
+        if self._permuted:
+            kw["rows_permuted"] = True
+        if self._takes_call:
+            out = self.model(self.x, self.adj, self.adj_high, self.adj_un, **kw)
+        else:
+            with AF.deferred_reductions_as(call.defer), AF.input_pipeline(call.pipe):
+                out = self.model(self.x, self.adj, self.adj_high, self.adj_un, **kw)
+        loss, dz = AF.bce_loss_and_grad(out, self.labels, self.weights, defer=call.defer)
         return loss, dz, out
 
     def _eager(self):
@@ -406,13 +438,47 @@ class TrainStep:
 
 
 @torch.no_grad()
-def evaluate(model, x, adj, labels, index_sets, adj_high=None, adj_un=None):
-    """Eval-mode logits and the accuracy on each index set (data_utils.py:153-168)."""
+def evaluate(model, x, adj, labels, index_sets, adj_high=None, adj_un=None, metric="acc"):
+    """Eval-mode logits and the accuracy -- ``metric="rocauc"``: the ROC-AUC (AF.eval_rocauc; NaN where a set lacks a class)
+    -- on each index set (data_utils.py:153-168)."""
+    _checked(metric, METRICS, "metric")
     model.eval()
     out = model(x, adj, adj_high, adj_un)
+    if metric == "rocauc":
+        return out, AF.eval_rocauc(out, labels, _set_weights(index_sets, labels, mean=False)).tolist()
     pred = out.argmax(dim=1)
     accs = [float((pred[idx] == labels[idx]).float().mean()) for idx in index_sets]
     return out, accs
+
+
+def _is_sharded(adj):
+    return isinstance(adj, FilterOperators) and adj.sharded
+
+
+def _selection_key(rule, metric_va, val_loss):
+    """What ``fit`` maximises.  An undefined validation metric (a NaN ROC-AUC: the split lacks a class) never becomes "best":
+    its key is None and the epoch is passed over."""
+    key = metric_va if rule == "max_val_acc" else -val_loss
+    return None if key != key else key
+
+
+def _eager_val_loss(out, labels, val_idx, criterion):
+    """The validation loss of an un-captured epoch, as the reference forms it (train.py:123-135)."""
+    if criterion == "bce":
+        target = (labels[val_idx].view(-1, 1) == torch.arange(out.shape[1], device=out.device).view(1, -1)).to(out.dtype)
+        return float(F.binary_cross_entropy_with_logits(out[val_idx], target))
+    return float(F.nll_loss(F.log_softmax(out, 1)[val_idx], labels[val_idx]))
+
+
+def _set_weights(index_sets, labels, mean=True):
+    """[k, n] fp32 rows: 1 / |set| (``mean``) or 1 on a set's rows, 0 elsewhere.  Index tensors or boolean masks."""
+    n, dev = labels.shape[0], labels.device
+    w = torch.zeros(len(index_sets), n, dtype=torch.float32, device=dev)
+    for k, idx in enumerate(index_sets):
+        idx = torch.as_tensor(idx, device=dev)
+        idx = idx.nonzero().view(-1) if idx.dtype == torch.bool else idx.long()
+        w[k].index_fill_(0, idx, 1.0 / max(int(idx.numel()), 1) if mean else 1.0)
+    return w
 
 
 class EvalStep:
@@ -431,21 +497,26 @@ class EvalStep:
     the same model on other inputs may replace the layers' cache entries, the replay still reads valid memory.
 
     ``small_step`` (None = where it applies): small graphs run the forward as three launches behind one C-ABI call
-    (small.SmallPlan) WITHOUT calling ``model.forward`` -- a model with forward hooks keeps the general path."""
+    (small.SmallPlan) WITHOUT calling ``model.forward`` -- a model with forward hooks keeps the general path.
+
+    The reference's second protocol (ACM-Geometric/train.py:86-92, data_utils.py:128-151): ``metric="rocauc"`` makes the
+    per-set results ROC-AUCs (AF.eval_rocauc: scores, one ``torch.sort``, exact integer statistic; NaN where a set lacks a
+    class) and ``criterion="bce"`` makes the loss on ``loss_set`` the BCE-with-logits against the one-hot labels (acm_bce_loss,
+    loss only).  Still one synchronising copy per pass (float64 then: the AUCs are exact quotients of integers).  The sort is
+    global, so row-sharded operators are refused with ``metric="rocauc"``."""
 
     def __init__(self, model, x, adj, labels, index_sets, adj_high=None, adj_un=None, loss_set=1, use_graph=False,
-                 small_step=None, fused_metrics=True):
+                 small_step=None, fused_metrics=True, metric="acc", criterion="nll"):
         self.model, self.x, self.adj, self.adj_high, self.adj_un = model, x, adj, adj_high, adj_un
+        self.metric, self.criterion = _checked(metric, METRICS, "metric"), _checked(criterion, CRITERIA, "criterion")
+        if self.metric == "rocauc" and _is_sharded(adj):
+            raise NotImplementedError('EvalStep(metric="rocauc"): the ROC-AUC sorts the scores of ALL rows; row-sharded '
+                                      "operators are not supported")
         self.fused_metrics, self._metrics = bool(fused_metrics), None
+        self._auc = None
         self.labels = labels
         self._labels_safe = labels.clamp_min(0)             # -1 = unlabeled (never in an index set)
-        n, dev = labels.shape[0], labels.device
-        w = torch.zeros(len(index_sets), n, dtype=torch.float32, device=dev)
-        for k, idx in enumerate(index_sets):
-            idx = torch.as_tensor(idx, device=dev)
-            idx = idx.nonzero().view(-1) if idx.dtype == torch.bool else idx.long()
-            w[k].index_fill_(0, idx, 1.0 / max(int(idx.numel()), 1))
-        self.w, self.loss_set = w, int(loss_set)
+        self.w, self.loss_set = _set_weights(index_sets, labels), int(loss_set)
         # small graphs: the evaluation forward as one call (small.SmallPlan without an optimizer)
         self.small, self.small_refused = None, "not requested"
         if small_step is not False:
@@ -478,6 +549,8 @@ class EvalStep:
             out = self.small.run()                       # three launches, one C-ABI call (acm_small_step, train = 0)
         else:
             out = self.model(self.x, self.adj, self.adj_high, self.adj_un)
+        if self.metric == "rocauc" or self.criterion == "bce":
+            return out, self._second_protocol(out)
         if self._metrics_ok(out):
             # accuracy on every index set + the NLL on one of them as ONE launch over the logits (acm_eval_metrics, ABI 28)
             # instead of argmax / compare / log_softmax / gather / matmul / sum / cat (eight torch launches)
@@ -486,6 +559,22 @@ class EvalStep:
         nll = -F.log_softmax(out, 1).gather(1, self._labels_safe.view(-1, 1)).view(-1)
         res = torch.cat([self.w @ correct, (self.w[self.loss_set] * nll).sum().view(1)])
         return out, res
+
+    def _second_protocol(self, out):
+        """[metric per index set ..., loss on ``loss_set``] in float64 for ``metric="rocauc"`` and / or ``criterion="bce"``:
+        the library's launches (+ one torch.sort), no fallback."""
+        if self.metric == "rocauc":
+            if self._auc is None:
+                self._auc = AF.rocauc_buffers(out.shape[0], self.w.shape[0], out.device)
+            per_set = AF.eval_rocauc(out, self.labels, self.w, self._auc)
+        else:
+            per_set = (self.w @ (out.argmax(dim=1) == self.labels).to(torch.float32)).double()
+        if self.criterion == "bce":
+            loss = AF.bce_loss(out, self.labels, self.w[self.loss_set])
+        else:
+            nll = -F.log_softmax(out, 1).gather(1, self._labels_safe.view(-1, 1)).view(-1)
+            loss = (self.w[self.loss_set] * nll).sum()
+        return torch.cat([per_set, loss.double().view(1)])
 
     def _metrics_ok(self, out):
         return (self.fused_metrics and out.dim() == 2 and out.shape[1] <= 64 and 1 <= self.w.shape[0] <= 8
@@ -535,8 +624,14 @@ class EvalStep:
 
 
 def fit(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, rule="max_val_acc",
-        early_stopping=0, adj_high=None, adj_un=None, use_graph=False, fused_dropout=None, pipeline_input=None):
+        early_stopping=0, adj_high=None, adj_un=None, use_graph=False, fused_dropout=None, pipeline_input=None,
+        criterion="nll", metric="acc"):
     """Train and return (selected test accuracy, per-epoch history).
+
+    ``criterion`` / ``metric``: the reference's two protocols (ACM-Geometric/train.py:86-92): "nll" + "acc", or -- genius,
+    twitch-e, yelp-chi, ``--rocauc`` -- "bce" + "rocauc".  With "rocauc" the three per-set numbers of a history row and the
+    selected value are ROC-AUCs, ``rule="max_val_acc"`` selects on the validation AUC, and an undefined (NaN) AUC is never
+    "best".  The validation loss follows the criterion.
 
     ``pipeline_input``: TrainStep's input pipeline (None = where the configuration qualifies, False = never).  On by
     default since round 3: with the sixteen-rows-per-wave backward kernel carrying the gather, an epoch (training step +
@@ -550,24 +645,25 @@ def fit(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, 
                            (ACM-Pytorch/train.py:129-139)
     """
     w = row_weights(train_idx, x.shape[0], device=x.device)
+    _checked(metric, METRICS, "metric")
     step = TrainStep(model, optimizer, x, adj, labels, w, adj_high, adj_un, use_graph=use_graph,
-                     fused_dropout=fused_dropout, pipeline_input=pipeline_input)
+                     fused_dropout=fused_dropout, pipeline_input=pipeline_input, criterion=criterion)
     best_key, selected, history = None, 0.0, []
     val_hist = []
     # the evaluation pass of every epoch: its own captured graph when the training step is one
     ev = EvalStep(model, x, adj, labels, (train_idx, val_idx, test_idx), adj_high, adj_un, loss_set=1,
-                  use_graph=use_graph) if use_graph else None
+                  use_graph=use_graph, metric=metric, criterion=criterion) if use_graph else None
     for epoch in range(epochs):
         loss = step()
         if ev is not None:
             out, (acc_tr, acc_va, acc_te), val_loss = ev()
         else:
             out, (acc_tr, acc_va, acc_te) = evaluate(model, x, adj, labels, (train_idx, val_idx, test_idx),
-                                                     adj_high, adj_un)
-            val_loss = float(F.nll_loss(F.log_softmax(out, 1)[val_idx], labels[val_idx]))
+                                                     adj_high, adj_un, metric=metric)
+            val_loss = _eager_val_loss(out, labels, val_idx, criterion)
         history.append((float(loss), acc_tr, acc_va, acc_te, val_loss))
-        key = acc_va if rule == "max_val_acc" else -val_loss
-        if best_key is None or key > best_key:
+        key = _selection_key(rule, acc_va, val_loss)
+        if key is not None and (best_key is None or key > best_key):
             best_key, selected = key, acc_te
         if rule == "min_val_loss":
             val_hist.append(val_loss)
@@ -578,7 +674,7 @@ def fit(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, 
 
 
 def fit_concurrent(runs, x, adj, labels, epochs, rule="min_val_loss", early_stopping=0, adj_high=None, adj_un=None, streams=2,
-                   fused_dropout=None):
+                   fused_dropout=None, criterion="nll", metric="acc"):
     """Several independent training runs on the same graph -- the reference's ten fixed splits, which ACM-Pytorch/train.py:49-139
     trains one after the other, each with a fresh model -- ``streams`` at a time, every run on its own stream with its own
     captured step and evaluation pass: the launches of one run fill the gaps of the other (a small-graph step is a chain of
@@ -587,14 +683,15 @@ def fit_concurrent(runs, x, adj, labels, epochs, rule="min_val_loss", early_stop
 
     ``runs``: a list of ``(model, optimizer, train_idx, val_idx, test_idx)``; every run is exactly ``fit(..., use_graph=True)``
     of its model (same selection rules, same history rows, bit-identical results: the runs share no state but the read-only
-    graph and features).  Returns ``[(selected test accuracy, history)]`` in the order of ``runs``.  Without a GPU stream to
+    graph and features; ``criterion`` / ``metric`` as in ``fit``).  Returns ``[(selected test accuracy, history)]`` in the order of ``runs``.  Without a GPU stream to
     overlap on (CPU test double) the runs are trained one after the other."""
     results = [None] * len(runs)
     on_gpu = labels.is_cuda and torch.cuda.is_available()
     if not on_gpu or streams <= 1:
         for k, (model, opt, tr, va, te) in enumerate(runs):
             results[k] = fit(model, opt, x, adj, labels, tr, va, te, epochs, rule=rule, early_stopping=early_stopping,
-                             adj_high=adj_high, adj_un=adj_un, use_graph=on_gpu, fused_dropout=fused_dropout)
+                             adj_high=adj_high, adj_un=adj_un, use_graph=on_gpu, fused_dropout=fused_dropout,
+                             criterion=criterion, metric=metric)
         return results
     pending = list(range(len(runs)))
     slots = [None] * min(int(streams), len(runs))
@@ -604,8 +701,10 @@ def fit_concurrent(runs, x, adj, labels, epochs, rule="min_val_loss", early_stop
         model, opt, tr, va, te = runs[k]
         with torch.cuda.stream(stream):
             w = row_weights(tr, x.shape[0], device=labels.device)
-            step = TrainStep(model, opt, x, adj, labels, w, adj_high, adj_un, use_graph=True, fused_dropout=fused_dropout)
-            ev = EvalStep(model, x, adj, labels, (tr, va, te), adj_high, adj_un, loss_set=1, use_graph=True)
+            step = TrainStep(model, opt, x, adj, labels, w, adj_high, adj_un, use_graph=True, fused_dropout=fused_dropout,
+                             criterion=criterion)
+            ev = EvalStep(model, x, adj, labels, (tr, va, te), adj_high, adj_un, loss_set=1, use_graph=True, metric=metric,
+                          criterion=criterion)
         stream.synchronize()
         return dict(k=k, step=step, ev=ev, epoch=0, best=None, selected=0.0, history=[], vals=[])
 
@@ -623,8 +722,8 @@ def fit_concurrent(runs, x, adj, labels, epochs, rule="min_val_loss", early_stop
                 _, (acc_tr, acc_va, acc_te), val_loss = sl["ev"].read()
                 loss = float(sl["loss"])
             sl["history"].append((loss, acc_tr, acc_va, acc_te, val_loss))
-            key = acc_va if rule == "max_val_acc" else -val_loss
-            if sl["best"] is None or key > sl["best"]:
+            key = _selection_key(rule, acc_va, val_loss)
+            if key is not None and (sl["best"] is None or key > sl["best"]):
                 sl["best"], sl["selected"] = key, acc_te
             epoch = sl["epoch"]
             done = epoch + 1 >= epochs

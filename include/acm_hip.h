@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define ACM_ABI_VERSION 28
+#define ACM_ABI_VERSION 29
 
 typedef enum {
     ACM_OK = 0,
@@ -857,6 +857,51 @@ int acm_eval_metrics_workspace_bytes(int64_t n_rows, int n_sets, size_t* bytes);
 int acm_eval_metrics(int64_t n_rows, int n_classes, const float* logits, int64_t ld_logits, const int64_t* labels,
                      const float* weights, int64_t ld_weights, int n_sets, int loss_set, float* out,
                      void* workspace, size_t workspace_bytes, acm_stream_t stream);
+
+/* ------------------------------------------------ masked BCE-with-logits (ABI 29) --
+ * The reference's second protocol (genius, twitch-e, yelp-chi, --rocauc): nn.BCEWithLogitsLoss() on the one-hot labels,
+ *     true_label = F.one_hot(label, label.max() + 1).squeeze(1);  loss = criterion(out[train_idx], true_label[train_idx].float())
+ * (ACM-Geometric/train.py:86-92, 123-131) and its autograd, in one pass over the logits:
+ *   l(z, t)  = max(z, 0) - z t + log1p(exp(-|z|))                    (the stable form: exp never sees a positive argument)
+ *   loss     = sum_i w_i * (1/C) * sum_c l(z_ic, [c == y_i])
+ *   dz_ic    = w_i * (1/C) * (sigmoid(z_ic) - [c == y_i])
+ * With w_i = 1/|train| on the training rows and 0 elsewhere this is the mean over rows and classes the criterion takes.
+ * The one-hot target is formed by comparison, never by indexing: a row with w_i == 0 gets dz = 0 and its label is not
+ * interpreted (it may be -1); a row with w_i != 0 and a label outside [0, C) has the all-zero target.  A label never causes
+ * a memory access.  dlogits == NULL: loss only (ld_dlogits is ignored).  Otherwise exactly acm_nll_loss: one thread per
+ * row, n_classes <= 64, strided logits / dlogits, per-block partials in the workspace, second phase through `defer`,
+ * a fixed tree (bit-identical run to run).  Workspace: acm_bce_loss_workspace_bytes.
+ */
+int acm_bce_loss_workspace_bytes(int64_t n_rows, size_t* bytes);
+int acm_bce_loss(int64_t n_rows, int n_classes, const float* logits, int64_t ld_logits,
+                 const int64_t* labels, const float* row_weight,
+                 float* loss, float* dlogits, int64_t ld_dlogits,
+                 void* workspace, size_t workspace_bytes, acm_reduce_list_t* defer, acm_stream_t stream);
+
+/* ------------------------------------------------ ROC-AUC on the device (ABI 29) --
+ * data_utils.eval_rocauc for single-column labels (ACM-Geometric/data_utils.py:128-151: softmax, three device-to-host
+ * copies, sklearn.metrics.roc_auc_score per index set), restated in exact integers.
+ *   Score      s_i = softmax(z_i)[1] in fp32 = exp(z_i1 - m_i) / sum_c exp(z_ic - m_i), m_i the row maximum
+ *              (acm_rocauc_scores; 2 <= n_classes <= 64).  Rows with equal logit differences get bit-equal scores, a
+ *              difference above 20 gives exactly 1.0f.  Scores are non-negative floats: their own order is the sort order.
+ *   Members    of set k: rows with weights[k][i] != 0 and label 0 or 1; other labels in a set are skipped.
+ *   Statistic  per set, exact 64-bit integers:  npos, nneg and
+ *                U2 = sum over positive members p of (2 * #{negative members q: s_q < s_p} + #{q: s_q == s_p})
+ *              -- twice the Mann-Whitney statistic with ties at one half.  AUC = U2 / (2 * npos * nneg) in float64, NaN when
+ *              npos * nneg == 0 (where the reference skips the column or raises).
+ * The caller sorts the n scores once for all sets (ascending) and passes the sorted scores and the int64 order
+ * (order[j] = row at sorted position j).  acm_rocauc then writes counts[k][3] = {U2, npos, nneg} and, unless `auc` is
+ * NULL, auc[k].  Four launches (member flags + tile counts, scan of the tile counts, prefix counts of the negatives, the
+ * statistic); no kernel waits for another block; integer adds only, so every run gives the same bits; an `order` entry
+ * outside [0, n) or a label outside {0, 1} reads nothing.  NaN logits are undefined behaviour (the reference raises).
+ * n_sets <= 8, n_rows < 2^31.  Workspace: acm_rocauc_workspace_bytes, 8-byte aligned, no initialisation needed.
+ */
+int acm_rocauc_scores(int64_t n_rows, int n_classes, const float* logits, int64_t ld_logits, float* scores,
+                      acm_stream_t stream);
+int acm_rocauc_workspace_bytes(int64_t n_rows, int n_sets, size_t* bytes);
+int acm_rocauc(int64_t n_rows, const float* sorted_scores, const int64_t* order, const int64_t* labels,
+               const float* weights, int64_t ld_weights, int n_sets, int64_t* counts, double* auc,
+               void* workspace, size_t workspace_bytes, acm_stream_t stream);
 
 /* ---------------------------------------- output layer + loss + K3, fused --
  * For a narrow OUTPUT layer (f_out = n_classes <= 8, three channels, no post-op) whose result goes straight into the

@@ -61,15 +61,20 @@ CONFIGS = {
     # BASELINE config 5: ACM-SGC 3-hop (one linear ACM layer, the low channel through A_low three times)
     "arxiv-year/acmsgc-3hop": dict(graph="syn:arxiv-year", method="acmsgc", s=0, variant=0, dropout=0.1, hops=3),
     "penn94/acmsgc-3hop/csrX": dict(graph="syn:penn94", method="acmsgc", s=0, variant=0, dropout=0.1, sparse=1, hops=3),
+    # the reference's second protocol (ACM-Geometric/train.py:86-92): BCE-with-logits on the one-hot labels, ROC-AUC per epoch.
+    # Reported next to ms/step: the epoch = step + EvalStep(metric="rocauc"), both captured, and the same epoch with the AUC
+    # formed the reference's way (softmax, three copies to the host, roc_auc_score)
+    "genius/acmgcnp/bce": dict(graph="syn:genius", method="acmgcnp", s=0, variant=0, dropout=0.1, criterion="bce"),
 }
 
 
 def run(name, cfg, steps=20):
     if cfg["graph"].startswith("syn:"):
         ds = cfg["graph"][4:]
-        adj, x_np, y_np, (tr, _, _), n = D.synthetic_dataset(ds)
+        adj, x_np, y_np, splits, n = D.synthetic_dataset(ds)
         perm = D.degree_order(adj)
-        adj, x_np, y_np, (tr, _, _) = D.permute_dataset(adj, x_np, y_np, (tr, tr, tr), perm)
+        adj, x_np, y_np, splits = D.permute_dataset(adj, x_np, y_np, splits, perm)
+        tr = splits[0]
         f_in, classes = x_np.shape[1], int(y_np.max()) + 1
     else:
         adj, g = real_graph(cfg["graph"])
@@ -93,7 +98,8 @@ def run(name, cfg, steps=20):
                             variant=bool(cfg["variant"]), attn_layernorm=True, gather_dtype=cfg.get("gather_dtype")).to(DEV)
     opt = acm_gnn_amd.FusedAdam(model.parameters(), lr=0.01, weight_decay=1e-4)
     w = T.row_weights(torch.from_numpy(tr).to(DEV), n)
-    step = T.TrainStep(model, opt, x, ops, y, w)
+    crit = cfg.get("criterion", "nll")
+    step = T.TrainStep(model, opt, x, ops, y, w, criterion=crit)
     for _ in range(5):
         step()
     timer = AF.KernelTimer()
@@ -108,7 +114,7 @@ def run(name, cfg, steps=20):
         step()
     torch.cuda.synchronize()
     eager = (time.perf_counter() - t) / steps * 1e3
-    gstep = T.TrainStep(model, opt, x, ops, y, w, use_graph=True)
+    gstep = T.TrainStep(model, opt, x, ops, y, w, use_graph=True, criterion=crit)
     for _ in range(3):
         gstep()
     torch.cuda.synchronize()
@@ -117,8 +123,56 @@ def run(name, cfg, steps=20):
         gstep()
     torch.cuda.synchronize()
     graph = (time.perf_counter() - t) / steps * 1e3
-    return dict(config=name, n=n, nnz_low=int(low.nnz), f_in=f_in, eager_ms=round(eager, 3), graph_ms=round(graph, 3),
-                kernel_us=kern)
+    res = dict(config=name, n=n, nnz_low=int(low.nnz), f_in=f_in, eager_ms=round(eager, 3), graph_ms=round(graph, 3),
+               kernel_us=kern)
+    if crit == "bce":
+        res.update(rocauc_epoch(model, gstep, x, ops, y, [torch.from_numpy(i).to(DEV) for i in splits], steps))
+    return res
+
+
+def _midrank_auc(y, s):
+    """ROC-AUC with ties at one half from two searchsorted calls (= sklearn.metrics.roc_auc_score on binary labels)."""
+    neg = np.sort(s[y == 0])
+    pos = s[y == 1]
+    u2 = np.searchsorted(neg, pos, "left").sum() + np.searchsorted(neg, pos, "right").sum()
+    return u2 / (2.0 * len(pos) * len(neg))
+
+
+def rocauc_epoch(model, gstep, x, ops, y, idx, steps):
+    """ms per epoch = captured step + captured EvalStep(metric="rocauc", criterion="bce") with its one host read; and the same
+    epoch with the AUC formed as data_utils.eval_rocauc does: eval-mode forward, softmax, three .cpu() copies, roc_auc_score."""
+    ev = T.EvalStep(model, x, ops, y, idx, loss_set=1, use_graph=True, metric="rocauc", criterion="bce")
+    try:
+        from sklearn.metrics import roc_auc_score as auc_fn
+    except ImportError:
+        auc_fn = _midrank_auc
+
+    def ours():
+        gstep()
+        return ev()[1]
+
+    def reference_way():
+        gstep()
+        with torch.no_grad():
+            model.eval()
+            out = model(x, ops, None, None)
+            vals = [auc_fn(y[i].cpu().numpy(), torch.softmax(out[i], dim=-1)[:, 1].cpu().numpy()) for i in idx]
+            model.train()
+        return vals
+
+    timed = {}
+    for key, fn in (("epoch_ms", ours), ("epoch_reference_auc_ms", reference_way), ("eval_ms", ev)):
+        for _ in range(3):
+            last = fn()
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for _ in range(steps):
+            last = fn()
+        torch.cuda.synchronize()
+        timed[key] = round((time.perf_counter() - t) / steps * 1e3, 3)
+        if key != "eval_ms":
+            timed[key.replace("_ms", "_auc")] = [round(float(v), 6) for v in last]
+    return timed
 
 
 if __name__ == "__main__":
