@@ -10,5 +10,8 @@ from .models import GCN  # noqa: F401
 from .graph import CsrGraph, FilterOperators, SparseFeatures, operators_for  # noqa: F401
 from .optim import FusedAdam, FusedAdamW  # noqa: F401
 from . import tuning  # noqa: F401
+from . import homophily  # noqa: F401
+from .homophily import HomophilyCensus  # noqa: F401
 
-__all__ = ["GraphConvolution", "MLP", "GCN", "CsrGraph", "FilterOperators", "SparseFeatures", "operators_for", "FusedAdam", "FusedAdamW"]
+__all__ = ["GraphConvolution", "MLP", "GCN", "CsrGraph", "FilterOperators", "SparseFeatures", "operators_for", "FusedAdam", "FusedAdamW", "homophily",
+           "HomophilyCensus"]

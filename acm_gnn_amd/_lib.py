@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "acm_small_step_workspace_bytes", "acm_small_step", "acm_conv_head_fwd", "acm_conv_aggw_fwd", "acm_conv_aggw_bwd_workspace_bytes", "acm_conv_aggw_bwd",
     "acm_eval_metrics_workspace_bytes", "acm_eval_metrics",
     "acm_bce_loss_workspace_bytes", "acm_bce_loss", "acm_rocauc_scores", "acm_rocauc_workspace_bytes", "acm_rocauc",
+    "acm_homophily_workspace_bytes", "acm_homophily_census", "acm_class_means_workspace_bytes", "acm_class_means", "acm_class_score",
 )
 
 
@@ -295,6 +296,11 @@ def _declare(lib):
     lib.acm_rocauc_scores.argtypes = [i64, i32, vp, i64, vp, vp]
     lib.acm_rocauc_workspace_bytes.argtypes = [i64, i32, C.POINTER(sz)]
     lib.acm_rocauc.argtypes = [i64, vp, vp, vp, vp, i64, i32, vp, vp, vp, sz, vp]
+    lib.acm_homophily_workspace_bytes.argtypes = [i64, i64, i32, C.POINTER(sz)]
+    lib.acm_homophily_census.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp, sz, vp]
+    lib.acm_class_means_workspace_bytes.argtypes = [i64, i32, i32, C.POINTER(sz)]
+    lib.acm_class_means.argtypes = [i64, i32, i32, vp, i64, vp, vp, i64, vp, vp, sz, vp]
+    lib.acm_class_score.argtypes = [i64, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp]
     lib.acm_reduce_flush.argtypes = [vp, vp]
     lib.acm_conv_fwd_tail_workspace_bytes.argtypes = [i64, i32, i32, C.POINTER(sz)]
     lib.acm_conv_fwd_tail.argtypes = [vp, C.POINTER(ConvFwd), C.POINTER(Loss), C.POINTER(ConvBwdLocal), vp, sz, vp, sz, vp]

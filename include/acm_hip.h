@@ -1043,6 +1043,65 @@ int acm_small_step_workspace_bytes(const acm_csr_t* a_low, const acm_csr_t* x, c
 int acm_small_step(const acm_csr_t* a_low, const acm_csr_t* x, const acm_csr_t* x_t, const acm_small_step_t* p,
                    acm_stream_t stream);
 
+/* ------------------------------------- homophily measures on the device (added under ABI 29) --
+ * synthetic-experiments/homophily.py without its dense n x n matrices (label @ label.T at :16, A.nonzero() at :31 / :44 /
+ * :97, (A X)(A X)^T at :115-117).  ONE RULE for the four label measures:
+ *   A        the stored pattern of a CSR operator: values are ignored, every stored entry counts once.
+ *   labels   int64, one per COLUMN of the operator; row i's own label is labels[row_offset + i] (so a row slice made by
+ *            acm_csr_slice_rows can be censused on its own, and the integer outputs of the slices add up to the whole).
+ *            A negative label, or one >= n_classes, means "unlabeled" and never becomes an index.
+ *   An entry (i, j) COUNTS iff j != row_offset + i, y_i is labeled and y_j is labeled.
+ * counts[C*C + 2C + 2] (int64; exact on any device, in any execution order):
+ *   M[a][b]      counted entries from class a to class b                         (homophily.py:63-87, the matrix before :86)
+ *   cls[a]       labeled rows of class a                                          (:101-103)
+ *   iso[a]       labeled rows of class a with NO stored off-diagonal entry at all, whatever the neighbours' labels -- the
+ *                diagonal the reference adds with A + diag(sum(A, 1) == 0)          (:95-96)
+ *   n_labeled, n_deg = rows with row_deg > 0
+ * row_same[i], row_deg[i] (int32, optional): for a labeled row the counted entries with y_j == y_i, and all counted
+ *   entries; 0 for an unlabeled row                                               (:56-59)
+ * node_sum (float64) = sum over rows with row_deg > 0 of row_same / row_deg, added in a fixed order: the same bits on every
+ *   run.  The caller finishes in float64:
+ *     edge   = trace(M) / sum(M)                                                  (:8-19)
+ *     node   = node_sum / n_deg                                                   (:40-60)
+ *     compat = M / rowsum(M)                                                      (:22-37, :63-87)
+ *     class  = sum_k max(H_kk - cls_k / n_labeled, 0) / (C - 1), H = (M + diag(iso)) row-normalised, NaN terms skipped
+ *                                                                                 (:90-111)
+ * On fully labeled graphs these are the reference's values; class homophily also on graphs with unlabeled nodes.  The
+ * reference's node_homophily_edge_idx has no notion of an unlabeled node (it compares the raw labels, so two nodes
+ * labelled -1 "match"); here an unlabeled endpoint removes the entry from both the numerator and the degree.
+ * Three stream-ordered launches (byte labels + zeroing, the walk over the handle's work items, the row pass with its
+ * fixed-order float64 sum); nothing is allocated, nothing waits for the host, the sequence can be captured.
+ * 2 <= n_classes <= 64.  Workspace: acm_homophily_workspace_bytes(n_rows, n_cols, n_classes), 8-byte aligned, no
+ * initialisation needed.
+ *
+ * Aggregation homophily (homophily.py:114-124; its `modified` argument is not read there):  with Z = A X already formed
+ * (acm_spmm*),
+ *   acm_class_means   mu_k = mean of Z_u over y_u = k, class_count[k] (int64).  Since the mean is linear,
+ *                     Z_v . mu_k = mean(inner_prod[v, labels == k]) (:122-123) and nothing n x n is formed.  fp32 sums
+ *                     inside a tile of rows in row order, float64 across tiles in tile order, no float atomics: the same
+ *                     bits on every run.  mu of a class without a member is 0.  Any n_features.
+ *   acm_class_score   W[v][k] = Z_v . mu_k on the fp32 matrix pipe, the FIRST arg-max over the classes that have a member
+ *                     (torch.argmax, :124), row_hit[v] = [arg-max == y_v] (optional, one byte per row; 0 for an unlabeled
+ *                     row), counts[2] = {hits, scored rows}.  The result is hits / scored.  n_features <= 256; for wider Z
+ *                     form W = Z mu^T with acm_gemm and call this with z := W, mu := the C x C identity.
+ * Two deviations, both where the reference has no defined answer: unlabeled rows enter no mean and are not scored (the
+ * reference takes arg-max of a one-hot row, which labels an all-zero row as class 0); a class without a member is never
+ * chosen (the reference's mean over an empty selection is NaN).
+ * Errors: ACM_EINVAL null pointer, ACM_ESHAPE n_classes < 2 or a leading dimension below n_features, ACM_EUNSUPPORTED
+ * n_classes > 64 or acm_class_score with n_features > 256, ACM_ENOMEM short workspace.
+ */
+int acm_homophily_workspace_bytes(int64_t n_rows, int64_t n_cols, int n_classes, size_t* bytes);
+int acm_homophily_census(const acm_csr_t* a, const int64_t* labels, int64_t row_offset, int n_classes,
+                         int64_t* counts, double* node_sum, int32_t* row_same, int32_t* row_deg,
+                         void* workspace, size_t workspace_bytes, acm_stream_t stream);
+int acm_class_means_workspace_bytes(int64_t n_rows, int n_features, int n_classes, size_t* bytes);
+int acm_class_means(int64_t n_rows, int n_features, int n_classes, const float* z, int64_t ld_z,
+                    const int64_t* labels, float* mu, int64_t ld_mu, int64_t* class_count,
+                    void* workspace, size_t workspace_bytes, acm_stream_t stream);
+int acm_class_score(int64_t n_rows, int n_features, int n_classes, const float* z, int64_t ld_z,
+                    const float* mu, int64_t ld_mu, const int64_t* class_count, const int64_t* labels,
+                    uint8_t* row_hit, int64_t* counts, acm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
