@@ -12,6 +12,7 @@ from .optim import FusedAdam, FusedAdamW  # noqa: F401
 from . import tuning  # noqa: F401
 from . import homophily  # noqa: F401
 from .homophily import HomophilyCensus  # noqa: F401
+from . import synthetic  # noqa: F401
 
 __all__ = ["GraphConvolution", "MLP", "GCN", "CsrGraph", "FilterOperators", "SparseFeatures", "operators_for", "FusedAdam", "FusedAdamW", "homophily",
-           "HomophilyCensus"]
+           "HomophilyCensus", "synthetic"]

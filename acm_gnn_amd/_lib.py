@@ -31,6 +31,8 @@ EXPORTED_SYMBOLS = (
     "acm_eval_metrics_workspace_bytes", "acm_eval_metrics",
     "acm_bce_loss_workspace_bytes", "acm_bce_loss", "acm_rocauc_scores", "acm_rocauc_workspace_bytes", "acm_rocauc",
     "acm_homophily_workspace_bytes", "acm_homophily_census", "acm_class_means_workspace_bytes", "acm_class_means", "acm_class_score",
+    "acm_synth_regular", "acm_synth_uniform", "acm_synth_random_plan", "acm_synth_draw", "acm_synth_select_workspace_bytes", "acm_synth_select",
+    "acm_synth_inter_count", "acm_synth_emit",
 )
 
 
@@ -301,6 +303,15 @@ def _declare(lib):
     lib.acm_class_means_workspace_bytes.argtypes = [i64, i32, i32, C.POINTER(sz)]
     lib.acm_class_means.argtypes = [i64, i32, i32, vp, i64, vp, vp, i64, vp, vp, sz, vp]
     lib.acm_class_score.argtypes = [i64, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp]
+    u64 = C.c_uint64
+    lib.acm_synth_regular.argtypes = [i32, i64, i64, i64, u64, u64, i64, i64, vp, vp]
+    lib.acm_synth_uniform.argtypes = [i64, i64, u64, u64, i64, vp, i64, vp]
+    lib.acm_synth_random_plan.argtypes = [i32, i64, i64, C.c_double, C.POINTER(C.c_int64)]
+    lib.acm_synth_draw.argtypes = [i32, i64, i64, i32, i32, u64, u64, i64, vp, vp]
+    lib.acm_synth_select_workspace_bytes.argtypes = [i32, i64, C.POINTER(sz)]
+    lib.acm_synth_select.argtypes = [i32, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, sz, vp]
+    lib.acm_synth_inter_count.argtypes = [i32, i32, C.c_double, vp, vp, vp]
+    lib.acm_synth_emit.argtypes = [i32, i32, i64, i32, i32, vp, vp, i64, vp, vp, vp]
     lib.acm_reduce_flush.argtypes = [vp, vp]
     lib.acm_conv_fwd_tail_workspace_bytes.argtypes = [i64, i32, i32, C.POINTER(sz)]
     lib.acm_conv_fwd_tail.argtypes = [vp, C.POINTER(ConvFwd), C.POINTER(Loss), C.POINTER(ConvBwdLocal), vp, sz, vp, sz, vp]

@@ -1102,6 +1102,86 @@ int acm_class_score(int64_t n_rows, int n_features, int n_classes, const float* 
                     const float* mu, int64_t ld_mu, const int64_t* class_count, const int64_t* labels,
                     uint8_t* row_hit, int64_t* counts, acm_stream_t stream);
 
+/* ------------------------------------- synthetic graphs and features (added under ABI 29) --
+ * synthetic-experiments/graph_generation.py (`regular`, `random`) and feature_generation.py (`random` base) without their
+ * dense n x n matrices and Python loops, with the block size read as nodes_per_class.  n = C * npc nodes, node i has label
+ * i / npc, 2 <= C <= 64, n < 2^31.  The output is a PURE FUNCTION of the arguments: nothing depends on the grid, the block
+ * size, the launch order or the order in which atomics arrive, so a graph is reproducible from (seed, graph_index), a row
+ * range regenerates exactly its rows, and a numpy restatement reproduces every bit (tests/synthetic_ref.py).
+ *
+ * SAMPLING CONTRACT.  Every random word is a Philox4x32-7 word (acm_common.h: acm_philox7; oracle/philox.py:
+ * philox7_words(seed, step, tag, rows, blocks)) with key = seed and counter = (row field, block | tag << 16, graph_index lo,
+ * graph_index hi), i.e. step = graph_index.  A call yields words 0..3.  The streams:
+ *   tag 0x5301  regular, intra-class   row field = node j, block = s >> 2, word s & 3 for Floyd step s
+ *   tag 0x5302  regular, inter-class   the same
+ *   tag 0x5303  ACM_SYNTH_PAIR         row field = t >> 1, block = class, draw t: v_t = w[2p] << 32 | w[2p + 1], p = t & 1
+ *   tag 0x5304  ACM_SYNTH_RECT         the same
+ *   tag 0x5306  ACM_SYNTH_RANGE        the same (block = the caller's stream number, e.g. the class of a feature row choice)
+ *   tag 0x5305  uniform features       row field = row, block = f >> 2, word f & 3 for column f
+ * Two primitives:
+ *   k DISTINCT OF [0, m) FOR ONE ROW -- Floyd's algorithm: for s = 0 .. k-1, t = m - k + s, r = (word_s * (t + 1)) >> 32;
+ *     take r if it has not been chosen yet, else t.  Every k-subset is equally likely up to the bias of the multiply-high
+ *     draw: r deviates from uniform on [0, t] by at most (t + 1) / 2^32 per step.
+ *   THE FIRST M DISTINCT KEYS OF A STREAM -- draw t = 0, 1, .. gives v_t (64 bits); slot = mulhi64(v_t, R) in [0, R); the
+ *     slot decodes to a key or to "invalid" (INT64_MAX):
+ *       ACM_SYNTH_PAIR   R = a * a, (x, y) = (slot / a, slot % a), invalid if x == y, key = min * a + max
+ *       ACM_SYNTH_RECT   R = a * b, key = slot (row slot / b, column slot % b)
+ *       ACM_SYNTH_RANGE  R = a * b, key = slot
+ *     The result is the set of the first M distinct valid keys in draw order -- a uniformly random M-subset of the keys
+ *     (bias of a slot <= R / 2^64) -- delivered in draw order.  It does not depend on the stream length T as long as the
+ *     first T draws hold M distinct keys: a longer stream has the same first T draws.  acm_synth_draw writes the keys of T
+ *     draws; the caller sorts them STABLY with their draw numbers (any stable sort; the package uses torch.sort);
+ *     acm_synth_select marks the first occurrence of every valid key, ranks the marks in draw order (a three-phase scan over
+ *     4096-draw chunks) and writes key `rank` to out[segment * out_cap + rank] for rank < min(m[segment], out_cap); m is
+ *     read from DEVICE memory.  found[segment] = entries written.  status |= ACM_SYNTH_SHORT if the stream held fewer than
+ *     m distinct keys (the caller retries with a longer stream), |= ACM_SYNTH_OVER if m > out_cap; nothing is written out
+ *     of range in either case.  No kernel waits for another block; there is no retry loop on the device.
+ *
+ * acm_synth_regular (graph_generation.py:21-58): row j of class c takes degree_intra distinct nodes of its own block other
+ *   than j (Floyd over npc - 1 ids; ids >= j - c npc are shifted by one) and degree_inter distinct nodes outside the block
+ *   (Floyd over n - npc ids; ids >= c npc are shifted by npc).  Rows are DIRECTED, as in the reference.  One launch writes
+ *   indices[(j - row_begin) * d + e], d = degree_intra + degree_inter, for rows [row_begin, row_end), every row sorted
+ *   ascending; indptr is j * d.  One wave per row; the row is sorted in LDS and stored as d contiguous ids.
+ *   d <= ACM_SYNTH_MAX_DEGREE (256), else ACM_EUNSUPPORTED; degree_intra > npc - 1 or degree_inter > n - npc: ACM_ESHAPE.
+ * random (graph_generation.py:65-134), S = degree_intra * npc (even, else ACM_ESHAPE from acm_synth_random_plan):
+ *   every class block receives exactly S / 2 undirected edges, the first S / 2 distinct keys of its ACM_SYNTH_PAIR stream
+ *   (a = npc, block = class).  Then for i = 0 .. C-2 in order class i receives m_i = max(0, rint(T - e_i) + 1) edges toward
+ *   the later classes, the first m_i distinct keys of its ACM_SYNTH_RECT stream (a = npc, b = (C-1-i) npc, block = i): key
+ *   = x * b + y is the edge (i npc + x, (i+1) npc + y).  T = S (1 - h) / h in float64 (the caller's), rint = round half to
+ *   even = Python's round, e_i = the entries earlier classes placed into block i = sum_{k<i} block_counts[k][i]
+ *   (acm_synth_inter_count, read on the device: no host synchronisation inside the chain).  acm_synth_emit writes both
+ *   directions of every selected edge as row * n + col into edge_keys[2 * (segment * cap + r) + {0, 1}] (INT64_MAX beyond
+ *   found[segment]) and adds the C x C int64 block_counts with integer atomics (PAIR: stores the diagonal cell).  Sorting
+ *   the edge keys gives the CSR.  acm_synth_random_plan checks the shape on the host and answers plan[0] = S / 2, plan[1] =
+ *   rint(T) + 1 >= every m_i.
+ * acm_synth_uniform (feature_generation.py:33): out[r][f] = (word >> 8) * 2^-24, fp32 in [0, 1), rows row_begin + r.
+ *   n_features <= ACM_SYNTH_MAX_FEATURES.
+ * Errors: ACM_EINVAL null pointer / unknown kind / misaligned workspace, ACM_ESHAPE sizes, ACM_EUNSUPPORTED more than 64
+ * classes or a cap above, ACM_ENOMEM short workspace (acm_synth_select_workspace_bytes; 16-byte aligned, no initialisation).
+ */
+#define ACM_SYNTH_PAIR 0
+#define ACM_SYNTH_RECT 1
+#define ACM_SYNTH_RANGE 2
+#define ACM_SYNTH_SHORT 1
+#define ACM_SYNTH_OVER 2
+#define ACM_SYNTH_MAX_DEGREE 256
+#define ACM_SYNTH_MAX_FEATURES 262144
+int acm_synth_regular(int n_classes, int64_t nodes_per_class, int64_t degree_intra, int64_t degree_inter, uint64_t seed,
+                      uint64_t graph_index, int64_t row_begin, int64_t row_end, int32_t* indices, acm_stream_t stream);
+int acm_synth_uniform(int64_t n_rows, int64_t n_features, uint64_t seed, uint64_t graph_index, int64_t row_begin, float* out,
+                      int64_t ld_out, acm_stream_t stream);
+int acm_synth_random_plan(int n_classes, int64_t nodes_per_class, int64_t degree_intra, double edge_homo, int64_t* plan);
+int acm_synth_draw(int kind, int64_t a, int64_t b, int block_first, int n_segments, uint64_t seed, uint64_t graph_index,
+                   int64_t n_draws, int64_t* keys, acm_stream_t stream);
+int acm_synth_select_workspace_bytes(int n_segments, int64_t n_draws, size_t* bytes);
+int acm_synth_select(int n_segments, int64_t n_draws, const int64_t* keys, const int64_t* sorted_keys, const int64_t* perm,
+                     const int64_t* m, int64_t out_cap, int64_t* out, int64_t* found, int32_t* status, void* workspace,
+                     size_t workspace_bytes, acm_stream_t stream);
+int acm_synth_inter_count(int n_classes, int cls, double t_edges, const int64_t* block_counts, int64_t* m_out,
+                          acm_stream_t stream);
+int acm_synth_emit(int kind, int n_classes, int64_t nodes_per_class, int class_first, int n_segments, const int64_t* selected,
+                   const int64_t* found, int64_t cap, int64_t* edge_keys, int64_t* block_counts, acm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
