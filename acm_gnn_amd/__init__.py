@@ -13,6 +13,7 @@ from . import tuning  # noqa: F401
 from . import homophily  # noqa: F401
 from .homophily import HomophilyCensus  # noqa: F401
 from . import synthetic  # noqa: F401
+from . import baselines  # noqa: F401
 
 __all__ = ["GraphConvolution", "MLP", "GCN", "CsrGraph", "FilterOperators", "SparseFeatures", "operators_for", "FusedAdam", "FusedAdamW", "homophily",
-           "HomophilyCensus", "synthetic"]
+           "HomophilyCensus", "synthetic", "baselines"]

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "acm_homophily_workspace_bytes", "acm_homophily_census", "acm_class_means_workspace_bytes", "acm_class_means", "acm_class_score",
     "acm_synth_regular", "acm_synth_uniform", "acm_synth_random_plan", "acm_synth_draw", "acm_synth_select_workspace_bytes", "acm_synth_select",
     "acm_synth_inter_count", "acm_synth_emit",
+    "acm_gcn_fwd", "acm_gcn_bwd_workspace_bytes", "acm_gcn_bwd", "acm_gemm_act",
 )
 
 
@@ -198,6 +199,19 @@ class SpmmOpts(C.Structure):
                 ("sub_scale", C.c_void_p), ("relu", C.c_int32), ("g_bf16", C.c_int32)]
 
 
+class GcnFwd(C.Structure):
+    _fields_ = [("width", C.c_int32), ("relu", C.c_int32), ("z", C.c_void_p), ("ld_z", C.c_int64), ("y", C.c_void_p), ("ld_y", C.c_int64),
+                ("row_scale", C.c_void_p), ("drop", Dropout), ("f_next", C.c_int32), ("reserved", C.c_int32),
+                ("w_next", C.c_void_p), ("ld_w_next", C.c_int64), ("z_next", C.c_void_p), ("ld_z_next", C.c_int64)]
+
+
+class GcnBwd(C.Structure):
+    _fields_ = [("width", C.c_int32), ("hidden", C.c_int32), ("dy", C.c_void_p), ("ld_dy", C.c_int64), ("h", C.c_void_p), ("ld_h", C.c_int64),
+                ("w2", C.c_void_p), ("ld_w2", C.c_int64), ("keep_scale", C.c_float), ("relu", C.c_int32),
+                ("g", C.c_void_p), ("ld_g", C.c_int64), ("dz", C.c_void_p), ("ld_dz", C.c_int64),
+                ("d_w2", C.c_void_p), ("ld_dw2", C.c_int64), ("defer", C.c_void_p)]
+
+
 class AdamTensor(C.Structure):
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
                 ("step", C.c_void_p), ("numel", C.c_int64)]
@@ -312,6 +326,10 @@ def _declare(lib):
     lib.acm_synth_select.argtypes = [i32, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, sz, vp]
     lib.acm_synth_inter_count.argtypes = [i32, i32, C.c_double, vp, vp, vp]
     lib.acm_synth_emit.argtypes = [i32, i32, i64, i32, i32, vp, vp, i64, vp, vp, vp]
+    lib.acm_gcn_fwd.argtypes = [vp, C.POINTER(GcnFwd), vp, sz, vp]
+    lib.acm_gcn_bwd_workspace_bytes.argtypes = [vp, i32, i32, C.POINTER(sz)]
+    lib.acm_gcn_bwd.argtypes = [vp, C.POINTER(GcnBwd), vp, sz, vp]
+    lib.acm_gemm_act.argtypes = [i64, i64, i64, vp, i64, vp, i64, i32, vp, vp, i64, vp, sz, vp]
     lib.acm_reduce_flush.argtypes = [vp, vp]
     lib.acm_conv_fwd_tail_workspace_bytes.argtypes = [i64, i32, i32, C.POINTER(sz)]
     lib.acm_conv_fwd_tail.argtypes = [vp, C.POINTER(ConvFwd), C.POINTER(Loss), C.POINTER(ConvBwdLocal), vp, sz, vp, sz, vp]

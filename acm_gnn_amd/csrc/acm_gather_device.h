@@ -860,6 +860,12 @@ inline GatherForm choose_gather_form(int64_t n_rows, int64_t n_cols, int64_t nnz
     return f;
 }
 
+// An epilogue that declares `static constexpr bool kWideOnly = true` is never launched with F <= 8: launch_gather then does not
+// instantiate the narrow gather and its fix-ups for it (the caller answers narrow shapes another way).  Compile-time only:
+// epilogues without the member are what they were.
+template <class E, class = void> struct epi_wide_only : std::false_type {};
+template <class E> struct epi_wide_only<E, std::void_t<decltype(E::kWideOnly)>> : std::bool_constant<E::kWideOnly> {};
+
 // (spmm_narrow_pair3_kernel exists for three gathered channels only; other NG never reach the call)
 template <int NG, class Epi>
 void launch_pair3(int grid, hipStream_t st, const CsrView& v, const float* table, const typename Epi::Args& ea, float* partial) {
@@ -901,15 +907,21 @@ int launch_gather(const acm_csr* a, const GatherSrc& g, int F, const typename Ep
                                                acm_tuning().wide_form, Epi::kFusedHead);
     // the forms for F > 8: a wave per work item, the same arguments
     auto wide = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((int)((a->n_items + 3) / 4)), dim3(256), 0, st, v, g, F, ea, partial); };
+    if constexpr (epi_wide_only<Epi>::value)
+        ACM_REQUIRE(F > 8, ACM_EUNSUPPORTED, "%s: this epilogue exists for more than 8 columns (got %d)", who, F);
     switch (form.kind) {
     case GatherForm::PAIR3: {
+      if constexpr (!epi_wide_only<Epi>::value) {
         int grid = (int)((a->n_items + 15) / 16);
         if (grid > NARROW_MAX_BLOCKS) grid = NARROW_MAX_BLOCKS;
         launch_pair3<NG, Epi>(grid, st, v, g.p[0], ea, partial);
         ACM_CHECK_HIP(hipGetLastError());
         return finish_window_rows<NG, Epi>(a, v, F, ea, partial, st);
+      }
+      break;
     }
     case GatherForm::NARROW:
+      if constexpr (!epi_wide_only<Epi>::value)
         acm_with_fp(F, [&](auto fp) {
             auto launch = [&](auto gs) {
                 constexpr int FP = decltype(fp)::value, GS = decltype(gs)::value, gpb = 256 / GS;
@@ -933,9 +945,11 @@ int launch_gather(const acm_csr* a, const GatherSrc& g, int F, const typename Ep
     }
     ACM_CHECK_HIP(hipGetLastError());
     // sixteen lanes per item: the narrow gather has finished the long rows itself, except the rows of several windows
-    if (F <= 8 && narrow_finishes_long_rows(a)) return finish_window_rows<NG, Epi>(a, v, F, ea, partial, st);
+    if constexpr (!epi_wide_only<Epi>::value)
+        if (F <= 8 && narrow_finishes_long_rows(a)) return finish_window_rows<NG, Epi>(a, v, F, ea, partial, st);
     if (defer_fixup || !a->n_long) return ACM_OK;      // (deferred: the caller's next kernel adds the partial slots of the long rows)
     if (F <= 8) {
+      if constexpr (!epi_wide_only<Epi>::value)
         acm_with_fp(F, [&](auto fp) {
             hipLaunchKernelGGL((spmm_fixup_narrow_kernel<decltype(fp)::value, NG, Epi>), dim3((int)((a->n_long + 15) / 16)), dim3(256), 0,
                                st, v, F, ea, partial);

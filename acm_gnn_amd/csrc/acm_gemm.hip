@@ -314,6 +314,27 @@ extern "C" int acm_linear_fwd(int64_t n_rows, int64_t f_in, int64_t f_out, const
                      stream, bias, drop);
 }
 
+// Y = dropout(relu?(X W)), W stored [f_in, f_out]: the same epilogue on the untransposed product (the baselines' first layer on
+// the cached P = A_low^k X, baseline_models/layers.py:120-123 + models.py:32).  Without a dropout: acm_gemm, whichever form it takes.
+extern "C" int acm_gemm_act(int64_t n_rows, int64_t f_in, int64_t f_out, const float* X, int64_t ldx, const float* W, int64_t ldw,
+                            int relu, const acm_dropout_t* drop, float* Y, int64_t ldy, void* workspace, size_t workspace_bytes,
+                            acm_stream_t stream) {
+    ACM_REQUIRE(X && W && Y, ACM_EINVAL, "acm_gemm_act: NULL argument");
+    ACM_REQUIRE(n_rows >= 0 && f_in > 0 && f_out > 0 && n_rows < INT32_MAX && f_in < INT32_MAX && f_out < INT32_MAX, ACM_ESHAPE,
+                "acm_gemm_act: n_rows %lld f_in %lld f_out %lld", (long long)n_rows, (long long)f_in, (long long)f_out);
+    ACM_REQUIRE(ldx >= f_in && ldw >= f_out && ldy >= f_out, ACM_ESHAPE, "acm_gemm_act: leading dimension too small (ldx %lld ldw %lld ldy %lld)",
+                (long long)ldx, (long long)ldw, (long long)ldy);
+    ACM_REQUIRE(!drop || drop->p == 0.f || (drop->p > 0.f && drop->p < 1.f && drop->step), ACM_EINVAL, "acm_gemm_act: bad dropout spec");
+    {
+        size_t need = 0;
+        acm_gemm_workspace_bytes(0, 0, n_rows, f_out, f_in, &need);
+        ACM_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), ACM_ENOMEM, "acm_gemm_act: workspace %zu B < required %zu B",
+                    workspace_bytes, need);
+    }
+    return gemm_core(0, 0, n_rows, f_out, f_in, X, ldx, W, ldw, Y, ldy, 0, 0, 0, nullptr, 0, relu, workspace, workspace_bytes, stream,
+                     nullptr, (drop && drop->p > 0.f) ? drop : nullptr);
+}
+
 extern "C" int acm_gemm_blocks(int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A,
                                int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t c_col_block,
                                int64_t c_block_stride, int relu, void* workspace, size_t workspace_bytes,

@@ -271,6 +271,45 @@ def random_features(n, n_features=1433, seed=0, graph_index=0, device="cuda", ro
     return out
 
 
+# ---- the study's split -------------------------------------------------------------------------------------------------------
+_SPLIT_STREAM = 1 << 63          # graph_index of the split keys: the feature draws of the same seed use graph_index < 2^63
+
+
+def disassortative_splits(labels, n_classes, seed, split_index=0):
+    """The study's 60 / 20 / 20 split (synthetic-experiments/utils.py:440-461, ``random_disassortative_splits``) ->
+    (train, val, test): three sorted int64 index tensors on the labels' device.
+
+    Per class ``int(round(0.6 * n / C))`` training nodes (Python's ``round``, as there; a class with fewer members gives all of
+    them); of the shuffled rest ``int(round(0.2 * n))`` validation nodes, the remainder is the test set.  Nodes whose label
+    lies outside [0, C) are in no set, as in the reference.  The shuffles are a pure function of ``(seed, split_index)``: node i
+    carries the two uniform keys ``acm_synth_uniform`` draws for row i under graph_index = 2^63 + split_index, a class's members
+    (and the rest) are ordered by key with ``torch.sort`` (stable: equal keys keep the ascending node order).  The reference
+    shuffles with ``torch.randperm`` on the unseeded global generator; that stream is NOT reproduced -- the split has its
+    sizes and its per-class shares, not its members."""
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 1 or labels.dtype != torch.int64:
+        raise ValueError("disassortative_splits: labels must be an int64 [n] tensor")
+    _require_cuda(labels, "labels")
+    c, n = int(n_classes), labels.numel()
+    if c < 1 or not 0 <= int(seed) < 2 ** 64 or not 0 <= int(split_index) < _SPLIT_STREAM:
+        raise ValueError(f"disassortative_splits: {c} classes, seed {seed}, split_index {split_index}")
+    per_class, n_val = int(round(0.6 * (n / c))), int(round(0.2 * n))
+    dev = labels.device
+    keys = random_features(n, 2, seed=seed, graph_index=_SPLIT_STREAM + int(split_index), device=dev) if n else labels.new_zeros(0, 2, dtype=torch.float32)
+    nodes = ((labels >= 0) & (labels < c)).nonzero().view(-1)
+    lab = labels.index_select(0, nodes)
+    by_key = torch.sort(keys[:, 0].index_select(0, nodes), stable=True).indices
+    by_class = torch.sort(lab.index_select(0, by_key), stable=True).indices
+    order = by_key.index_select(0, by_class)                             # grouped by class, shuffled inside
+    lab_sorted = lab.index_select(0, order)
+    first = torch.cumsum(torch.bincount(lab, minlength=c), 0) - torch.bincount(lab, minlength=c)
+    rank = torch.arange(order.numel(), device=dev) - first.index_select(0, lab_sorted)
+    shuffled = nodes.index_select(0, order)
+    train = shuffled[rank < per_class]
+    rest = shuffled[rank >= per_class]
+    rest = rest.index_select(0, torch.sort(keys[:, 1].index_select(0, rest), stable=True).indices)
+    return tuple(torch.sort(t).values for t in (train, rest[:n_val], rest[n_val:]))
+
+
 def base_feature_rows(base_y, n_classes=5, nodes_per_class=400, seed=0, graph_index=0):
     """int64 ``[n_classes * nodes_per_class]`` rows of a base data set (feature_generation.py:36-54): class j draws from base
     class ``j % n_base``; with more than ``nodes_per_class`` members it takes that many without replacement, otherwise every

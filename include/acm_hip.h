@@ -1182,6 +1182,78 @@ int acm_synth_inter_count(int n_classes, int cls, double t_edges, const int64_t*
 int acm_synth_emit(int kind, int n_classes, int64_t nodes_per_class, int class_first, int n_segments, const int64_t* selected,
                    const int64_t* found, int64_t cap, int64_t* edge_keys, int64_t* block_counts, acm_stream_t stream);
 
+/* ------------------------------- one-channel graph layers: the GCN / SGC baselines (added under ABI 29) --
+ * The synthetic study's baselines (synthetic-experiments/baseline_models/layers.py:122-124, models.py:29-33):
+ *     gcn   A_low (dropout(relu(A_low (X W1))) W2)        sgc   A_low^k (X W)
+ * where the reference multiplies a dense N x N adj_low with torch.mm.  Here A_low is a CSR handle (explicit values, or the
+ * pattern P of the implicit form A_low = diag(row_scale) P) and both entry points are epilogues of the gather family: wide
+ * and narrow execution shapes, rows longer than `chunk` combined in slot order, the epilogue applied ONCE to the combined sum.
+ *
+ * acm_gcn_fwd    Y = drop(relu?(row_scale * (A Z)))  for Z [n_cols, width] of any width, the keep / drop decision of element
+ *                (row, col) regenerated from `drop` (acm_dropout_t: global row, column, tag, step; p = 0: none); optionally, in
+ *                the same launch, Z_next = Y W_next for f_next <= 8 columns (W_next [width, f_next], width <= 256) -- the
+ *                following layer's projection, taken while the row is in registers.  Replaces torch.mm(adj_low, .) +
+ *                F.relu + F.dropout (+ the next layer's torch.mm(input, self.weight_low)): layers.py:123, models.py:32-33.
+ *                Only the `width` (`f_next`) leading columns of a row of Y (Z_next) are written.  Without a post-op (no ReLU, p = 0,
+ *                f_next = 0) the call IS acm_spmm_ex with `row_scale`, at any width.  With one it takes width > 8: the narrow
+ *                gather has no scalar registers to spare for the post-op's parameters (ACM_EUNSUPPORTED; a narrow hidden layer
+ *                composes acm_spmm_ex + acm_bias_act + acm_gemm, as functional.gcn_fwd does).  Workspace:
+ *                acm_spmm_workspace_bytes(a, min(width, 256)).
+ * acm_gcn_bwd    dZ = A^T dY for a NARROW dY (width <= 8: the output layer), `a_t` being the handle of A^T (the pattern
+ *                itself for the symmetric implicit form, with dY scaled by row_scale at the source), and in its epilogue the
+ *                row-local backward of the layer below:
+ *                    G[r, :] = (dZ[r] W2^T) * keep_scale [H[r, :] > 0]      dW2 = H^T dZ
+ *                H = that layer's stored forward output, both masks read off it as acm_bias_act_bwd does (relu = 0 and
+ *                keep_scale > 1: dropped iff H == 0; neither: G = dZ W2^T).  Replaces the SpmmBackward / MmBackward /
+ *                ReluBackward / dropout-backward chain of the same lines -- acm_spmm + acm_gemm + acm_bias_act_bwd +
+ *                acm_gemm(transA) -- by one gather launch.  dW2 is summed from per-group slabs in a fixed order (no float
+ *                atomics; bit-identical from run to run) and honours `defer`.  dz (optional) receives dZ.  Wider dY:
+ *                ACM_EUNSUPPORTED -- the caller composes the four calls above; so is hidden > 256 (it bounds the slabs).  The
+ *                call's parameters travel in a device record at the head of the workspace, written by the launch that zeroes
+ *                the slabs.  Workspace: acm_gcn_bwd_workspace_bytes, 16-byte aligned, no initialisation.
+ * Errors: ACM_EINVAL NULL pointer / bad dropout spec, ACM_ESHAPE a leading dimension below its width, ACM_EUNSUPPORTED
+ * f_next > 8, f_next > 0 with width > 256, a post-op with width <= 8, acm_gcn_bwd with width > 8 or hidden > 256; ACM_ENOMEM short
+ * workspace.
+ */
+typedef struct {
+    int32_t width;                /* columns of Z and Y                                                            */
+    int32_t relu;
+    const float* z; int64_t ld_z; /* gathered operand [n_cols, width]                                              */
+    float* y; int64_t ld_y;       /* [n_rows, width]                                                               */
+    const float* row_scale;       /* n_rows: the implicit form's diag(row_scale) (NULL = 1)                        */
+    acm_dropout_t drop;
+    int32_t f_next;               /* 0: no fused projection                                                        */
+    int32_t reserved;
+    const float* w_next; int64_t ld_w_next;   /* [width, f_next]                                                   */
+    float* z_next; int64_t ld_z_next;         /* [n_rows, f_next]                                                  */
+} acm_gcn_fwd_t;
+
+typedef struct {
+    int32_t width;                /* columns of dY / dZ / W2 (<= 8)                                                */
+    int32_t hidden;               /* columns of H / G, rows of W2                                                  */
+    const float* dy; int64_t ld_dy;   /* [n_cols of a_t, width]                                                    */
+    const float* h; int64_t ld_h;     /* [n_rows, hidden]                                                          */
+    const float* w2; int64_t ld_w2;   /* [hidden, width]                                                           */
+    float keep_scale;             /* 1 / (1 - p) of the dropout behind H (1: none)                                 */
+    int32_t relu;
+    float* g; int64_t ld_g;       /* [n_rows, hidden]                                                              */
+    float* dz; int64_t ld_dz;     /* optional [n_rows, width]                                                      */
+    float* d_w2; int64_t ld_dw2;  /* [hidden, width]; undefined until the flush when deferred                      */
+    acm_reduce_list_t* defer;
+} acm_gcn_bwd_t;
+
+int acm_gcn_fwd(const acm_csr_t* a, const acm_gcn_fwd_t* p, void* workspace, size_t workspace_bytes, acm_stream_t stream);
+int acm_gcn_bwd_workspace_bytes(const acm_csr_t* a_t, int width, int hidden, size_t* bytes);
+int acm_gcn_bwd(const acm_csr_t* a_t, const acm_gcn_bwd_t* p, void* workspace, size_t workspace_bytes, acm_stream_t stream);
+
+/* Y = dropout(relu?(X W)) with W stored [f_in, f_out] (pitch ldw) -- acm_linear_fwd's epilogue (ReLU, then the counter-based
+ * mask of `drop`; NULL / p = 0: none) on the plain product: the first layer of the baselines on the cached P = A_low^k X and
+ * the hidden layer of `mlp` (layers.py:120, models.py:32), without a second pass over the [n_rows, f_out] result.  Without a
+ * dropout it is acm_gemm.  Workspace: acm_gemm_workspace_bytes(0, 0, n_rows, f_out, f_in). */
+int acm_gemm_act(int64_t n_rows, int64_t f_in, int64_t f_out, const float* X, int64_t ldx, const float* W, int64_t ldw,
+                 int relu, const acm_dropout_t* drop, float* Y, int64_t ldy, void* workspace, size_t workspace_bytes,
+                 acm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
