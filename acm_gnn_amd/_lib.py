@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = (
     "acm_synth_regular", "acm_synth_uniform", "acm_synth_random_plan", "acm_synth_draw", "acm_synth_select_workspace_bytes", "acm_synth_select",
     "acm_synth_inter_count", "acm_synth_emit",
     "acm_gcn_fwd", "acm_gcn_bwd_workspace_bytes", "acm_gcn_bwd", "acm_gemm_act",
+    "acm_select_step", "acm_copy_if",
 )
 
 
@@ -223,6 +224,16 @@ class AdamConfig(C.Structure):
                 ("arrive", C.c_void_p), ("pending", C.c_void_p)]
 
 
+class Select(C.Structure):
+    _fields_ = [("rule", C.c_int32), ("early_stopping", C.c_int32), ("epochs", C.c_int32), ("reserved", C.c_int32),
+                ("result", C.c_void_p), ("result_f64", C.c_void_p), ("train_loss", C.c_void_p),
+                ("ctrl", C.c_void_p), ("best", C.c_void_p), ("history", C.c_void_p)]
+
+
+class CopyTensor(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("numel", C.c_int64)]
+
+
 SMALL_ROLES = 17
 # acm_small_step_t.t[layer][role]: role indices (include/acm_hip.h: ACM_SR_*)
 SR_W_LOW, SR_W_HIGH, SR_W_MLP, SR_V_LOW, SR_V_HIGH, SR_V_MLP, SR_V_STRUC = range(7)
@@ -330,6 +341,8 @@ def _declare(lib):
     lib.acm_gcn_bwd_workspace_bytes.argtypes = [vp, i32, i32, C.POINTER(sz)]
     lib.acm_gcn_bwd.argtypes = [vp, C.POINTER(GcnBwd), vp, sz, vp]
     lib.acm_gemm_act.argtypes = [i64, i64, i64, vp, i64, vp, i64, i32, vp, vp, i64, vp, sz, vp]
+    lib.acm_select_step.argtypes = [C.POINTER(Select), vp]
+    lib.acm_copy_if.argtypes = [i32, vp, vp, vp]
     lib.acm_reduce_flush.argtypes = [vp, vp]
     lib.acm_conv_fwd_tail_workspace_bytes.argtypes = [i64, i32, i32, C.POINTER(sz)]
     lib.acm_conv_fwd_tail.argtypes = [vp, C.POINTER(ConvFwd), C.POINTER(Loss), C.POINTER(ConvBwdLocal), vp, sz, vp, sz, vp]

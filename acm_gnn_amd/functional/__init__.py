@@ -8,7 +8,7 @@ missing library is an error.
 Beside the three device seams (``_device_ctx`` / ``_require_cuda`` / ``_stream``: ``_launch`` looks them up HERE at call
 time, so that a test double replaces them in one place) and ``_gather_rows`` (the routes call it through this namespace, where
 a test counts halo exchanges), this file only re-exports what the project and the tests reach as ``functional.NAME``: ``_launch`` (the launch block, its
-timing and argument marshalling), ``_context`` (step- and call-scoped state), ``ops`` (single-kernel operators), ``linear`` (the
+timing and argument marshalling), ``_context`` (step- and call-scoped state), ``ops`` (single-kernel operators), ``select`` (a run's selection state on the device), ``linear`` (the
 residual branch), ``gcn`` (the one-channel layers of the study's baselines), ``conv`` (the layer's entry point) over ``_conv_shared``, ``conv_agg`` and ``conv_literal`` (its four routes).
 """
 from .. import _lib, tuning  # noqa: F401
@@ -19,6 +19,7 @@ from ._context import (CallContext, DeferredReductions, InputPipeline, Tape, Tap
 from .ops import (DropoutState, _drop_spec, agg_pad_width, bce_loss, bce_loss_and_grad, cast_bf16, dropout, eval_metrics,  # noqa: F401
                   eval_metrics_buffers, eval_rocauc, gemm, gemm_drop_supported, gemm_split, masked_bce, masked_nll, mm, nll_loss_and_grad, proj3, proj_bwd,
                   proj_bwd_supported, proj_fwd, rocauc_buffers, spmm, spmm_v)
+from .select import SelectionState, copy_if  # noqa: F401
 from .linear import residual_add_linear, residual_add_supported, residual_linear  # noqa: F401
 from .gcn import aggregate, dense_act, gcn_bwd, gcn_fwd, gcn_two_layer, gemm_act, low_t_product, mask_bwd, sparse_mm  # noqa: F401
 from ._conv_shared import AcmConfig, _flat_views, _gather_rows, _ptr_array  # noqa: F401

@@ -10,7 +10,8 @@ cannot run.
                      whole step is one graph launch instead of ~60 kernel launches).
 * ``evaluate``       eval-mode forward + accuracy (or, ``metric="rocauc"``, ROC-AUC) on index sets, on device (the
                      reference pulls the predictions to the host three times per epoch, data_utils.py:117-118, 132-135).
-* ``fit``            the two model-selection rules of the reference.
+* ``fit``            the two model-selection rules of the reference; with ``sync_every`` / ``keep_best`` the selection state
+                     stays on the device across epochs (functional.SelectionState) and the selected model is returned.
 """
 import torch
 import torch.nn.functional as F
@@ -503,10 +504,17 @@ class EvalStep:
     per-set results ROC-AUCs (AF.eval_rocauc: scores, one ``torch.sort``, exact integer statistic; NaN where a set lacks a
     class) and ``criterion="bce"`` makes the loss on ``loss_set`` the BCE-with-logits against the one-hot labels (acm_bce_loss,
     loss only).  Still one synchronising copy per pass (float64 then: the AUCs are exact quotients of integers).  The sort is
-    global, so row-sharded operators are refused with ``metric="rocauc"``."""
+    global, so row-sharded operators are refused with ``metric="rocauc"``.
+
+    ``selector`` (a functional.SelectionState) with ``train_loss`` (the training step's fp32 loss scalar; the attribute may
+    be re-pointed between un-captured passes): every pass ends by folding its epoch into the selector's device-resident
+    state -- acm_select_step on (train_loss, result), then, if the selector keeps snapshots, acm_copy_if.  Needs three index
+    sets (train, validation, test) and ``loss_set=1``.  A captured pass holds these launches at the tail of its graph (one
+    linear chain: an epoch stays two graph replays); the selector is reset after the capture's warm-up passes, so
+    :meth:`refresh` is refused once the run has begun."""
 
     def __init__(self, model, x, adj, labels, index_sets, adj_high=None, adj_un=None, loss_set=1, use_graph=False,
-                 small_step=None, fused_metrics=True, metric="acc", criterion="nll"):
+                 small_step=None, fused_metrics=True, metric="acc", criterion="nll", selector=None, train_loss=None):
         self.model, self.x, self.adj, self.adj_high, self.adj_un = model, x, adj, adj_high, adj_un
         self.metric, self.criterion = _checked(metric, METRICS, "metric"), _checked(criterion, CRITERIA, "criterion")
         if self.metric == "rocauc" and _is_sharded(adj):
@@ -517,6 +525,9 @@ class EvalStep:
         self.labels = labels
         self._labels_safe = labels.clamp_min(0)             # -1 = unlabeled (never in an index set)
         self.w, self.loss_set = _set_weights(index_sets, labels), int(loss_set)
+        self.selector, self.train_loss = selector, train_loss
+        if selector is not None and (self.w.shape[0] != 3 or self.loss_set != 1):
+            raise ValueError("EvalStep(selector=...): needs the three index sets (train, validation, test) and loss_set=1")
         # small graphs: the evaluation forward as one call (small.SmallPlan without an optimizer)
         self.small, self.small_refused = None, "not requested"
         if small_step is not False:
@@ -537,13 +548,28 @@ class EvalStep:
             self._capture()
 
     def refresh(self):
-        """Re-capture after an in-place edit of the features (or of anything else the captured pass read once)."""
+        """Re-capture after an in-place edit of the features (or of anything else the captured pass read once).
+
+        With a ``selector`` only before the run's first epoch: the capture's warm-up passes fold epochs into the selector's
+        state and the capture resets it, which in the middle of a run would wipe the epoch counter, the best key and the stop
+        flag.  Refused (RuntimeError) once an epoch has been folded in; asking costs one small synchronising read."""
         if self._use_graph:
+            if self.selector is not None and self.selector.poll()[0] > 0:
+                raise RuntimeError("EvalStep.refresh(): the selector has folded epochs in; a re-capture would reset its state "
+                                   "in the middle of the run")
             self.graph = None
             self._capture()
 
     @torch.no_grad()
     def _run(self):
+        out, res = self._pass()
+        if self.selector is not None:
+            if self.train_loss is None:
+                raise ValueError("EvalStep(selector=...): train_loss is not set")
+            self.selector.launch(self.train_loss, res)
+        return out, res
+
+    def _pass(self):
         self.model.eval()
         if self.small is not None:
             out = self.small.run()                       # three launches, one C-ABI call (acm_small_step, train = 0)
@@ -596,6 +622,9 @@ class EvalStep:
                 self._run()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        if self.selector is not None:
+            self.selector.reset()               # the warm-up passes folded two epochs in
+            torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, **_capture_mode()):
             self.out, self.res = self._run()
@@ -625,8 +654,20 @@ class EvalStep:
 
 def fit(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, rule="max_val_acc",
         early_stopping=0, adj_high=None, adj_un=None, use_graph=False, fused_dropout=None, pipeline_input=None,
-        criterion="nll", metric="acc"):
+        criterion="nll", metric="acc", sync_every=1, keep_best=False):
     """Train and return (selected test accuracy, per-epoch history).
+
+    ``sync_every`` / ``keep_best``: with the defaults (1, False) every epoch ends in a synchronising read of its numbers and
+    the selection is done here on the host.  Otherwise the selection state lives on the device (functional.SelectionState:
+    acm_select_step at the tail of the captured evaluation pass), up to ``sync_every`` epochs are enqueued back to back, and
+    only then the host looks whether the run has stopped -- never more than ``epochs`` in total.  Needs ``use_graph=True``;
+    row-sharded operators are refused.  Both returned values equal those of ``sync_every=1`` from the same initial state
+    exactly (the window mean is the plain left-to-right float64 sum, ``sum()`` up to CPython 3.11; see DESIGN.md section 4a
+    for the compensated ``sum()`` of later interpreters).  After an early stop the MODEL has taken up to ``sync_every - 1`` more optimizer steps than with
+    ``sync_every=1``: the device state is frozen from the stopping epoch on, so the results do not see them.
+    ``keep_best=True`` snapshots the parameters on the device whenever an epoch is selected (acm_copy_if, predicated on the
+    selection: no cost in the other epochs, no extra read) and restores the selected epoch's parameters into ``model`` in
+    place before returning -- the values after that epoch's optimizer step, which its evaluation pass saw.
 
     ``criterion`` / ``metric``: the reference's two protocols (ACM-Geometric/train.py:86-92): "nll" + "acc", or -- genius,
     twitch-e, yelp-chi, ``--rocauc`` -- "bce" + "rocauc".  With "rocauc" the three per-set numbers of a history row and the
@@ -644,6 +685,9 @@ def fit(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, 
                            exceeds the mean of the last `early_stopping` epochs
                            (ACM-Pytorch/train.py:129-139)
     """
+    if _resident_loop(sync_every, keep_best):
+        return _fit_resident(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, rule, early_stopping,
+                             adj_high, adj_un, use_graph, fused_dropout, pipeline_input, criterion, metric, sync_every, keep_best)
     w = row_weights(train_idx, x.shape[0], device=x.device)
     _checked(metric, METRICS, "metric")
     step = TrainStep(model, optimizer, x, adj, labels, w, adj_high, adj_un, use_graph=use_graph,
@@ -673,8 +717,110 @@ def fit(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, 
     return selected, history
 
 
+def _resident_loop(sync_every, keep_best):
+    """Whether fit / fit_concurrent keep the selection state on the device (anything but the defaults)."""
+    if int(sync_every) != sync_every or sync_every < 1:
+        raise ValueError(f"sync_every must be an integer >= 1, not {sync_every!r}")
+    return sync_every != 1 or bool(keep_best)
+
+
+class _ResidentRun:
+    """One run of ``fit`` with its selection state on the device: the captured training step, the captured evaluation pass
+    whose graph ends in the selection launches, and how many epochs have been enqueued."""
+
+    def __init__(self, model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, rule, early_stopping, adj_high,
+                 adj_un, fused_dropout, pipeline_input, criterion, metric, keep_best):
+        _checked(metric, METRICS, "metric")
+        if _is_sharded(adj):
+            raise NotImplementedError("fit(sync_every > 1 or keep_best=True): the selection state lives on ONE device; "
+                                      "row-sharded operators are not supported")
+        self.model, self.epochs, self.enqueued = model, int(epochs), 0
+        self.select = AF.SelectionState(rule, early_stopping, epochs, labels.device,
+                                        params=list(model.parameters()) if keep_best else None)
+        w = row_weights(train_idx, x.shape[0], device=labels.device)
+        self.step = TrainStep(model, optimizer, x, adj, labels, w, adj_high, adj_un, use_graph=True, fused_dropout=fused_dropout,
+                              pipeline_input=pipeline_input, criterion=criterion)
+        self.ev = EvalStep(model, x, adj, labels, (train_idx, val_idx, test_idx), adj_high, adj_un, loss_set=1, use_graph=True,
+                           metric=metric, criterion=criterion, selector=self.select, train_loss=self.step.loss)
+
+    def enqueue(self, sync_every):
+        """Up to ``sync_every`` epochs (step replay + evaluation replay) on the current stream, within the budget."""
+        for _ in range(min(int(sync_every), self.epochs - self.enqueued)):
+            self.ev.train_loss = self.step()
+            self.ev.launch()
+            self.enqueued += 1
+
+    def finished(self):
+        """Waits for what was enqueued; True once the run has stopped or used its budget up."""
+        _, stopped = self.select.poll()
+        return stopped or self.enqueued >= self.epochs
+
+    def result(self):
+        selected, history, _ = self.select.result()
+        if self.select.snapshot is not None:
+            self.select.restore(self.model)
+        return selected, history
+
+
+def _fit_resident(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, rule, early_stopping, adj_high, adj_un,
+                  use_graph, fused_dropout, pipeline_input, criterion, metric, sync_every, keep_best):
+    if not use_graph:
+        raise ValueError("fit(sync_every > 1 or keep_best=True) needs use_graph=True: the selection launches ride the captured "
+                         "evaluation pass")
+    if int(epochs) < 1:
+        return 0.0, []
+    run = _ResidentRun(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, rule, early_stopping, adj_high,
+                       adj_un, fused_dropout, pipeline_input, criterion, metric, keep_best)
+    while True:
+        run.enqueue(sync_every)
+        if run.finished():
+            return run.result()
+
+
+def _fit_concurrent_resident(runs, x, adj, labels, epochs, rule, early_stopping, adj_high, adj_un, streams, fused_dropout,
+                             criterion, metric, sync_every, keep_best):
+    """fit_concurrent with every run's selection state on the device."""
+    if int(epochs) < 1:
+        return [(0.0, []) for _ in runs]
+    results = [None] * len(runs)
+    on_gpu = labels.is_cuda and torch.cuda.is_available()
+    if not on_gpu or streams <= 1:
+        for k, (model, opt, tr, va, te) in enumerate(runs):
+            results[k] = fit(model, opt, x, adj, labels, tr, va, te, epochs, rule=rule, early_stopping=early_stopping,
+                             adj_high=adj_high, adj_un=adj_un, use_graph=True, fused_dropout=fused_dropout, criterion=criterion,
+                             metric=metric, sync_every=sync_every, keep_best=keep_best)
+        return results
+    pending = list(range(len(runs)))
+    slots = [None] * min(int(streams), len(runs))
+    pool = [torch.cuda.Stream() for _ in slots]
+
+    def start(k, stream):
+        model, opt, tr, va, te = runs[k]
+        with torch.cuda.stream(stream):
+            run = _ResidentRun(model, opt, x, adj, labels, tr, va, te, epochs, rule, early_stopping, adj_high, adj_un,
+                               fused_dropout, None, criterion, metric, keep_best)
+        stream.synchronize()
+        return k, run
+
+    while pending or any(sl is not None for sl in slots):
+        for i in range(len(slots)):
+            if slots[i] is None and pending:
+                slots[i] = start(pending.pop(0), pool[i])
+        live = [(i, sl) for i, sl in enumerate(slots) if sl is not None]
+        for i, (k, run) in live:                         # every live run's epochs are enqueued before any state is awaited
+            with torch.cuda.stream(pool[i]):
+                run.enqueue(sync_every)
+        for i, (k, run) in live:
+            with torch.cuda.stream(pool[i]):
+                if run.finished():
+                    results[k] = run.result()
+                    pool[i].synchronize()                # keep_best: the restore was enqueued HERE, the caller reads elsewhere
+                    slots[i] = None
+    return results
+
+
 def fit_concurrent(runs, x, adj, labels, epochs, rule="min_val_loss", early_stopping=0, adj_high=None, adj_un=None, streams=2,
-                   fused_dropout=None, criterion="nll", metric="acc"):
+                   fused_dropout=None, criterion="nll", metric="acc", sync_every=1, keep_best=False):
     """Several independent training runs on the same graph -- the reference's ten fixed splits, which ACM-Pytorch/train.py:49-139
     trains one after the other, each with a fresh model -- ``streams`` at a time, every run on its own stream with its own
     captured step and evaluation pass: the launches of one run fill the gaps of the other (a small-graph step is a chain of
@@ -684,7 +830,16 @@ def fit_concurrent(runs, x, adj, labels, epochs, rule="min_val_loss", early_stop
     ``runs``: a list of ``(model, optimizer, train_idx, val_idx, test_idx)``; every run is exactly ``fit(..., use_graph=True)``
     of its model (same selection rules, same history rows, bit-identical results: the runs share no state but the read-only
     graph and features; ``criterion`` / ``metric`` as in ``fit``).  Returns ``[(selected test accuracy, history)]`` in the order of ``runs``.  Without a GPU stream to
-    overlap on (CPU test double) the runs are trained one after the other."""
+    overlap on (CPU test double) the runs are trained one after the other.
+
+    ``sync_every`` / ``keep_best`` as in ``fit``: a live run enqueues ``sync_every`` epochs on its stream before any run's
+    state is looked at, and a run's stream is drained before its result is handed back (with ``keep_best`` the models hold the
+    selected parameters on return, whatever stream the caller uses).  These need the captured graphs: the one-after-the-other
+    path (``streams <= 1``) then calls ``fit(use_graph=True)``, so unlike the default path it does not run without a GPU
+    (the CPU tests stub the capture)."""
+    if _resident_loop(sync_every, keep_best):
+        return _fit_concurrent_resident(runs, x, adj, labels, epochs, rule, early_stopping, adj_high, adj_un, streams,
+                                        fused_dropout, criterion, metric, sync_every, keep_best)
     results = [None] * len(runs)
     on_gpu = labels.is_cuda and torch.cuda.is_available()
     if not on_gpu or streams <= 1:

@@ -1254,6 +1254,58 @@ int acm_gemm_act(int64_t n_rows, int64_t f_in, int64_t f_out, const float* X, in
                  int relu, const acm_dropout_t* drop, float* Y, int64_t ldy, void* workspace, size_t workspace_bytes,
                  acm_stream_t stream);
 
+/* ------------------------------------------------ model selection and early stopping on the device --
+ * The per-epoch bookkeeping of the reference's training loops (ACM-Geometric/train.py:139-140 + logger.py:17-48: test metric
+ * at the best validation metric; ACM-Pytorch/train.py:129-139: test metric at the lowest validation loss, stop when the
+ * validation loss exceeds the mean of the last `early_stopping` epochs) as ONE launch of one 64-lane block behind the
+ * evaluation pass, so that a training loop need not read the epoch's numbers back before it enqueues the next epoch.
+ *
+ * acm_select_step folds one epoch into the run's device-resident state:
+ *   ctrl     int32[8]: [0] epoch (rows written so far), [1] stopped, [2] best_epoch (-1: nothing selected yet),
+ *            [3] improved (1 iff THIS call selected its epoch); [4..7] reserved, zero
+ *   best     double[2]: [0] best_key, [1] selected (the test metric at the best epoch; 0.0 until one is selected)
+ *   history  double[epochs, 5]: (train_loss, m_tr, m_va, m_te, val_loss) per epoch
+ * A run starts from ctrl = {0, 0, -1, 0, ...}, best = {0, 0}.  One call:
+ *   1. stopped != 0 or epoch >= epochs: improved = 0 and nothing else is written (the state is frozen).
+ *   2. history[epoch] = (train_loss[0], result[0..3]) widened to double.
+ *   3. key = m_va (rule 0) or -val_loss (rule 1).  A NaN key is passed over; otherwise, if best_epoch < 0 or key > best_key
+ *      (strictly: the first of equal keys stays; -inf is a valid first selection): best_key = key, selected = m_te,
+ *      best_epoch = epoch, improved = 1.  In every other case improved = 0.
+ *   4. rule 1, early_stopping > 0, epoch > early_stopping: stopped = 1 if val_loss > mean, the float64 sum of
+ *      history[epoch - es .. epoch - 1][4] in ascending epoch order divided by es (equal is not greater; a NaN on either
+ *      side does not stop).  The stopping epoch keeps its row and its selection.
+ *   5. epoch += 1.
+ * Every value equals what the host loop computes from float(loss) / result.tolist(), bit for bit.
+ * `result` (fp32, acm_eval_metrics' [m_tr, m_va, m_te, val_loss]) or `result_f64` (the same four in float64): exactly one.
+ */
+typedef struct {
+    int32_t rule;                  /* 0 = maximise the validation metric, 1 = minimise the validation loss */
+    int32_t early_stopping;        /* window length; 0 = never stop                                        */
+    int32_t epochs;                /* epoch budget = rows of `history`                                     */
+    int32_t reserved;
+    const float*  result;
+    const double* result_f64;
+    const float*  train_loss;      /* the training step's fp32 loss scalar */
+    int32_t* ctrl;
+    double*  best;
+    double*  history;
+} acm_select_t;
+
+int acm_select_step(const acm_select_t* p, acm_stream_t stream);
+
+/* dst[i] = src[i] (as bits: NaN payloads and -0.0 survive) for every tensor of the table if *flag != 0; nothing is read or
+ * written otherwise (`flag` is device memory, read once per block: acm_select_t.ctrl + 3 makes the copy "snapshot the
+ * parameters iff this epoch was selected").  `tensors` is a HOST array copied into the kernel arguments, 40 per launch, as
+ * acm_adam_step's: a captured call replays without touching host memory.  numel counts 32-bit elements, any value >= 0;
+ * src / dst need 4-byte alignment only (16-byte accesses where both allow) and must not overlap. */
+typedef struct {
+    const void* src;
+    void*       dst;
+    int64_t     numel;
+} acm_copy_tensor_t;
+
+int acm_copy_if(int32_t n_tensors, const acm_copy_tensor_t* tensors, const int32_t* flag, acm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
