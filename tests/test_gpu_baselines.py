@@ -10,6 +10,7 @@ import torch
 
 import baselines_ref as R
 import fake_lib
+import launch_forms as LF
 from conftest import GOLDEN, load_npz
 
 pytestmark = pytest.mark.gpu
@@ -27,14 +28,14 @@ def _close(got, ref, tol, what=""):
 
 
 # ---- operators of the kernel tests: computed once, never modified --------------------------------------------------------------
-def _make_operator(n, explicit, chunk=256):
+def _make_operator(n, explicit, chunk=256, density=None):
     """(CsrGraph, dense float64 matrix of what the handle multiplies by, row_scale or None).  n >= 300: node 0 is adjacent to
     every node (a row longer than ``chunk``: the split-row paths -- the fix-up launch at n = 1025, mean degree 8 and eight lanes
     per row; the in-LDS combine at n = 300, mean degree 20 and sixteen lanes; several windows of pieces at n = 2100 under
     chunk = 128); the pattern-only operators have an EMPTY row."""
     from acm_gnn_amd.graph import CsrGraph
     rng = np.random.RandomState(n + int(explicit))
-    dense = (rng.rand(n, n) < min(1.0, (6.0 if n in (63, 1025) else 20.0) / n)).astype(np.float64)
+    dense = (rng.rand(n, n) < (density or min(1.0, (6.0 if n in (63, 1025) else 20.0) / n))).astype(np.float64)
     if n >= 300:
         dense[0, :] = 1
         dense[:, 0] = 1
@@ -455,3 +456,183 @@ def test_end_to_end_fit_on_a_generated_graph():
     opt = FusedAdam(model.parameters(), lr=0.05, weight_decay=5e-4)
     acc, history = T.fit(model, opt, x, ops, g.labels, tr, va, te, epochs=30, rule="min_val_loss", early_stopping=200, use_graph=True)
     assert np.isfinite(acc) and len(history) == 30 and all(np.isfinite(row).all() for row in history)
+
+
+# ---- launch forms no small case reaches: exact integers against scipy.sparse in int64 -------------------------------------------
+# Unit-valued pattern operators and small integer operands: every product and every partial sum is an integer below 2^24, so
+# any summation order and any slab assignment give the same bits and the comparisons are torch.equal.
+EXACT = 2 ** 24
+
+
+def _pattern_operator(n, tune, density=None):
+    """(CsrGraph of a unit-valued pattern, the same pattern as a scipy int64 CSR matrix): the file's generator and its cache
+    at the default density, a private draw of the same generator otherwise."""
+    import scipy.sparse as sp
+    if density is None:
+        graph, dense, _ = _operator(n, False, tune)
+    else:
+        tune(chunk=256)
+        key = (n, False, density)
+        if key not in _OPERATORS:
+            _OPERATORS[key] = _make_operator(n, False, density=density)
+        graph, dense, _ = _OPERATORS[key]
+    return graph, sp.csr_matrix((dense != 0).astype(np.int64))
+
+
+def _sparse_pattern_operator(n, mean_degree, seed):
+    """The same kind of operator at a size where the generator's dense n x n draw no longer fits a quick test: a random
+    pattern of ``mean_degree`` entries per row, node 0 adjacent to every node, row n // 2 empty."""
+    import scipy.sparse as sp
+    from acm_gnn_amd.graph import CsrGraph
+    rng = np.random.RandomState(seed)
+    m = n * mean_degree
+    a = sp.coo_matrix((np.ones(m + 2 * n, np.int64),
+                       (np.concatenate([rng.randint(0, n, m), np.zeros(n, np.int64), np.arange(n)]),
+                        np.concatenate([rng.randint(0, n, m), np.arange(n), np.zeros(n, np.int64)]))), shape=(n, n)).tocsr()
+    a.data[:] = 1
+    a = a.tolil()
+    a[n // 2, :] = 0
+    a = a.tocsr()
+    a.eliminate_zeros()
+    a.sort_indices()
+    graph = CsrGraph.from_csr(torch.from_numpy(a.indptr.astype(np.int32)).to(DEV), torch.from_numpy(a.indices.astype(np.int32)).to(DEV),
+                              None, n, chunk=256)
+    return graph, a.astype(np.int64)
+
+
+def _nan_padded(a, pad=3):
+    """``a`` on the device as the leading columns of a NaN-filled wider buffer."""
+    wide = torch.full((a.shape[0], a.shape[1] + pad), float("nan"), device=DEV)
+    wide[:, :a.shape[1]] = torch.from_numpy(a).to(DEV)
+    return wide[:, :a.shape[1]]
+
+
+def _bwd_exact_case(pattern, hidden, width, seed):
+    """(dy, h, w2 as fp32 integers, dz int64) with every partial sum of dz, of dz W2^T and of H^T dz below 2^24."""
+    n = pattern.shape[0]
+    rng = np.random.RandomState(seed)
+    dy = rng.randint(-2, 3, (n, width)).astype(np.float32)
+    w2 = rng.randint(-2, 3, (hidden, width)).astype(np.float32)
+    h = (rng.randint(0, 4, (n, hidden)) * (rng.rand(n, hidden) < 0.6)).astype(np.float32)
+    assert (h == 0).mean() >= 0.30
+    dz = pattern @ dy.astype(np.int64)
+    abs_dz = pattern @ np.abs(dy).astype(np.int64)
+    assert abs_dz.max() < EXACT and 2 * (abs_dz @ np.abs(w2).astype(np.int64).T).max() < EXACT
+    assert (h.astype(np.int64).T @ abs_dz).max() < EXACT
+    return dy, h, w2, dz
+
+
+def _bwd_refs(dz, h, w2, relu, ks):
+    mask = (h > 0) if relu else (h != 0)
+    g = (dz @ w2.astype(np.int64).T) * mask * int(ks)
+    dw = h.astype(np.int64).T @ dz
+    return (torch.from_numpy(t.astype(np.float32)) for t in (g, dw, dz))
+
+
+BWD_MODES = ((True, 2.0), (True, 1.0), (False, 2.0))
+
+
+def _check_bwd_exact(graph, pattern, hidden, width, seed, lanes):
+    from acm_gnn_amd import functional as AF
+    avg = pattern.nnz / pattern.shape[0]
+    want_lanes = 8 if avg <= LF.T["NARROW_8_LANES_UP_TO"] else (16 if avg <= LF.T["NARROW_16_LANES_UP_TO"] else 32)
+    if want_lanes == 16 and width >= 5:                       # (5..8 columns never take sixteen lanes)
+        want_lanes = 32
+    assert want_lanes == lanes, (avg, width)                  # the case runs the form it is listed for (acm_gcn.hip: gcn_bwd_plan)
+    dy, h, w2, dz_ref = _bwd_exact_case(pattern, hidden, width, seed)
+    dyd, hd, w2d = _nan_padded(dy), _nan_padded(h), _nan_padded(w2)
+    for relu, ks in BWD_MODES:
+        g_ref, dw_ref, dz_want = _bwd_refs(dz_ref, h, w2, relu, ks)
+        g, dw, dz = AF.gcn_bwd(graph, dyd, hd, w2d, keep_scale=ks, relu=relu, want_dz=True)
+        what = (pattern.shape[0], hidden, width, relu, ks)
+        assert torch.equal(dz.cpu(), dz_want), what
+        assert torch.equal(g.cpu(), g_ref), what
+        assert torch.equal(dw.cpu(), dw_ref), what
+
+
+@pytest.mark.parametrize("n,density,lanes", LF.GCN_BWD_OPERATORS)
+def test_gcn_bwd_is_exact_on_integers(n, density, lanes, tune):
+    """Every (hidden, width) whose dW2 slabs end in a partial group of 32, hidden below the lanes of a group and hidden at the
+    limit, with 8, 16 and 32 lanes per work item; inputs are column slices of NaN-filled buffers."""
+    graph, pattern = _pattern_operator(n, tune, density)
+    if n >= 300:
+        assert graph.n_long_rows >= 1
+    for hidden, width in LF.GCN_BWD_SHAPES:
+        _check_bwd_exact(graph, pattern, hidden, width, 7 * n + hidden + width, 32 if lanes == 16 and width >= 5 else lanes)
+
+
+@pytest.mark.parametrize("n,mean_degree,hidden,width,lanes", LF.GCN_BWD_HELD_GRIDS)
+def test_gcn_bwd_is_exact_with_the_gather_grid_at_its_cap(n, mean_degree, hidden, width, lanes, tune):
+    """More work items than GCN_BWD_MAX_BLOCKS blocks of groups: a group adds several items into its slab."""
+    if n <= 2500:
+        graph, pattern = _pattern_operator(n, tune)
+    else:
+        tune(chunk=256)
+        graph, pattern = _sparse_pattern_operator(n, mean_degree, n)
+    assert graph.n_long_rows >= 1 and graph.n_items > LF.GCN_BWD_MAX_BLOCKS * (256 // lanes)
+    _check_bwd_exact(graph, pattern, hidden, width, n, lanes)
+
+
+@pytest.mark.parametrize("n,hidden,width", [(63, 33, 3), (300, 9, 5)])
+def test_gcn_bwd_leaves_the_padding_of_its_outputs_alone(n, hidden, width, tune):
+    """One raw acm_gcn_bwd call with ld_g, ld_dw2 and ld_dz above the widths: the guard columns survive, the rest is exact."""
+    import ctypes as C
+    from acm_gnn_amd import _lib
+    from acm_gnn_amd.functional._launch import _vp, _workspace_sized, launch
+    graph, pattern = _pattern_operator(n, tune)
+    dy, h, w2, dz_ref = _bwd_exact_case(pattern, hidden, width, n)
+    dyd, hd, w2d = _nan_padded(dy), _nan_padded(h), _nan_padded(w2)
+    guard = -77.0
+    g = torch.full((n, hidden + 2), guard, device=DEV)
+    dw = torch.full((hidden, width + 3), guard, device=DEV)
+    dz = torch.full((n, width + 1), guard, device=DEV)
+    ws, nbytes = _workspace_sized(torch.device(DEV), "acm_gcn_bwd_workspace_bytes", graph.handle, width, hidden)
+    p = _lib.GcnBwd()
+    p.width, p.hidden, p.keep_scale, p.relu = width, hidden, 2.0, 1
+    p.dy, p.ld_dy, p.h, p.ld_h, p.w2, p.ld_w2 = dyd.data_ptr(), dyd.stride(0), hd.data_ptr(), hd.stride(0), w2d.data_ptr(), w2d.stride(0)
+    p.g, p.ld_g, p.d_w2, p.ld_dw2, p.dz, p.ld_dz = g.data_ptr(), g.stride(0), dw.data_ptr(), dw.stride(0), dz.data_ptr(), dz.stride(0)
+    p.defer = None
+    launch("acm_gcn_bwd", None, torch.device(DEV), graph.handle, C.byref(p), _vp(ws), nbytes)
+    torch.cuda.synchronize()
+    g_ref, dw_ref, dz_want = _bwd_refs(dz_ref, h, w2, True, 2.0)
+    assert torch.equal(g[:, :hidden].cpu(), g_ref) and bool((g[:, hidden:] == guard).all())
+    assert torch.equal(dw[:, :width].cpu(), dw_ref) and bool((dw[:, width:] == guard).all())
+    assert torch.equal(dz[:, :width].cpu(), dz_want) and bool((dz[:, width:] == guard).all())
+
+
+@pytest.mark.parametrize("n", [63, 1025])
+def test_gcn_fwd_is_exact_on_integers(n, tune):
+    """The ridden projection at every width class up to 256 and the column-block splits beyond (128 + rest, 256 + rest): integer
+    z and W_next, keep factor exactly 2, the mask a function of the global column.  At n = 1025 the hub row takes the fix-up."""
+    from acm_gnn_amd import functional as AF
+    graph, pattern = _pattern_operator(n, tune)
+    if n == 1025:
+        assert graph.n_long_rows >= 1
+    state = AF.DropoutState(torch.device(DEV), seed=4321 + n)
+    state.step.fill_(5)
+    rng = np.random.RandomState(n)
+    cases = [(w, f) for w in LF.GCN_FWD_RIDDEN_WIDTHS for f in (1, 8)] + [(w, 0) for w in LF.GCN_FWD_SPLIT_WIDTHS]
+    for width, f_next in cases:
+        z = rng.randint(-2, 3, (n, width)).astype(np.float32)
+        az = pattern @ z.astype(np.int64)
+        assert (pattern @ np.abs(z).astype(np.int64)).max() < EXACT
+        factors = _host_factors(state, 0.5, 3, n, width)
+        assert set(np.unique(factors)) == {0.0, 2.0}
+        w_next = rng.randint(-2, 3, (width, f_next)).astype(np.float32) if f_next else None
+        zd = torch.from_numpy(z).to(DEV)
+        wn = _nan_padded(w_next, 1) if f_next else None
+        for relu, p in ((False, 0.0), (True, 0.0), (True, 0.5), (False, 0.5)):
+            ref = np.maximum(az, 0) if relu else az
+            if p:
+                ref = ref * factors.astype(np.int64)
+            buf = torch.full((n, width + 3), 7.0, device=DEV)
+            nbuf = torch.full((n, f_next + 2), 7.0, device=DEV) if f_next else None
+            y, zn = AF.gcn_fwd(graph, zd, relu=relu, drop=state.spec(p, 3) if p else None, w_next=wn, out=buf[:, :width],
+                               out_next=nbuf[:, :f_next] if f_next else None)
+            what = (n, width, f_next, relu, p)
+            assert torch.equal(y.cpu(), torch.from_numpy(ref.astype(np.float32))), what
+            assert bool((buf[:, width:] == 7.0).all()), what
+            if f_next:
+                assert (np.abs(ref) @ np.abs(w_next).astype(np.int64)).max() < EXACT
+                assert torch.equal(zn.cpu(), torch.from_numpy((ref @ w_next.astype(np.int64)).astype(np.float32))), what
+                assert bool((nbuf[:, f_next:] == 7.0).all()), what

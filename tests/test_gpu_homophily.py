@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import homophily_ref as R
+import launch_forms as LF
 from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -246,3 +247,192 @@ def test_a_class_without_a_member_is_never_chosen():
     assert counts.cpu().tolist() == [4, 4] and rows.cpu().tolist() == [1, 1, 1, 1]
     counts = H.class_score(z, neg, torch.tensor([2, 1, 2], device=DEV), y)
     assert counts.cpu().tolist() == [0, 4]
+
+
+# ---- launch forms no small case reaches: exact integers against int64 references ---------------------------------------------
+# Inputs are small integers held in fp32, so every product and partial sum is an integer below 2^24: any summation order, any
+# slab assignment and the MFMA give the same bits, and the comparisons below are ``==`` with no tolerance.
+EXACT = 2 ** 24
+
+
+def _score_case(n, c, f, seed):
+    """(z, mu, class_count, labels, want_hit, want_counts, ties) of one exact acm_class_score case.  About a quarter of the
+    classes is empty, class 0 among them, and class 0's mu row is the copy of a paired (often winning) row: unmasked it would be
+    the first maximum.  Rows of mu are copied at the distances 1 (within a lane), 4 (across the four lanes of a row), 16 and 32
+    (across MFMA tiles).  ``ties`` counts the labeled rows whose maximum is tied, in all and per kind."""
+    rng = np.random.default_rng(seed)
+    z = rng.integers(-2, 3, (n, f)).astype(np.float32)
+    mu = rng.integers(-2, 3, (c, f)).astype(np.float32)
+    count = rng.integers(1, 9, c).astype(np.int64)
+    count[rng.random(c) < 0.25] = 0
+    count[0] = 0
+    if not count[1:].any():
+        count[c - 1] = 3
+    free = count > 0
+    paired = 0
+    fits = {1: lambda k: k % 4 != 3, 4: lambda k: k % 16 < 12, 16: lambda k: True, 32: lambda k: True}
+    for turn in range(c):
+        d = (32, 16, 4, 1)[turn % 4]
+        for k in range(c - d):
+            if c >= 8 and free[k] and free[k + d] and fits[d](k) and paired < 0.6 * c:
+                mu[k + d] = mu[k]
+                free[k] = free[k + d] = False
+                if paired == 0:
+                    mu[0] = mu[k]                              # the empty class 0 doubles a paired row
+                paired += 2
+                break
+    w = z.astype(np.int64) @ mu.astype(np.int64).T
+    assert np.abs(z.astype(np.int64)).max(initial=0) * np.abs(mu.astype(np.int64)).max() * f < EXACT   # every partial sum
+    assert np.abs(w).max(initial=0) < EXACT
+    w[:, count == 0] = -EXACT
+    arg = w.argmax(1)                                          # the first maximum
+    y = arg.copy()
+    other = rng.random(n) < 0.4
+    y[other] = rng.integers(0, c, int(other.sum()))
+    top = w == w.max(1, keepdims=True)
+    later = np.array([np.flatnonzero(t)[-1] for t in top], np.int64) if n else arg
+    swap = rng.random(n) < 0.2
+    y[swap] = later[swap]                                      # a later tied class is a miss
+    idx = np.arange(n)
+    y[idx % 7 == 3] = -1
+    y[idx % 11 == 5] = c
+    y[idx % 13 == 6] = c + 3
+    labeled = (y >= 0) & (y < c)
+    hit = labeled & (arg == y)
+    a = arg
+    def also(d, ok):
+        j = np.minimum(a + d, c - 1)
+        return labeled & ok & (a + d < c) & top[idx, j]
+    ties = dict(any=int((labeled & (top.sum(1) > 1)).sum()), lane=int(also(1, a % 4 != 3).sum()),
+                row=int(also(4, a % 16 < 12).sum()), tile=int((also(16, True) | also(32, True)).sum()),
+                labeled=int(labeled.sum()))
+    return z, mu, count, y.astype(np.int64), hit, [int(hit.sum()), int(labeled.sum())], ties
+
+
+def _z_layout(z, kind):
+    """``z`` on the device as a view of a NaN-filled buffer: contiguous, row pitch F + 1, row pitch F + 4, or a base one float
+    behind a 16-byte boundary with a pitch that is a multiple of 4."""
+    n, f = z.shape
+    if kind == "contiguous":
+        return _t(z)
+    ld, off = {"pitch_f1": (f + 1, 0), "pitch_f4_nan": (f + 4, 0), "base_off_4B": ((f + 3) // 4 * 4 + 4, 1)}[kind]
+    buf = torch.full((off + n * ld + 3,), float("nan"), device=DEV)
+    view = buf[off:off + n * ld].view(n, ld)[:, :f]
+    view.copy_(_t(z))
+    assert view.data_ptr() % 16 == 4 * off and view.stride(0) == ld
+    return view
+
+
+def _run_score(n, c, f, layout="contiguous", ties_required=None):
+    from acm_gnn_amd import homophily as H
+    z, mu, count, y, want_hit, want_counts, ties = _score_case(n, c, f, 1000 * c + f + n)
+    if f >= 16 if ties_required is None else ties_required:
+        assert ties["any"] >= 0.10 * ties["labeled"], ties     # conditions on the reference, not on the kernel
+        assert ties["lane"] > 0 and ties["row"] > 0 and ties["tile"] > 0, ties
+    zt = _z_layout(z, layout)
+    counts, rows = H.class_score(zt, _t(mu), _t(count), _t(y), return_rows=True)
+    torch.cuda.synchronize()
+    assert counts.cpu().tolist() == want_counts
+    assert np.array_equal(rows.cpu().numpy().astype(bool), want_hit)
+
+
+@pytest.mark.parametrize("c,f", LF.SCORE_SHAPES)
+def test_class_score_is_exact_on_integers(c, f):
+    _run_score(1000, c, f)
+
+
+@pytest.mark.parametrize("n", LF.SCORE_SMALL_N)
+@pytest.mark.parametrize("c,f", [(17, 15), (49, 64)])
+def test_class_score_is_exact_at_partial_row_groups(c, f, n):
+    _run_score(n, c, f, ties_required=False)                   # (too few rows to demand every kind of tie)
+
+
+@pytest.mark.parametrize("layout", ["contiguous", "pitch_f1", "pitch_f4_nan", "base_off_4B"])
+@pytest.mark.parametrize("c,f", [(16, 4), (33, 16), (49, 64)])
+def test_class_score_is_exact_on_padded_and_misaligned_rows(c, f, layout):
+    _run_score(1000, c, f, layout)
+
+
+@pytest.mark.parametrize("c,f,n", LF.SCORE_SECOND_TRIPS)
+def test_class_score_is_exact_past_its_grid_cap(c, f, n):
+    _run_score(n, c, f)
+
+
+@pytest.mark.parametrize("n,f,c,pad", LF.MEANS_CASES)
+def test_class_means_are_exact_on_integers(n, f, c, pad):
+    from acm_gnn_amd import homophily as H
+    rng = np.random.default_rng(n + f)
+    y = rng.integers(-1, c, n).astype(np.int64)                # some rows unlabeled
+    y[:c] = np.arange(c)
+    y[-3:] = [c - 1, 0, 1]                                     # the last tile holds members
+    z = rng.integers(-3, 4, (n, f)).astype(np.float32)
+    want = np.zeros((c, f), np.float32)
+    want_count = np.bincount(y[y >= 0], minlength=c)
+    for k in range(c):
+        s = z[y == k].astype(np.int64).sum(0)
+        assert np.abs(z[y == k].astype(np.int64)).sum(0).max() < EXACT
+        want[k] = (s.astype(np.float64) / want_count[k]).astype(np.float32)
+    wide = torch.full((n, f + pad), float("nan"), device=DEV)
+    wide[:, :f] = _t(z)
+    mu, count = H.class_means(wide[:, :f], _t(y), c)
+    torch.cuda.synchronize()
+    assert count.cpu().numpy().tolist() == want_count.tolist()
+    assert np.array_equal(mu.cpu().numpy().view(np.int32), want.view(np.int32))
+
+
+def _symmetric_random_graph(n, c, seed, pairs, unlabeled=0, hub=0):
+    """(directed edge list of a symmetric graph with ``pairs`` random pairs and ``hub`` extra neighbours of node 0, labels)"""
+    rng = np.random.default_rng(seed)
+    src, dst = rng.integers(0, n, pairs), rng.integers(0, n, pairs)
+    if hub:
+        src = np.concatenate([src, np.zeros(hub, np.int64)])
+        dst = np.concatenate([dst, rng.choice(np.arange(1, n), hub, replace=False)])
+    key = np.unique(np.concatenate([src * n + dst, dst * n + src]))
+    e = np.stack([key // n, key % n], 1).astype(np.int32)
+    y = rng.integers(0, c, n).astype(np.int64)
+    y[:c] = np.arange(c)
+    if unlabeled:
+        idx = rng.choice(np.arange(c, n), unlabeled, replace=False)
+        y[idx[: unlabeled // 2]] = -1
+        y[idx[unlabeled // 2:]] = c + 3
+    return e, y
+
+
+def _census_twice(ip, ix, y, c, n, chunk=0):
+    from acm_gnn_amd import homophily as H
+    graph, yt = _pattern(ip, ix, n, chunk), _t(y)
+    buf = H.census_buffers(graph, c)
+    H.census(graph, yt, c, out=buf)
+    _assert_census(buf, R.census(ip, ix, y, c))
+    first = (buf._buf.clone(), buf.row_same.clone(), buf.row_deg.clone())
+    buf._buf.fill_(-7), buf.row_same.fill_(-7), buf.row_deg.fill_(-7)
+    H.census(graph, yt, c, out=buf)
+    torch.cuda.synchronize()
+    assert torch.equal(buf._buf, first[0]) and torch.equal(buf.row_same, first[1]) and torch.equal(buf.row_deg, first[2])
+    return graph
+
+
+@pytest.mark.parametrize("c", LF.CENSUS_BALLOT_CLASSES)
+def test_census_is_exact_on_both_sides_of_the_per_lane_counter_limit(c):
+    n = LF.CENSUS_SMALL_N
+    e, y = _symmetric_random_graph(n, c, 40 + c, pairs=5 * n, unlabeled=200, hub=600)
+    ip, ix = R.csr_of_edges(e, n)
+    graph = _census_twice(ip, ix, y, c, n, chunk=128)
+    assert graph.n_long_rows > 0                               # the hub row is split into pieces
+
+
+@pytest.mark.parametrize("c", LF.CENSUS_BALLOT_CLASSES)
+def test_census_is_exact_past_the_edges_and_finish_grid_caps(c):
+    n = LF.CENSUS_EDGES_N
+    e, y = _symmetric_random_graph(n, c, 50 + c, pairs=3 * n // 2, unlabeled=2000)
+    ip, ix = R.csr_of_edges(e, n)
+    _census_twice(ip, ix, y, c, n)
+
+
+def test_census_is_exact_past_the_prep_grid_cap():
+    n = LF.CENSUS_PREP_N
+    i = np.arange(n, dtype=np.int64)
+    e = np.concatenate([np.stack([i, (i + 1) % n], 1), np.stack([i, (i - 1) % n], 1)]).astype(np.int32)
+    y = np.random.default_rng(61).integers(0, 2, n).astype(np.int64)
+    ip, ix = R.csr_of_edges(e, n)
+    _census_twice(ip, ix, y, 2, n)

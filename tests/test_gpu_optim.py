@@ -4,6 +4,8 @@ import numpy as np
 import pytest
 import torch
 
+import launch_forms as LF
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
@@ -39,6 +41,40 @@ def test_fused_adam_matches_torch(decoupled, wd):
         np.testing.assert_allclose(p.detach().cpu().numpy(), want, rtol=3e-6, atol=3e-6 * max(1.0, float(np.abs(want).max())))
         st = a.state[p]
         assert float(st["step"]) == 12.0
+        wm = b.state[q]["exp_avg"].numpy()
+        np.testing.assert_allclose(st["exp_avg"].cpu().numpy(), wm, rtol=3e-6, atol=3e-6 * float(np.abs(wm).max()))
+        wv = b.state[q]["exp_avg_sq"].numpy()
+        np.testing.assert_allclose(st["exp_avg_sq"].cpu().numpy(), wv, rtol=3e-6, atol=3e-6 * float(np.abs(wv).max()))
+
+
+@pytest.mark.parametrize("decoupled,wd", [(False, 5e-4), (True, 5e-4)], ids=["adam", "adamw"])
+def test_fused_adam_matches_torch_where_a_block_takes_several_rounds(decoupled, wd):
+    """Parameters of more than CHUNK * MAX_BLOCKS elements (two and three rounds per block, with a tail) followed by a small
+    one: three steps against the single-tensor CPU implementation, gradients alternating between an aligned tensor (the
+    vector path) and a 4-byte-offset view (the scalar path)."""
+    from acm_gnn_amd import FusedAdam, FusedAdamW
+    g = torch.Generator().manual_seed(7)
+    init = [torch.randn(n, generator=g) for n in LF.ADAM_SIZES] + [torch.randn(5, 3, generator=g)]
+    ref = [torch.nn.Parameter(t.clone()) for t in init]
+    mine = [torch.nn.Parameter(t.clone().to(DEV)) for t in init]
+    kw = dict(lr=0.01, betas=(0.9, 0.999), eps=1e-8, weight_decay=wd)
+    a = (FusedAdamW if decoupled else FusedAdam)(mine, **kw)
+    b = (torch.optim.AdamW if decoupled else torch.optim.Adam)(ref, foreach=False, **kw)
+    for it in range(3):
+        for p, q in zip(mine, ref):
+            gr = torch.randn(q.shape, generator=g) * (1.0 + it)
+            q.grad = gr
+            buf = torch.empty(gr.numel() + 1, device=DEV)
+            view = buf[1:].view(gr.shape)                       # 4-byte aligned, not 16
+            view.copy_(gr)
+            p.grad = view if it % 2 else gr.to(DEV)
+        a.step()
+        b.step()
+    for p, q in zip(mine, ref):
+        want = q.detach().numpy()
+        np.testing.assert_allclose(p.detach().cpu().numpy(), want, rtol=3e-6, atol=3e-6 * max(1.0, float(np.abs(want).max())))
+        st = a.state[p]
+        assert float(st["step"]) == 3.0
         wm = b.state[q]["exp_avg"].numpy()
         np.testing.assert_allclose(st["exp_avg"].cpu().numpy(), wm, rtol=3e-6, atol=3e-6 * float(np.abs(wm).max()))
         wv = b.state[q]["exp_avg_sq"].numpy()

@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import launch_forms as LF
 import rocauc_ref as R
 from conftest import GOLDEN
 
@@ -59,6 +60,28 @@ def test_exact_triples_on_the_grid(n, k):
         sets[0] = np.asarray(sorted(set(range(n)) - out))    # ... which is taken out of them
         labels[sets[1][:3]] = 2                              # rows labelled 2 inside a set: skipped
     _check_exact(logits, labels, sets)
+
+
+def _grid_case(n, k):
+    rng = np.random.default_rng(n + k)
+    labels = rng.integers(0, 2, n).astype(np.int64)
+    labels[rng.random(n) < 0.02] = -1                       # unlabeled rows inside the sets: skipped
+    sets = [np.arange(n)] + [np.sort(rng.permutation(n)[: max(2, n // (j + 1))]) for j in range(1, k)]
+    return R.grid_logits(n, n + k), labels, sets
+
+
+@pytest.mark.parametrize("k", [1, 8])
+@pytest.mark.parametrize("n", LF.AUC_TILE_EDGE_N)
+def test_exact_triples_where_the_positions_end_on_a_tile_edge(n, k):
+    """The n + 1 prefix positions end one short of a tile, exactly on it and one past it."""
+    _check_exact(*_grid_case(n, k))
+
+
+@pytest.mark.parametrize("n,k", [(LF.AUC_SCAN_N, 2), (LF.AUC_SCORES_N, 1)])
+def test_exact_triples_past_the_scan_step_and_the_scores_grid(n, k):
+    """More than 256 tiles: the scan over the tile counts takes a second trip with a carry; more than 4096 x 256 rows: the
+    grid-stride loop of the scores kernel does."""
+    _check_exact(*_grid_case(n, k))
 
 
 def test_long_tie_groups_all_equal_one_class_and_reused_buffers():

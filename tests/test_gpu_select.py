@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import launch_forms as LF
 from select_ref import same_floats, select_ref
 
 pytestmark = pytest.mark.gpu
@@ -221,9 +222,19 @@ def _layout(sizes, offset):
 
 @pytest.mark.parametrize("n_tensors", [len(SIZES), 1, 40, 41, 81])
 def test_copy_if_is_bitwise_predicated_and_in_bounds(n_tensors):
+    _check_copy_if(_tables(n_tensors), n_tensors)
+
+
+@pytest.mark.parametrize("sizes", LF.COPY_TABLES, ids=lambda t: "+".join(str(s) for s in t))
+def test_copy_if_is_bitwise_where_a_block_takes_several_rounds(sizes):
+    """Tensors of more than CHUNK * MAX_BLOCKS words: every block copies several rounds of CHUNK words; 2 097 152 is the last
+    size with one round, 2 097 153 the first with two (and a one-word tail), 4 194 309 takes three."""
+    _check_copy_if(sizes, len(sizes))
+
+
+def _check_copy_if(sizes, seed):
     from acm_gnn_amd import _lib, functional as AF
-    sizes = _tables(n_tensors)
-    rng = np.random.default_rng(n_tensors)
+    rng = np.random.default_rng(seed)
     for src_off in (0, 1):
         for dst_off in (0, 1):
             s_at, s_len = _layout(sizes, src_off)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import launch_forms as LF
 import synthetic_ref as R
 from conftest import GOLDEN
 
@@ -256,3 +257,31 @@ def test_fit_runs_on_a_generated_graph():
     best, hist = T.fit(model, opt, x, ops, y, *sets, epochs=4)
     assert len(hist) == 4 and 0.0 <= best <= 1.0
     assert all(np.isfinite(row[0]) and np.isfinite(row[4]) and all(0.0 <= v <= 1.0 for v in row[1:4]) for row in hist)
+
+
+# ---- second trips of the grid-stride loops, several chunk sums per thread of the scan ------------------------------------------
+@pytest.mark.parametrize("n,f", LF.SYN_FEATURES)
+def test_features_equal_the_restatement_past_the_grid_cap(n, f):
+    """More quads of columns than the capped grid has threads: 16-byte stores (F % 4 == 0) and the scalar tail."""
+    from acm_gnn_amd import synthetic as S
+    got = S.random_features(n, f, seed=9, graph_index=4, device=DEV)
+    assert np.array_equal(_np(got).view(np.int32), R.uniform(n, f, 9, 4).view(np.int32))
+
+
+@pytest.mark.parametrize("kind,a,b", [(R.RANGE, 300_000, 7), (R.PAIR, 35_000, 1)], ids=["range", "pair"])
+def test_draws_equal_the_restatement_past_the_grid_cap(kind, a, b):
+    from acm_gnn_amd import synthetic as S
+    t = LF.SYN_DRAWS
+    got = _np(S.draw_keys(kind, a, b, 3, 1, 2 ** 63 + 5, 2 ** 40 + 1, t, DEV))
+    assert got.shape == (1, t) and np.array_equal(got[0], R.draw_keys(kind, a, b, 3, 2 ** 63 + 5, 2 ** 40 + 1, t))
+
+
+def test_select_with_several_chunk_sums_per_thread_of_the_scan():
+    """More than 256 chunks of 4096 draws: every thread of the scan adds, and later prefixes, several chunk sums."""
+    a, t, m = LF.SYN_SELECT["a"], LF.SYN_SELECT["draws"], LF.SYN_SELECT["m"]
+    keys = R.draw_keys(R.RANGE, a, 1, 2, 77, 1, t)
+    want, short = R.first_distinct(keys, m)
+    assert not short and len(want) == m
+    out, found, status = _select_raw(keys[None, :], [m], m + 5)
+    assert found == [m] and status == 0
+    assert np.array_equal(out[0, :m], want) and (out[0, m:] == -7).all()
