@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "acm_synth_inter_count", "acm_synth_emit",
     "acm_gcn_fwd", "acm_gcn_bwd_workspace_bytes", "acm_gcn_bwd", "acm_gemm_act",
     "acm_select_step", "acm_copy_if",
+    "acm_bnorm_stats_workspace_bytes", "acm_bnorm_stats", "acm_bnorm_fold", "acm_bnorm_param_bwd", "acm_bnorm_bwd_workspace_bytes", "acm_bnorm_bwd",
 )
 
 
@@ -343,6 +344,12 @@ def _declare(lib):
     lib.acm_gemm_act.argtypes = [i64, i64, i64, vp, i64, vp, i64, i32, vp, vp, i64, vp, sz, vp]
     lib.acm_select_step.argtypes = [C.POINTER(Select), vp]
     lib.acm_copy_if.argtypes = [i32, vp, vp, vp]
+    lib.acm_bnorm_stats_workspace_bytes.argtypes = [i64, i32, C.POINTER(sz)]
+    lib.acm_bnorm_stats.argtypes = [i64, i32, vp, i64, vp, vp, C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, sz, vp]
+    lib.acm_bnorm_fold.argtypes = [i32, i32, vp, i64, vp, vp, vp, i64, vp, vp]
+    lib.acm_bnorm_param_bwd.argtypes = [i32, i32, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp]
+    lib.acm_bnorm_bwd_workspace_bytes.argtypes = [i64, i32, C.POINTER(sz)]
+    lib.acm_bnorm_bwd.argtypes = [i64, i32, vp, i64, vp, i64, vp, vp, vp, C.c_float, i32, vp, i64, vp, vp, sz, vp, vp]
     lib.acm_reduce_flush.argtypes = [vp, vp]
     lib.acm_conv_fwd_tail_workspace_bytes.argtypes = [i64, i32, i32, C.POINTER(sz)]
     lib.acm_conv_fwd_tail.argtypes = [vp, C.POINTER(ConvFwd), C.POINTER(Loss), C.POINTER(ConvBwdLocal), vp, sz, vp, sz, vp]

@@ -45,10 +45,10 @@ class SelectionState:
     folds one epoch in (acm_select_step restates the host loop: same values, bit for bit); once the run has stopped, or the
     budget of ``epochs`` rows is used up, further launches change nothing but ``improved`` = 0.
 
-    ``params`` (keep the best): the tensors to snapshot whenever an epoch is selected -- one flat fp32 allocation with a view
-    per parameter, filled by a copy predicated on ``improved`` (acm_copy_if) right behind the selection launch."""
+    ``params`` (keep the best): the tensors to snapshot whenever an epoch is selected (``buffers``: further fp32 tensors kept
+    with them, the model's floating-point buffers) -- one flat fp32 allocation with a view per tensor, filled by a copy predicated on ``improved`` (acm_copy_if) right behind the selection launch."""
 
-    def __init__(self, rule, early_stopping, epochs, device, params=None):
+    def __init__(self, rule, early_stopping, epochs, device, params=None, buffers=None):
         if rule not in RULES:
             raise ValueError(f"rule must be one of {RULES}, not {rule!r}")
         if int(epochs) < 1 or int(early_stopping) < 0:
@@ -62,7 +62,9 @@ class SelectionState:
         self.params, self.snapshot, self._table = None, None, None
         if params is not None:
             self.params = list(params)
-            for p in self.params:
+            self._n_owned = len(self.params)                 # restore(model) checks these against model.parameters()
+            self.params += list(buffers or ())               # (``buffers``: snapshotted and restored with them, e.g. BatchNorm's
+            for p in self.params:                            #  running statistics -- what an evaluation pass reads beside the weights)
                 _check_device(p, "parameter")
                 if p.dtype != _F32 or not p.is_contiguous() or p.device != self.device:
                     raise ValueError(f"SelectionState: parameters must be contiguous fp32 tensors on {self.device}")
@@ -126,7 +128,7 @@ class SelectionState:
             raise RuntimeError("SelectionState.restore: the state keeps no snapshot (params=None)")
         if model is not None:
             mine = list(model.parameters())
-            if len(mine) != len(self.params) or any(a is not b for a, b in zip(mine, self.params)):
+            if len(mine) != self._n_owned or any(a is not b for a, b in zip(mine, self.params)):
                 raise ValueError("SelectionState.restore: not the model whose parameters the snapshot holds")
         if self.ctrl.tolist()[_CTRL_BEST_EPOCH] < 0:
             return False

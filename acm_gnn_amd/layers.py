@@ -272,7 +272,8 @@ class GraphConvolution(nn.Module):
 
 class MLP(nn.Module):
     """Linear stack with ReLU -> BatchNorm -> dropout between layers (the residual
-    branch of ACM-GCN++ uses num_layers=1, i.e. a single Linear; layers.py:123-163)."""
+    branch of ACM-GCN++ uses num_layers=1, i.e. a single Linear; layers.py:123-163).  A deeper stack on device tensors runs
+    on the acm_bnorm_* kernels inside functional.residual_mlp's envelope, on these torch modules outside it."""
 
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, dropout=0.5):
         super().__init__()
@@ -295,6 +296,8 @@ class MLP(nn.Module):
 
     def forward(self, data, input_tensor=False):
         x = data if input_tensor else data.graph["node_feat"]
+        if AF.residual_mlp_supported(x, self, self.training):          # device tensors inside the envelope: acm_bnorm_* kernels
+            return AF.residual_mlp(x, self, relu=False)
         for lin, bn in zip(self.lins[:-1], self.bns):
             x = torch.relu(lin(x))
             x = bn(x)

@@ -81,8 +81,9 @@ class GCN(nn.Module):
         counter-based dropout in the same epilogue (``drop`` = (p, tag, state, row_offset)): one GEMM launch
         (functional.residual_linear; CSR features: acm_spmm_v + acm_bias_act).  Row-sharded: the Linear's weight / bias
         gradients are summed over the ranks.  mlpX stacks deeper than one Linear (init_layers_X > 1: BatchNorm between
-        the layers) and Linears wider than 256 outputs (acm_bias_act_bwd's column budget) stay on torch modules and are
-        single-process only."""
+        the layers) run on the acm_bnorm_* kernels with the BatchNorm folded into the Linears (functional.residual_mlp)
+        inside its envelope; outside it, and Linears wider than 256 outputs (acm_bias_act_bwd's column budget), stay on
+        torch modules.  Both are single-process only: batch statistics are not combined over the ranks."""
         ops = adj_low if isinstance(adj_low, FilterOperators) else None
         group = ops.group if (ops is not None and ops.sharded) else None
         if len(self.mlpX.lins) == 1 and self.mlpX.lins[0].out_features <= 256:      # (acm_bias_act_bwd's column budget)
@@ -91,6 +92,8 @@ class GCN(nn.Module):
         if group is not None:
             raise NotImplementedError("row-sharded acmgcnpp supports init_layers_X = 1 with nhid <= 256 (the torch fallback "
                                       "does not reduce its gradients over the ranks)")
+        if AF.residual_mlp_supported(x, self.mlpX, self.mlpX.training):
+            return AF.residual_mlp(x, self.mlpX, relu=True, drop=drop, call=call)
         if isinstance(x, SparseFeatures):
             raise NotImplementedError("CSR features with init_layers_X > 1 or nhid > 256")
         f_in = self.mlpX.lins[0].in_features              # x may carry zero pad columns (dropout(..., pad_to=...))
@@ -202,7 +205,7 @@ class GCN(nn.Module):
     def auto_csr(self, x, ops):
         """Wide, mostly-zero features handed over dense -> their CSR twin (graph.SparseFeatures.auto, tuning key
         ``csr_features``), where this model has the CSR route: not acmsnowball (it concatenates the input with the hidden
-        blocks), not an mlpX stack the residual kernel does not cover, not row-sharded operators (a rank's block keeps the
+        blocks), not an mlpX stack neither residual kernel covers, not row-sharded operators (a rank's block keeps the
         dense halo exchange), and not while someone has replaced ``F.dropout`` (a mask-replay harness hands out masks of
         the dense shape: the input stays what the masks were recorded for)."""
         if not isinstance(x, torch.Tensor) or F.dropout is not _TORCH_DROPOUT or self.model_type == "acmsnowball":
@@ -210,7 +213,10 @@ class GCN(nn.Module):
         if ops is not None and ops.sharded:
             return x
         if self.model_type == "acmgcnpp" and not (len(self.mlpX.lins) == 1 and self.mlpX.lins[0].out_features <= 256):
-            return x
+            # a deep stack: where functional.residual_mlp takes the CSR twin (probed with the dense tensor: same device,
+            # same dtype, same width)
+            if not AF.residual_mlp_supported(x, self.mlpX, self.mlpX.training):
+                return x
         return SparseFeatures.auto(x)
 
     def forward(self, x, adj_low, adj_high=None, adj_low_unnormalized=None, rows_permuted=False, call=None):

@@ -63,6 +63,14 @@ def _rng_restore(snap):
         torch.cuda.set_rng_state(cuda, dev)
 
 
+def _buffers_restore(snap):
+    """Put the model's buffers back (values cloned before a pass that has to be redone)."""
+    if snap:
+        with torch.no_grad():
+            for b, v in snap:
+                b.copy_(v)
+
+
 def _held_entries(model):
     """What a captured pass over ``model`` reads beyond its graph's own pool: the layers' P = A_low X cache entries
     (layers.GraphConvolution._eval_agg_holder: key, input, {"agg": P, "xpad": ...}, operators) as they are right now."""
@@ -147,6 +155,7 @@ class TrainStep:
         self._manual_advance = False
         self._defer = True
         self._tape = bool(tape)
+        self._pass_proven = False           # a pass went through without a redo: the model's buffers need no snapshot any more
         self._tape_proven = False           # a first taped step went through: the model's Functions are all this package's
         if self._tape and F.dropout is not _TORCH_DROPOUT and getattr(model, "dropout", 0) > 0 and not _tape_safe(model):
             # someone replaced F.dropout (a mask-replay harness: it hands out recorded masks by call position) and this model
@@ -230,6 +239,9 @@ class TrainStep:
         # put back first, so that the redo draws the masks (F.dropout) the aborted forward drew -- the step then IS the step an
         # autograd run of the same seeds takes (acmgcnpp trained on other masks with tape=True than with False)
         rng = _rng_snapshot(self.labels.device) if (tape is not None and not self._tape_proven) else None
+        # ... and the model's buffers (BatchNorm running statistics and batch counter of a deep mlpX stack: the forward updates
+        # them) -- until a pass has gone through without a redo: a redone step must count once
+        buffers = None if self._pass_proven else [(b, b.detach().clone()) for b in getattr(self.model, "buffers", lambda: ())()]
         try:
             with AF.on_tape(tape):
                 loss, dz, out = self._forward_loss(call)
@@ -254,6 +266,7 @@ class TrainStep:
             # torch operations between the layers: this model's steps run on autograd from now on; the step is redone
             self._tape = False
             _rng_restore(rng)
+            _buffers_restore(buffers)
             self.opt.zero_grad(set_to_none=True)
             if pipe is not None:
                 pipe.primed = False
@@ -265,6 +278,7 @@ class TrainStep:
                 pending.discard()
             raise
         if pending is None:
+            self._pass_proven = True
             return loss
         adopted = pending.all_adopted([loss] + [p.grad for p in self._params])
         # The optimizer's launch can flush the list itself (acm_adam_config_t.pending: one launch and one grid drain less)
@@ -272,14 +286,17 @@ class TrainStep:
         self._unflushed = None
         if for_optimizer and adopted and self._opt_flushes and not pending.collectives_pending:
             self._unflushed = pending
+            self._pass_proven = True
             return loss
         pending.flush()
         if not adopted:
             self._defer = False
+            _buffers_restore(buffers)
             self.opt.zero_grad(set_to_none=True)
             if pipe is not None:
                 pipe.primed = False               # the first pass has already refilled its buffers for the next step
             return self._forward_backward(for_optimizer)
+        self._pass_proven = True
         return loss
 
     def _forward_loss(self, call):
@@ -665,7 +682,7 @@ def fit(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, 
     exactly (the window mean is the plain left-to-right float64 sum, ``sum()`` up to CPython 3.11; see DESIGN.md section 4a
     for the compensated ``sum()`` of later interpreters).  After an early stop the MODEL has taken up to ``sync_every - 1`` more optimizer steps than with
     ``sync_every=1``: the device state is frozen from the stopping epoch on, so the results do not see them.
-    ``keep_best=True`` snapshots the parameters on the device whenever an epoch is selected (acm_copy_if, predicated on the
+    ``keep_best=True`` snapshots the parameters (and the model's fp32 buffers: BatchNorm running statistics) on the device whenever an epoch is selected (acm_copy_if, predicated on the
     selection: no cost in the other epochs, no extra read) and restores the selected epoch's parameters into ``model`` in
     place before returning -- the values after that epoch's optimizer step, which its evaluation pass saw.
 
@@ -736,7 +753,10 @@ class _ResidentRun:
                                       "row-sharded operators are not supported")
         self.model, self.epochs, self.enqueued = model, int(epochs), 0
         self.select = AF.SelectionState(rule, early_stopping, epochs, labels.device,
-                                        params=list(model.parameters()) if keep_best else None)
+                                        params=list(model.parameters()) if keep_best else None,
+                                        # (the running statistics of a deep mlpX stack's BatchNorms: the selected epoch's
+                                        #  evaluation pass read them, so the returned model must hold them too)
+                                        buffers=[b for b in model.buffers() if b.dtype == torch.float32] if keep_best else None)
         w = row_weights(train_idx, x.shape[0], device=labels.device)
         self.step = TrainStep(model, optimizer, x, adj, labels, w, adj_high, adj_un, use_graph=True, fused_dropout=fused_dropout,
                               pipeline_input=pipeline_input, criterion=criterion)

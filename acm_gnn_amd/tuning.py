@@ -29,6 +29,8 @@ Host-level keys:
                n > 0 = for inputs of at least n columns with at most 1/16 of the entries nonzero.  Default 256
     small_step the fused six-launch training step / three-launch evaluation pass for small graphs (small.SmallPlan,
                acm_small_step): 0 = never, n > 0 = for graphs of at most n rows (the kernels take <= 16384).  Default 16384
+    mlp_stack  deep mlpX stacks (Linear-ReLU-BatchNorm, init_layers_X > 1) on the acm_bnorm_* kernels with the BatchNorm folded
+               into the Linears (functional.residual_mlp): 1 = on (default), 0 = the torch modules
 
 One policy for a malformed ACM_TUNING in both readers: the item is REPORTED on stderr and IGNORED -- by the
 library when it is loaded, by this module when it is imported (``parse(text)`` itself stays strict for programmatic use:
@@ -43,9 +45,10 @@ import os
 import threading
 
 KERNEL_KEYS = ("chunk", "wide_form", "bwd_split", "rows16", "agg_fused", "gemm_forms")
-HOST_DEFAULTS = {"rewrites": 15, "implicit": 1, "relabel": -1, "pipeline": 8192, "csr_features": 256, "small_step": 16384}
+HOST_DEFAULTS = {"rewrites": 15, "implicit": 1, "relabel": -1, "pipeline": 8192, "csr_features": 256, "small_step": 16384,
+                 "mlp_stack": 1}
 HOST_RANGES = {"rewrites": (0, 15), "implicit": (0, 1), "relabel": (-1, 1), "pipeline": (0, 1 << 31), "csr_features": (0, 1 << 31),
-               "small_step": (0, 16384)}
+               "small_step": (0, 16384), "mlp_stack": (0, 1)}
 
 REWRITE_AGG_FIRST = 1
 REWRITE_ACMII_RECOMPUTE = 2

@@ -1306,6 +1306,47 @@ typedef struct {
 
 int acm_copy_if(int32_t n_tensors, const acm_copy_tensor_t* tensors, const int32_t* flag, acm_stream_t stream);
 
+/* ------------------------------------------------ BatchNorm1d inside a deep mlpX stack (ABI 29) --
+ * ACM-GCN++ with --link_init_layers_X k > 1 (ACM-Pytorch/models/models.py:37-41,150-152): mlpX is k Linears with
+ *     x = lin(x); x = F.relu(x); x = self.bns[i](x); x = F.dropout(x, p=0)        (ACM-Pytorch/models/layers.py:279-284)
+ * between them.  With H = relu(lin(x)) [n_rows, f] the BatchNorm is Z = a * H + c per column, a = gamma r, c = beta - mu a,
+ * r = 1 / sqrt(var + eps); Z is never written: the NEXT Linear takes H with W' = W diag(a), b' = b + W c.  f <= 256 throughout.
+ *
+ * acm_bnorm_stats  replaces nn.BatchNorm1d's statistics (layers.py:282; torch.nn.functional.batch_norm): stats = [4][f] =
+ *                  mu | r | a | c.  train != 0: mu and the biased variance of the n_rows >= 2 rows of H, per-block
+ *                  (count, mean, M2) triples merged pairwise in a fixed order (never a sum of squares of the raw values); the
+ *                  same kernel updates running_mean / running_var (momentum in 0..1, unbiased variance) and adds 1 to the
+ *                  int64 *num_batches (any of the three may be NULL).  train == 0: mu / var are the running buffers, H is
+ *                  not read and nothing but `stats` is written.  Deterministic.  Workspace (train): acm_bnorm_stats_workspace_bytes,
+ *                  16-byte aligned, no initialisation.
+ * acm_bnorm_fold   W_folded = W diag(a) ([f_out, f_in], nn.Linear's layout), bias_folded = bias + W c (bias NULL: zero) --
+ *                  what makes lin(bn(H)) (layers.py:280,282) one acm_linear_fwd on H.
+ * acm_bnorm_param_bwd  the BatchNorm's and the following Linear's parameter gradients from M = G^T H ([f_out, f_in]) and
+ *                  s = colsum(G) (= that Linear's d_bias), G = dL/d(its pre-activation):
+ *                      dW = M diag(a) + s c^T     d_beta[k] = sum_o s[o] W[o, k]     d_gamma[k] = r[k] (sum_o W[o, k] M[o, k] - mu[k] d_beta[k])
+ *                  -- no pass over the rows (replaces the BatchNorm / Linear backward nodes of layers.py:280-282).
+ * acm_bnorm_bwd    the row-local pass of that backward: with dZ = G W,
+ *                      G_prev = [H > 0] a (dZ - d_beta / n - (H - mu) r d_gamma / n)
+ *                  (BatchNorm and ReLU backward of layers.py:281-282 in one pass) and d_bias = colsum(G_prev), the previous
+ *                  Linear's bias gradient (per-block partials, [group of 32 columns][block][32]; honours `defer`).  G may
+ *                  be dZ.  stats == NULL: the stack's OUTPUT epilogue instead -- G = dZ * keep_scale * [H > 0] with H the
+ *                  forward's output (relu = 0: dropped iff H == 0; neither: G = dZ), as acm_bias_act_bwd.  Workspace:
+ *                  acm_bnorm_bwd_workspace_bytes, 16-byte aligned.
+ * Errors: ACM_EINVAL NULL pointer / eps / momentum, ACM_ESHAPE a pitch below its width or too few rows, ACM_EUNSUPPORTED a
+ * width outside 1..256, ACM_ENOMEM workspace. */
+int acm_bnorm_stats_workspace_bytes(int64_t n_rows, int f, size_t* bytes);
+int acm_bnorm_stats(int64_t n_rows, int f, const float* H, int64_t ldh, const float* gamma, const float* beta, float eps,
+                    float momentum, int train, float* running_mean, float* running_var, int64_t* num_batches,
+                    float* stats, void* workspace, size_t workspace_bytes, acm_stream_t stream);
+int acm_bnorm_fold(int f_out, int f_in, const float* W, int64_t ldw, const float* bias, const float* stats, float* W_folded,
+                   int64_t ldwf, float* bias_folded, acm_stream_t stream);
+int acm_bnorm_param_bwd(int f_out, int f_in, const float* M, int64_t ldm, const float* s, const float* W, int64_t ldw,
+                        const float* stats, float* dW, int64_t lddw, float* d_beta, float* d_gamma, acm_stream_t stream);
+int acm_bnorm_bwd_workspace_bytes(int64_t n_rows, int f, size_t* bytes);
+int acm_bnorm_bwd(int64_t n_rows, int f, const float* dZ, int64_t lddz, const float* H, int64_t ldh, const float* stats,
+                  const float* d_beta, const float* d_gamma, float keep_scale, int relu, float* G, int64_t ldg,
+                  float* d_bias, void* workspace, size_t workspace_bytes, acm_reduce_list_t* defer, acm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
