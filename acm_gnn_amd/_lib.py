@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "acm_synth_inter_count", "acm_synth_emit",
     "acm_gcn_fwd", "acm_gcn_bwd_workspace_bytes", "acm_gcn_bwd", "acm_gemm_act",
     "acm_select_step", "acm_copy_if",
+    "acm_small_batch_table_bytes", "acm_small_batch_bind", "acm_small_batch_step", "acm_eval_metrics_batch", "acm_select_step_batch",
     "acm_bnorm_stats_workspace_bytes", "acm_bnorm_stats", "acm_bnorm_fold", "acm_bnorm_param_bwd", "acm_bnorm_bwd_workspace_bytes", "acm_bnorm_bwd",
 )
 
@@ -231,6 +232,12 @@ class Select(C.Structure):
                 ("ctrl", C.c_void_p), ("best", C.c_void_p), ("history", C.c_void_p)]
 
 
+class EvalMetricsSlot(C.Structure):
+    """acm_eval_metrics_slot_t: one slot's block of acm_eval_metrics_batch's device table (logits NULL: empty slot)."""
+    _fields_ = [("logits", C.c_void_p), ("weights", C.c_void_p), ("labels", C.c_void_p), ("out", C.c_void_p),
+                ("workspace", C.c_void_p)]
+
+
 class CopyTensor(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("numel", C.c_int64)]
 
@@ -252,6 +259,8 @@ class SmallStep(C.Structure):
                 ("weight_decay", C.c_double), ("decoupled", C.c_int32), ("also_advance", C.c_void_p), ("arrive", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
+
+SMALL_BATCH_MAX = 32          # ACM_SMALL_BATCH_MAX: slots of one acm_small_batch_* table
 
 _lib = None
 _lock = threading.Lock()
@@ -355,6 +364,11 @@ def _declare(lib):
     lib.acm_conv_fwd_tail.argtypes = [vp, C.POINTER(ConvFwd), C.POINTER(Loss), C.POINTER(ConvBwdLocal), vp, sz, vp, sz, vp]
     lib.acm_small_step_workspace_bytes.argtypes = [vp, vp, vp, C.POINTER(sz)]
     lib.acm_small_step.argtypes = [vp, vp, vp, C.POINTER(SmallStep), vp]
+    lib.acm_small_batch_table_bytes.argtypes = [i32, C.POINTER(sz)]
+    lib.acm_small_batch_bind.argtypes = [vp, vp, vp, i32, C.POINTER(C.POINTER(SmallStep)), vp, sz, vp]
+    lib.acm_small_batch_step.argtypes = [vp, vp, vp, i32, C.POINTER(SmallStep), vp, vp]
+    lib.acm_eval_metrics_batch.argtypes = [i64, i32, i64, i64, i32, i32, i32, vp, sz, vp]
+    lib.acm_select_step_batch.argtypes = [i32, vp, vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("acm_version", "acm_last_error", "acm_csr_destroy"):

@@ -48,10 +48,10 @@ __global__ __launch_bounds__(256) void bce_rows_kernel(int n, int C, const float
 // the counter -- one launch, the same bits on every run.
 constexpr int EVAL_MAX_SETS = 8;
 
-__global__ __launch_bounds__(256) void eval_metrics_kernel(int n, int C, const float* __restrict__ z, long ldz,
-                                                           const int64_t* __restrict__ y, const float* __restrict__ w, long ldw,
-                                                           int S, int loss_set, float* __restrict__ out,
-                                                           float* __restrict__ partial, int* __restrict__ arrive) {
+__device__ __forceinline__ void eval_metrics_body(int n, int C, const float* __restrict__ z, long ldz,
+                                                  const int64_t* __restrict__ y, const float* __restrict__ w, long ldw,
+                                                  int S, int loss_set, float* __restrict__ out,
+                                                  float* __restrict__ partial, int* __restrict__ arrive) {
     __shared__ float red[EVAL_MAX_SETS + 1][4];
     __shared__ int last;
     float acc[EVAL_MAX_SETS + 1];
@@ -127,6 +127,26 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(int n, int C, const f
         out[threadIdx.x] = (r[0] + r[1]) + (r[2] + r[3]);
     }
     if (threadIdx.x == 0) __hip_atomic_store(arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(256) void eval_metrics_kernel(int n, int C, const float* __restrict__ z, long ldz,
+                                                           const int64_t* __restrict__ y, const float* __restrict__ w, long ldw,
+                                                           int S, int loss_set, float* __restrict__ out,
+                                                           float* __restrict__ partial, int* __restrict__ arrive) {
+    eval_metrics_body(n, C, z, ldz, y, w, ldw, S, loss_set, out, partial, arrive);
+}
+
+// Grid row blockIdx.y runs the kernel above on its own argument block of a device table (read through the constant address
+// space: the row index is uniform, the pointers arrive by scalar loads like kernel arguments).  logits == NULL: an empty slot.
+// The partials and the arrival counter are the slot's own, and gridDim.x is the single launch's: the same tree, the same bits.
+__global__ __launch_bounds__(256) void eval_metrics_batch_kernel(int n, int C, long ldz, long ldw, int S, int loss_set, int nblk,
+                                                                 const acm_eval_metrics_slot_t* table) {
+    const __attribute__((address_space(4))) acm_eval_metrics_slot_t* p =
+        (const __attribute__((address_space(4))) acm_eval_metrics_slot_t*)table + blockIdx.y;
+    if (!p->logits) return;
+    float* partial = (float*)p->workspace;
+    eval_metrics_body(n, C, p->logits, ldz, p->labels, p->weights, ldw, S, loss_set, p->out, partial,
+                      (int*)(partial + (size_t)nblk * (size_t)(S + 1)));
 }
 
 int eval_blocks(int64_t n) {
@@ -221,6 +241,26 @@ extern "C" int acm_eval_metrics(int64_t n_rows, int n_classes, const float* logi
     int* arrive = (int*)(partial + (size_t)nblk * (size_t)(n_sets + 1));
     hipLaunchKernelGGL(eval_metrics_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (int)n_rows, n_classes, logits,
                        (long)ld_logits, labels, weights, (long)ld_weights, n_sets, loss_set, out, partial, arrive);
+    ACM_CHECK_HIP(hipGetLastError());
+    return ACM_OK;
+}
+
+extern "C" int acm_eval_metrics_batch(int64_t n_rows, int n_classes, int64_t ld_logits, int64_t ld_weights, int n_sets,
+                                      int loss_set, int32_t n_slots, const acm_eval_metrics_slot_t* table,
+                                      size_t workspace_bytes, acm_stream_t stream) {
+    ACM_REQUIRE(table, ACM_EINVAL, "acm_eval_metrics_batch: NULL table");
+    ACM_REQUIRE(n_slots >= 1, ACM_EINVAL, "acm_eval_metrics_batch: n_slots must be 1 .. %d (got %d)", ACM_SMALL_BATCH_MAX, (int)n_slots);
+    ACM_REQUIRE(n_slots <= ACM_SMALL_BATCH_MAX, ACM_EUNSUPPORTED, "acm_eval_metrics_batch: n_slots %d > %d", (int)n_slots, ACM_SMALL_BATCH_MAX);
+    ACM_REQUIRE(n_rows >= 0 && n_rows < INT32_MAX && n_classes >= 1, ACM_ESHAPE, "acm_eval_metrics_batch: bad sizes");
+    ACM_REQUIRE(n_classes <= 64, ACM_EUNSUPPORTED, "acm_eval_metrics_batch: %d classes > 64", n_classes);
+    ACM_REQUIRE(n_sets >= 1 && n_sets <= EVAL_MAX_SETS && loss_set >= 0 && loss_set < n_sets, ACM_ESHAPE,
+                "acm_eval_metrics_batch: %d index sets (1..%d), loss set %d", n_sets, EVAL_MAX_SETS, loss_set);
+    ACM_REQUIRE(ld_logits >= n_classes && ld_weights >= n_rows, ACM_ESHAPE, "acm_eval_metrics_batch: leading dimension too small");
+    const int nblk = eval_blocks(n_rows);
+    const size_t need = ((size_t)nblk * (size_t)(n_sets + 1) + 1) * sizeof(float);
+    ACM_REQUIRE(workspace_bytes >= need, ACM_ENOMEM, "acm_eval_metrics_batch: workspace %zu B per slot < required %zu B", workspace_bytes, need);
+    hipLaunchKernelGGL(eval_metrics_batch_kernel, dim3(nblk, n_slots), dim3(256), 0, (hipStream_t)stream, (int)n_rows, n_classes,
+                       (long)ld_logits, (long)ld_weights, n_sets, loss_set, nblk, table);
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }

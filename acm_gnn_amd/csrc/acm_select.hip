@@ -24,7 +24,7 @@ struct SelectArgs {
     double* history;
 };
 
-__global__ __launch_bounds__(64) void select_step_kernel(SelectArgs a) {
+__device__ __forceinline__ void select_step_body(const SelectArgs& a) {
     __shared__ double win[64];
     const int lane = threadIdx.x;
     const int epoch = a.ctrl[CTRL_EPOCH];              // block-uniform
@@ -68,6 +68,17 @@ __global__ __launch_bounds__(64) void select_step_kernel(SelectArgs a) {
     a.ctrl[CTRL_IMPROVED] = improved;
     if (windowed && val_loss > sum / (double)es) a.ctrl[CTRL_STOPPED] = 1;
     a.ctrl[CTRL_EPOCH] = epoch + 1;
+}
+
+__global__ __launch_bounds__(64) void select_step_kernel(SelectArgs a) { select_step_body(a); }
+
+// One block per slot on its own argument block of a device table (read through the constant address space: the block index is
+// uniform, the fields arrive by scalar loads like kernel arguments).  Both result pointers NULL: an empty slot.
+__global__ __launch_bounds__(64) void select_step_batch_kernel(const acm_select_t* table) {
+    const __attribute__((address_space(4))) acm_select_t* p = (const __attribute__((address_space(4))) acm_select_t*)table + blockIdx.x;
+    if (!p->result && !p->result_f64) return;
+    const SelectArgs a{p->rule, p->early_stopping, p->epochs, p->result, p->result_f64, p->train_loss, p->ctrl, p->best, p->history};
+    select_step_body(a);
 }
 
 // ---------------------------------------------------------------------------------------------- acm_copy_if
@@ -131,6 +142,15 @@ extern "C" int acm_select_step(const acm_select_t* p, acm_stream_t stream) {
     ACM_REQUIRE(p->train_loss && p->ctrl && p->best && p->history, ACM_EINVAL, "acm_select_step: NULL pointer");
     SelectArgs a{p->rule, p->early_stopping, p->epochs, p->result, p->result_f64, p->train_loss, p->ctrl, p->best, p->history};
     hipLaunchKernelGGL(select_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
+    ACM_CHECK_HIP(hipGetLastError());
+    return ACM_OK;
+}
+
+extern "C" int acm_select_step_batch(int32_t n_slots, const acm_select_t* table, acm_stream_t stream) {
+    ACM_REQUIRE(table, ACM_EINVAL, "acm_select_step_batch: NULL table");
+    ACM_REQUIRE(n_slots >= 1, ACM_EINVAL, "acm_select_step_batch: n_slots must be 1 .. %d (got %d)", ACM_SMALL_BATCH_MAX, (int)n_slots);
+    ACM_REQUIRE(n_slots <= ACM_SMALL_BATCH_MAX, ACM_EUNSUPPORTED, "acm_select_step_batch: n_slots %d > %d", (int)n_slots, ACM_SMALL_BATCH_MAX);
+    hipLaunchKernelGGL(select_step_batch_kernel, dim3(n_slots), dim3(64), 0, (hipStream_t)stream, table);
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }

@@ -20,8 +20,10 @@
 //     in its slot (write-through stores), arrives at the row's counter, and the LAST piece to arrive adds the slots in slot
 //     order and runs the row's epilogue -- no second launch, no float atomics, deterministic.
 #include <algorithm>
+#include <vector>
 
 #include "acm_common.h"
+#include "acm_small_batch_host.h"
 #include "acm_adam_device.h"
 
 namespace {
@@ -83,6 +85,25 @@ struct SmallDev {
     int64_t* also_advance;
     int* arrive;
 };
+
+// A sub-struct of the step's block as a value.  The block is either a kernel argument (generic reference) or an entry of the
+// batch table seen through the constant address space (scalar loads for uniform fields); functions that take a sub-struct by
+// generic reference get a copy made here, word by word -- small structs without indexing, so the copies dissolve into the
+// loads of the fields that are used.
+#define ACM_CONST_AS __attribute__((address_space(4)))
+template <class T>
+__device__ __forceinline__ T take(const T& v) { return v; }
+template <class T>
+__device__ __forceinline__ T take(const ACM_CONST_AS T& v) {
+    static_assert(sizeof(T) % 4 == 0 && sizeof(T) <= 64, "take: a small struct of whole words");
+    typedef uint32_t __attribute__((may_alias)) word_t;
+    T out;
+    const ACM_CONST_AS word_t* s = reinterpret_cast<const ACM_CONST_AS word_t*>(&v);
+    word_t* o = reinterpret_cast<word_t*>(&out);
+#pragma unroll
+    for (unsigned i = 0; i < sizeof(T) / 4; ++i) o[i] = s[i];
+    return out;
+}
 
 __device__ __forceinline__ f4 ld4(const float* p) { return *reinterpret_cast<const f4*>(p); }
 __device__ __forceinline__ void st4(float* p, f4 v) { *reinterpret_cast<f4*>(p) = v; }
@@ -311,15 +332,16 @@ __device__ __forceinline__ void adam_four(const SmallTensor& t, long i, f4 g, co
 //   W2T  [idx = ch * 8 + c][col]: layer 2's weights, classes padded to 8 -- a lane's four columns of one output are one
 //        16-byte load, for the forward projection (launch 2) and for dH = dZ2 W2^T (launch 4) alike
 //   FACT [layer * 17 + role][2]: the step-dependent Adam factors of every tensor (double-precision pow: once, not per block)
-__device__ __forceinline__ void write_tables(const SmallDev& d) {
+template <class D>
+__device__ __forceinline__ void write_tables(const D& d) {
     if (blockIdx.x != 0) return;
     for (int e = threadIdx.x; e < 3 * F * C8; e += blockDim.x) {
         const int idx = e / F, col = e % F, ch = idx >> 3, c = idx & 7;
         d.W2T[e] = c < d.C ? d.t[1][ACM_SR_W_LOW + ch].p[col * d.C + c] : 0.f;
     }
     if ((int)threadIdx.x < 2 * ACM_SMALL_ROLES && d.update) {
-        const SmallTensor& t = d.t[threadIdx.x / ACM_SMALL_ROLES][threadIdx.x % ACM_SMALL_ROLES];
-        if (t.p && t.step) acm_adam_step_factors(d.hp, t.step[0], d.FACT[2 * threadIdx.x], d.FACT[2 * threadIdx.x + 1]);
+        const SmallTensor t = take(d.t[threadIdx.x / ACM_SMALL_ROLES][threadIdx.x % ACM_SMALL_ROLES]);
+        if (t.p && t.step) acm_adam_step_factors(take(d.hp), t.step[0], d.FACT[2 * threadIdx.x], d.FACT[2 * threadIdx.x + 1]);
     }
     // the dropout counter of THIS step: the later launches draw their masks with this copy, so the last launch may advance
     // the live counter whenever it likes (no arrival barrier over its ~900 blocks: their atomics on one address were 10 us)
@@ -327,16 +349,17 @@ __device__ __forceinline__ void write_tables(const SmallDev& d) {
 }
 
 // ------------------------------------------------------------------------------------------------ launch 1: Z1 = drop(X) Wcat
-__global__ __launch_bounds__(256) void small_proj1_kernel(SmallDev d) {
+template <class D>
+__device__ __forceinline__ void small_proj1_body(const D& d) {
     write_tables(d);
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
     const int wave = (int)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int)gridDim.x * 4;
-    const AcmDropCtx dc = acm_drop_ctx(d.drop_in);
+    const AcmDropCtx dc = acm_drop_ctx(take(d.drop_in));
     const float* tab[3] = {d.t[0][ACM_SR_W_LOW].p, d.t[0][ACM_SR_W_HIGH].p, d.t[0][ACM_SR_W_MLP].p};
     const int ld[3] = {F, F, F};
     const float* __restrict__ xv = d.x_vals;
     wide_items<3>(
-        d.x, d.slots, d.counters, wave, n_waves, [](int) { return 0; },
+        take(d.x), d.slots, d.counters, wave, n_waves, [](int) { return 0; },
         [&](const AcmItem& item, f4(&acc)[3]) {
             wide_gather<3, 0>(d.x.indices, item.begin, item.end, tab, ld, 0,
                               [&](int pos) { return xv[pos] * acm_drop1(dc, pos, 0); }, acc);
@@ -354,13 +377,13 @@ struct Pre2 {
     float rs;
     f4 own;
 };
-template <bool FOUR, bool VARIANT>
-__global__ __launch_bounds__(64 * WAVES) void small_conv1_fwd_kernel(SmallDev d, const float* z1) {
+template <bool FOUR, bool VARIANT, class D>
+__device__ __forceinline__ void small_conv1_fwd_body(const D& d, const float* z1) {
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
     const int wave = (int)blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = (int)gridDim.x * WAVES;
     constexpr int NCH = FOUR ? 3 : 2;
     constexpr int K = FOUR ? 4 : 3;
-    const AcmDropCtx dh = acm_drop_ctx(d.drop_hidden);
+    const AcmDropCtx dh = acm_drop_ctx(take(d.drop_hidden));
     const float* tab[3] = {z1, z1 + F, FOUR ? d.t[0][ACM_SR_STRUC].p : z1};
     const int ld[3] = {3 * F, 3 * F, F};
     const bool act = g < K;
@@ -380,7 +403,7 @@ __global__ __launch_bounds__(64 * WAVES) void small_conv1_fwd_kernel(SmallDev d,
     const float* own_base = g == 1 ? z1 + F : (g == 2 ? z1 + 2 * F : (FOUR ? d.t[0][ACM_SR_STRUC].p : z1));
     const int own_ld = (g == 1 || g == 2) ? 3 * F : F;
     wide_items<NCH>(
-        d.graph, d.slots, d.counters, wave, n_waves,
+        take(d.graph), d.slots, d.counters, wave, n_waves,
         [&](int row) {
             Pre2 pf;
             pf.rs = d.row_scale[row];
@@ -458,8 +481,8 @@ struct Pre3 {
     float rs, zH, zI, sS, w;
     int y;
 };
-template <bool FOUR>
-__global__ __launch_bounds__(64 * WAVES) void small_conv2_fwd_kernel(SmallDev d) {
+template <bool FOUR, class D>
+__device__ __forceinline__ void small_conv2_fwd_body(const D& d) {
     __shared__ float red[WAVES][PART3_PITCH];
     const int lane = threadIdx.x & 63, c = lane & 7, wv = threadIdx.x >> 6;
     const int wave = (int)blockIdx.x * WAVES + wv, n_waves = (int)gridDim.x * WAVES;
@@ -489,7 +512,7 @@ __global__ __launch_bounds__(64 * WAVES) void small_conv2_fwd_kernel(SmallDev d)
         for (int b = 0; b < K; ++b) a_dm[ch][b] = 0.f;
     }
     narrow_items<NQ>(
-        d.graph, d.slots, d.counters, wave, n_waves,
+        take(d.graph), d.slots, d.counters, wave, n_waves,
         [&](int row) {
             Pre3 pf;
             pf.rs = d.row_scale[row];
@@ -653,8 +676,8 @@ struct Pre4 {
     f4 o, h;
     float mean, rstd, sa[8];
 };
-template <bool FOUR>
-__global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_kernel(SmallDev d, const float* z1) {
+template <bool FOUR, class D>
+__device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1) {
     __shared__ __attribute__((aligned(16))) float red[WAVES / 2][PART4];  // the waves' sums side by side (two rounds: 37 KB)
     __shared__ __attribute__((aligned(16))) float w2s[3 * F * C8];        // W2T [idx][col]: 24 rows of 64, read by every row's dH
     for (int e = 4 * threadIdx.x; e < 3 * F * C8; e += 4 * 64 * WAVES) st4(w2s + e, ld4(d.W2T + e));
@@ -665,7 +688,7 @@ __global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_kernel(SmallDev d,
     constexpr int K = FOUR ? 4 : 3;
     const int C = d.C;
     const bool variant = d.relu_before != 0;
-    const AcmDropCtx dh = acm_drop_ctx(d.drop_hidden);
+    const AcmDropCtx dh = acm_drop_ctx(take(d.drop_hidden));
     const float inv_keep = dh.on ? dh.inv_keep : 1.f;
     const bool act = g < K;
     const f4 av = act ? ld4(d.t[0][ACM_SR_V_LOW + g].p + 4 * m) : zero4();
@@ -678,8 +701,8 @@ __global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_kernel(SmallDev d,
     for (int a = 0; a < K; ++a)
 #pragma unroll
         for (int b = 0; b < K; ++b) mix[a][b] = d.t[0][ACM_SR_MIX].p[a * K + b];
-    const AdamFactors af(d.hp);
-    const SmallTensor& ts2 = d.t[1][ACM_SR_STRUC];
+    const AdamFactors af(take(d.hp));
+    const SmallTensor ts2 = take(d.t[1][ACM_SR_STRUC]);
     const bool s2_lane = FOUR && lane < 8 && c < C;
     f4 a_w2[6];
 #pragma unroll
@@ -687,7 +710,7 @@ __global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_kernel(SmallDev d,
     f4 a_dv = zero4(), a_dg = zero4(), a_db = zero4();
     float a_dm = 0.f;                                 // d(mix): lane L < 16 holds element (L >> 2, L & 3)
     narrow_items<NQ>(
-        d.graph, d.slots, d.counters, wave, n_waves,
+        take(d.graph), d.slots, d.counters, wave, n_waves,
         [&](int row) {                                   // everything the row's epilogue reads that is not a gathered sum
             Pre4 pf;
             pf.rs = d.row_scale[row];
@@ -862,17 +885,17 @@ __global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_kernel(SmallDev d,
 struct Pre5 {
     f4 a, b, pp, mm, vv;
 };
-template <bool FOUR, bool VARIANT>
-__global__ __launch_bounds__(64 * WAVES) void small_conv1_bwd_kernel(SmallDev d, const float* z1) {
+template <bool FOUR, bool VARIANT, class D>
+__device__ __forceinline__ void small_conv1_bwd_body(const D& d, const float* z1) {
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
     const int wave = (int)blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = (int)gridDim.x * WAVES;
     constexpr int NCH = FOUR ? 3 : 2;
     const float* tab[3] = {d.G1, d.G1 + F, d.G1 + 2 * F};
     const int ld[3] = {3 * F, 3 * F, 3 * F};
-    const AdamFactors af(d.hp);
-    const SmallTensor& ts = d.t[0][ACM_SR_STRUC];
+    const AdamFactors af(take(d.hp));
+    const SmallTensor ts = take(d.t[0][ACM_SR_STRUC]);
     wide_items<NCH>(
-        d.graph, d.slots, d.counters, wave, n_waves,
+        take(d.graph), d.slots, d.counters, wave, n_waves,
         [&](int row) {
             // group 0: the ReLU mask of Z_L (ACMII); group 1: its direct term dZ_H and the mask of Z_H; group 3: G_S of the row
             // and the parameter row with its moments
@@ -928,12 +951,13 @@ __global__ __launch_bounds__(64 * WAVES) void small_conv1_bwd_kernel(SmallDev d,
 // blocks [0, item_blocks): dW1 = drop(X)^T dZ1 by feature row (the transposed feature handle's items) + its update;
 // blocks behind: RED_EL elements of the two partial-sum vectors per block (sum over the producer workgroups and the long
 // rows' records, then the update).  The first block advances the step counters.
-__global__ __launch_bounds__(256) void small_finish_kernel(SmallDev d, int item_blocks, int red_blocks) {
+template <class D>
+__device__ __forceinline__ void small_finish_body(const D& d, int item_blocks, int red_blocks) {
     __shared__ float red8[256 / RED_EL][RED_EL];
     const float* __restrict__ fact = d.FACT;              // step factors of every tensor (launch 1 wrote them)
-    const AdamFactors af(d.hp);
+    const AdamFactors af(take(d.hp));
     auto apply = [&](int layer, int role, long i, float gsum) {
-        const SmallTensor& t = d.t[layer][role];
+        const SmallTensor t = take(d.t[layer][role]);
         if (!t.p) return;
         if (t.g) t.g[i] = gsum;
         if (!d.update) return;
@@ -946,19 +970,19 @@ __global__ __launch_bounds__(256) void small_finish_kernel(SmallDev d, int item_
     if (blk < item_blocks) {
         const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
         const int wave = blk * 4 + (threadIdx.x >> 6), n_waves = item_blocks * 4;
-        const AcmDropCtx dc = acm_drop_ctx(d.drop_in);
+        const AcmDropCtx dc = acm_drop_ctx(take(d.drop_in));
         const float* tab[3] = {d.DZ1, d.DZ1 + F, d.DZ1 + 2 * F};
         const int ld[3] = {3 * F, 3 * F, 3 * F};
         const float* __restrict__ xv = d.x_vals;
         const float* __restrict__ xtv = d.xt_vals;
         const int32_t* __restrict__ sp = d.xt_src_pos;
         wide_items<3>(
-            d.xt, d.slots, d.counters, wave, n_waves,
+            take(d.xt), d.slots, d.counters, wave, n_waves,
             [&](int frow) {                                // the weight rows this wave will update, with their moments
                 Pre5 pf;
                 pf.a = pf.b = pf.pp = pf.mm = pf.vv = zero4();
                 if (g < 3 && d.update) {
-                    const SmallTensor& t = d.t[0][ACM_SR_W_LOW + g];
+                    const SmallTensor t = take(d.t[0][ACM_SR_W_LOW + g]);
                     const long i = (long)frow * F + 4 * m;
                     pf.pp = ld4(t.p + i), pf.mm = ld4(t.m + i), pf.vv = ld4(t.v + i);
                 }
@@ -975,7 +999,7 @@ __global__ __launch_bounds__(256) void small_finish_kernel(SmallDev d, int item_
             [&](int frow, f4(&acc)[3], const Pre5& pf) {
                 if (g < 3) {
                     const f4 gw = sel4(g, acc[0], acc[1], acc[2], acc[2]);
-                    const SmallTensor& t = d.t[0][ACM_SR_W_LOW + g];
+                    const SmallTensor t = take(d.t[0][ACM_SR_W_LOW + g]);
                     const long i = (long)frow * F + 4 * m;
                     if (t.g) st4(t.g + i, gw);
                     if (d.update) {
@@ -1057,12 +1081,12 @@ __global__ __launch_bounds__(256) void small_finish_kernel(SmallDev d, int item_
     // workspace): the first block advances them
     if (blk == 0 && d.update) {
         if ((int)threadIdx.x < 2 * ACM_SMALL_ROLES) {
-            const SmallTensor& t = d.t[threadIdx.x / ACM_SMALL_ROLES][threadIdx.x % ACM_SMALL_ROLES];
+            const SmallTensor t = take(d.t[threadIdx.x / ACM_SMALL_ROLES][threadIdx.x % ACM_SMALL_ROLES]);
             if (t.p && t.step) {
                 // tensors that share one step scalar are advanced once (the first role that names it)
                 bool first = true;
                 for (int o = 0; o < (int)threadIdx.x; ++o) {
-                    const SmallTensor& u = d.t[o / ACM_SMALL_ROLES][o % ACM_SMALL_ROLES];
+                    const SmallTensor u = take(d.t[o / ACM_SMALL_ROLES][o % ACM_SMALL_ROLES]);
                     if (u.p && u.step == t.step) first = false;
                 }
                 if (first) t.step[0] += 1.0f;
@@ -1070,6 +1094,89 @@ __global__ __launch_bounds__(256) void small_finish_kernel(SmallDev d, int item_
         }
         if (threadIdx.x == 0 && d.also_advance) d.also_advance[0] += 1;
     }
+}
+
+// ------------------------------------------------------------------------------------------------ the kernels: single and batched forms
+// Single form: the step's SmallDev by value in the kernel arguments (acm_small_step).
+// Batched form (acm_small_batch_step): grid (the single form's x, n_slots); grid row blockIdx.y takes ITS SmallDev from a
+// device table.  The entry is read through the constant address space -- the table is written by copies between launches
+// only, never by a kernel, and the row index is wave-uniform -- so its fields arrive by scalar loads exactly as kernel
+// arguments do; the bodies are templates over the block's reference type, so both forms are the same source.
+// The body runs with the same blockIdx.x / gridDim.x as the single step, on the slot's own part3 / part4 / slots / counters
+// / latch: the same instructions in the same order, the same bits.
+struct SmallBatchEntry {
+    int32_t active;                  // 0: an empty slot -- every launch returns before it touches anything else
+    int32_t key[6];                  // per launch: gridDim.x * 8 + form (four | variant << 1 | train << 2) the entry was bound
+    int32_t item_blocks;             // for: a grid row of any other launch shape does nothing (part3 / part4 are sized by it)
+    SmallDev first;                  // launch 1: reads the live dropout counter and latches it
+    SmallDev rest;                   // launches 2-6: draw their masks with the latched copy
+};
+template <int LAUNCH>
+__device__ __forceinline__ const ACM_CONST_AS SmallBatchEntry* batch_entry(const SmallBatchEntry* table, int form) {
+    const ACM_CONST_AS SmallBatchEntry* e = (const ACM_CONST_AS SmallBatchEntry*)table + blockIdx.y;
+    if (e->active == 0 || e->key[LAUNCH] != (int)gridDim.x * 8 + form) return nullptr;
+    return e;
+}
+__host__ __device__ constexpr int form_of(bool four, bool variant, bool train) { return (four ? 1 : 0) | (variant ? 2 : 0) | (train ? 4 : 0); }
+
+__global__ __launch_bounds__(256) void small_proj1_kernel(SmallDev d) { small_proj1_body(d); }
+__global__ __launch_bounds__(256) void small_proj1_batch_kernel(const SmallBatchEntry* table, int form) {
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<0>(table, form);
+    if (!e) return;
+    const ACM_CONST_AS SmallDev& d = e->first;
+    small_proj1_body(d);
+}
+
+template <bool FOUR, bool VARIANT>
+__global__ __launch_bounds__(64 * WAVES) void small_conv1_fwd_kernel(SmallDev d, const float* z1) { small_conv1_fwd_body<FOUR, VARIANT>(d, z1); }
+template <bool FOUR, bool VARIANT>
+__global__ __launch_bounds__(64 * WAVES) void small_conv1_fwd_batch_kernel(const SmallBatchEntry* table, int form) {
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<1>(table, form);
+    if (!e) return;
+    const ACM_CONST_AS SmallDev& d = e->rest;
+    small_conv1_fwd_body<FOUR, VARIANT>(d, d.Z1);
+}
+
+template <bool FOUR>
+__global__ __launch_bounds__(64 * WAVES) void small_conv2_fwd_kernel(SmallDev d) { small_conv2_fwd_body<FOUR>(d); }
+template <bool FOUR>
+__global__ __launch_bounds__(64 * WAVES) void small_conv2_fwd_batch_kernel(const SmallBatchEntry* table, int form) {
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<2>(table, form);
+    if (!e) return;
+    const ACM_CONST_AS SmallDev& d = e->rest;
+    small_conv2_fwd_body<FOUR>(d);
+}
+
+template <bool FOUR>
+__global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_kernel(SmallDev d, const float* z1) { small_conv2_bwd_body<FOUR>(d, z1); }
+template <bool FOUR>
+__global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_batch_kernel(const SmallBatchEntry* table, int form) {
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<3>(table, form);
+    if (!e) return;
+    const ACM_CONST_AS SmallDev& d = e->rest;
+    small_conv2_bwd_body<FOUR>(d, d.Z1);
+}
+
+template <bool FOUR, bool VARIANT>
+__global__ __launch_bounds__(64 * WAVES) void small_conv1_bwd_kernel(SmallDev d, const float* z1) { small_conv1_bwd_body<FOUR, VARIANT>(d, z1); }
+template <bool FOUR, bool VARIANT>
+__global__ __launch_bounds__(64 * WAVES) void small_conv1_bwd_batch_kernel(const SmallBatchEntry* table, int form) {
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<4>(table, form);
+    if (!e) return;
+    const ACM_CONST_AS SmallDev& d = e->rest;
+    small_conv1_bwd_body<FOUR, VARIANT>(d, d.Z1);
+}
+
+__global__ __launch_bounds__(256) void small_finish_kernel(SmallDev d, int item_blocks, int red_blocks) { small_finish_body(d, item_blocks, red_blocks); }
+// (three waves per SIMD like the single form: without the hint the table pointer costs four registers and an occupancy step)
+// Three waves per SIMD like the single form.  Left alone the compiler takes 172 registers here (the single form: 168, the
+// limit for three waves) and drops to two; held to three it parks two loop-invariant addresses in scratch (20 bytes per lane:
+// stored once per wave, read back once per work item).  EXPERIMENTS.md has the table.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void small_finish_batch_kernel(const SmallBatchEntry* table, int form, int item_blocks, int red_blocks) {
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<5>(table, form);
+    if (!e || e->item_blocks != item_blocks) return;
+    const ACM_CONST_AS SmallDev& d = e->rest;
+    small_finish_body(d, item_blocks, red_blocks);
 }
 
 ItemView view_of(const acm_csr* a) {
@@ -1120,8 +1227,25 @@ extern "C" int acm_small_step_workspace_bytes(const acm_csr_t* a_low, const acm_
     return ACM_OK;
 }
 
-extern "C" int acm_small_step(const acm_csr_t* a, const acm_csr_t* x, const acm_csr_t* xt, const acm_small_step_t* p,
-                              acm_stream_t stream) {
+namespace {
+
+// The grids of the six launches: functions of the handles alone, so the same for every slot of a batch.
+struct Grids {
+    int proj, wide, graph, item_blocks, red_blocks;
+};
+Grids grids_of(const acm_csr* a, const acm_csr* x, const acm_csr* xt, bool train) {
+    Grids g;
+    g.proj = std::max((int)std::min<int64_t>(2 * MAX_WG, (x->n_items + 3) / 4), 1);
+    g.graph = (int)std::min<int64_t>(MAX_WG, (a->n_items + WAVES - 1) / WAVES);
+    g.wide = (int)std::min<int64_t>(MAX_WG_WIDE, (a->n_items + WAVES - 1) / WAVES);
+    g.item_blocks = train ? (int)std::min<int64_t>(2 * MAX_WG, (xt->n_items + 3) / 4) : 0;
+    g.red_blocks = (PART4 + PART3 + RED_EL - 1) / RED_EL;
+    return g;
+}
+
+// Validates one run's block against the handles and fills what its kernels read: d1 for launch 1 (the live dropout counter),
+// d for launches 2-6 (the latched one).  Shared by acm_small_step and acm_small_batch_bind: one envelope, one set of refusals.
+int small_prepare(const acm_csr* a, const acm_csr* x, const acm_csr* xt, const acm_small_step_t* p, SmallDev& d1, SmallDev& d) {
     ACM_REQUIRE(a && p, ACM_EINVAL, "acm_small_step: NULL argument");
     ACM_REQUIRE(a->vals == nullptr && a->n_rows == a->n_cols, ACM_EUNSUPPORTED,
                 "acm_small_step: pattern-only square operators only (acm_csr_create with vals = NULL)");
@@ -1151,7 +1275,7 @@ extern "C" int acm_small_step(const acm_csr_t* a, const acm_csr_t* x, const acm_
             for (int c = 0; c < K; ++c)
                 ACM_REQUIRE(p->t[l][ACM_SR_LNW_LOW + c].param && p->t[l][ACM_SR_LNB_LOW + c].param, ACM_EINVAL, "acm_small_step: layer %d lacks LayerNorm parameters", l);
     }
-    SmallDev d{};
+    d = SmallDev{};
     d.n = (int)a->n_rows, d.f_in = p->f_in, d.C = p->n_classes, d.k = K;
     d.relu_before = p->relu_before, d.layernorm = p->layernorm, d.train = p->train, d.update = p->update;
     d.scale = p->scale;
@@ -1180,19 +1304,43 @@ extern "C" int acm_small_step(const acm_csr_t* a, const acm_csr_t* x, const acm_
     d.drop_in = p->drop_in, d.drop_hidden = p->drop_hidden;
     d.hp = AdamScalars{p->lr, p->beta1, p->beta2, p->eps, p->weight_decay, p->decoupled};
     d.also_advance = p->also_advance, d.arrive = p->arrive;
-    const float* z1 = d.Z1;
-    hipStream_t s = (hipStream_t)stream;
-    SmallDev d1 = d;                               // launch 1 reads the live dropout counter and latches it for the others
+    d1 = d;                                        // launch 1 reads the live dropout counter and latches it for the others
     if (d.drop_in.p > 0.f) d.drop_in.step = d.latch;
     if (d.drop_hidden.p > 0.f) d.drop_hidden.step = d.latch;
-    const int graph_wg = (int)std::min<int64_t>(MAX_WG, (a->n_items + WAVES - 1) / WAVES);
-    const int wide_wg = (int)std::min<int64_t>(MAX_WG_WIDE, (a->n_items + WAVES - 1) / WAVES);
-    d.nwg3 = d.nwg4 = graph_wg;
-    const bool four = K == 4, variant = p->relu_before != 0;
-    {   // launch 1
-        const int wg = (int)std::min<int64_t>(2 * MAX_WG, (x->n_items + 3) / 4);
-        hipLaunchKernelGGL(small_proj1_kernel, dim3(std::max(wg, 1)), dim3(256), 0, s, d1);
-    }
+    d.nwg3 = d.nwg4 = grids_of(a, x, xt, p->train != 0).graph;
+    return ACM_OK;
+}
+
+// the checks acm_small_batch_step can make without the table (device memory): handles and the shared fields of `shape`
+int batch_shape_check(const acm_csr* a, const acm_csr* x, const acm_csr* xt, int32_t n_slots, const acm_small_step_t* shape) {
+    ACM_REQUIRE(n_slots >= 1, ACM_EINVAL, "acm_small_batch: n_slots must be 1 .. %d (got %d)", ACM_SMALL_BATCH_MAX, (int)n_slots);
+    ACM_REQUIRE(n_slots <= ACM_SMALL_BATCH_MAX, ACM_EUNSUPPORTED, "acm_small_batch: n_slots %d > %d slots of one table", (int)n_slots,
+                ACM_SMALL_BATCH_MAX);
+    ACM_REQUIRE(a && x && shape, ACM_EINVAL, "acm_small_batch: NULL argument");
+    ACM_REQUIRE(shape->n_channels == 3 || shape->n_channels == 4, ACM_EINVAL, "acm_small_batch: n_channels must be 3 or 4");
+    ACM_REQUIRE(a->n_rows >= 1 && a->n_rows <= 16384 && a->vals == nullptr && a->n_rows == a->n_cols, ACM_EUNSUPPORTED,
+                "acm_small_batch: pattern-only square operators of 1 .. 16384 rows");
+    ACM_REQUIRE(x->n_rows == a->n_rows && x->n_cols == shape->f_in, ACM_ESHAPE, "acm_small_batch: feature handle shape");
+    if (shape->train)
+        ACM_REQUIRE(xt && xt->n_rows == shape->f_in && xt->n_cols == a->n_rows, ACM_EINVAL,
+                    "acm_small_batch: the transposed feature handle (x_t) is needed for dW1");
+    return ACM_OK;
+}
+
+}  // namespace
+
+extern "C" int acm_small_step(const acm_csr_t* a, const acm_csr_t* x, const acm_csr_t* xt, const acm_small_step_t* p,
+                              acm_stream_t stream) {
+    SmallDev d1, d;
+    const int st = small_prepare(a, x, xt, p, d1, d);
+    if (st != ACM_OK) return st;
+    const float* z1 = d.Z1;
+    hipStream_t s = (hipStream_t)stream;
+    const Grids gr = grids_of(a, x, xt, p->train != 0);
+    const int graph_wg = gr.graph, wide_wg = gr.wide;
+    const bool four = p->n_channels == 4, variant = p->relu_before != 0;
+    // launch 1
+    hipLaunchKernelGGL(small_proj1_kernel, dim3(gr.proj), dim3(256), 0, s, d1);
     // launch 2
     if (four && variant) hipLaunchKernelGGL((small_conv1_fwd_kernel<true, true>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
     else if (four) hipLaunchKernelGGL((small_conv1_fwd_kernel<true, false>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
@@ -1211,9 +1359,85 @@ extern "C" int acm_small_step(const acm_csr_t* a, const acm_csr_t* x, const acm_
         else if (variant) hipLaunchKernelGGL((small_conv1_bwd_kernel<false, true>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
         else hipLaunchKernelGGL((small_conv1_bwd_kernel<false, false>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
         // launch 6
-        const int item_blocks = (int)std::min<int64_t>(2 * MAX_WG, (xt->n_items + 3) / 4);
-        const int red_blocks = (PART4 + PART3 + RED_EL - 1) / RED_EL;
-        hipLaunchKernelGGL(small_finish_kernel, dim3(item_blocks + red_blocks), dim3(256), 0, s, d, item_blocks, red_blocks);
+        hipLaunchKernelGGL(small_finish_kernel, dim3(gr.item_blocks + gr.red_blocks), dim3(256), 0, s, d, gr.item_blocks, gr.red_blocks);
+    }
+    ACM_CHECK_HIP(hipGetLastError());
+    return ACM_OK;
+}
+
+extern "C" int acm_small_batch_table_bytes(int32_t n_slots, size_t* bytes) {
+    ACM_REQUIRE(bytes, ACM_EINVAL, "acm_small_batch_table_bytes: NULL argument");
+    ACM_REQUIRE(n_slots >= 1, ACM_EINVAL, "acm_small_batch_table_bytes: n_slots must be 1 .. %d (got %d)", ACM_SMALL_BATCH_MAX, (int)n_slots);
+    ACM_REQUIRE(n_slots <= ACM_SMALL_BATCH_MAX, ACM_EUNSUPPORTED, "acm_small_batch_table_bytes: n_slots %d > %d", (int)n_slots, ACM_SMALL_BATCH_MAX);
+    *bytes = (size_t)n_slots * sizeof(SmallBatchEntry);
+    return ACM_OK;
+}
+
+extern "C" int acm_small_batch_bind(const acm_csr_t* a, const acm_csr_t* x, const acm_csr_t* xt, int32_t n_slots,
+                                    const acm_small_step_t* const* slots, void* table, size_t table_bytes, acm_stream_t stream) {
+    // what needs neither a handle nor a device first (acm_small_batch_host.h): count, shared fields, overlaps
+    char msg[256];
+    const int st0 = acm_small_batch_check_slots(n_slots, slots, a ? a->n_rows : 0, msg, sizeof(msg));
+    ACM_REQUIRE(st0 == ACM_OK, st0, "%s", msg);
+    ACM_REQUIRE(table, ACM_EINVAL, "acm_small_batch_bind: NULL table");
+    ACM_REQUIRE(table_bytes >= (size_t)n_slots * sizeof(SmallBatchEntry), ACM_ESHAPE, "acm_small_batch_bind: table of %zu bytes, %zu needed",
+                table_bytes, (size_t)n_slots * sizeof(SmallBatchEntry));
+    ACM_REQUIRE(a, ACM_EINVAL, "acm_small_batch_bind: NULL operator handle");
+    std::vector<SmallBatchEntry> host((size_t)n_slots);
+    for (int i = 0; i < n_slots; ++i) {
+        SmallBatchEntry& e = host[(size_t)i];
+        e = SmallBatchEntry{};
+        const acm_small_step_t* p = slots[i];
+        if (!p) continue;
+        const int st = small_prepare(a, x, xt, p, e.first, e.rest);
+        if (st != ACM_OK) return st;
+        const Grids gr = grids_of(a, x, xt, p->train != 0);
+        const int form = form_of(p->n_channels == 4, p->relu_before != 0, p->train != 0);
+        const int gx[6] = {gr.proj, gr.wide, gr.graph, gr.graph, gr.wide, gr.item_blocks + gr.red_blocks};
+        for (int l = 0; l < 6; ++l) e.key[l] = gx[l] * 8 + form;
+        e.item_blocks = gr.item_blocks;
+        e.active = 1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ACM_CHECK_HIP(hipMemcpyAsync(table, host.data(), host.size() * sizeof(SmallBatchEntry), hipMemcpyHostToDevice, s));
+    ACM_CHECK_HIP(hipStreamSynchronize(s));         // `host` dies here: complete on return
+    return ACM_OK;
+}
+
+extern "C" int acm_small_batch_step(const acm_csr_t* a, const acm_csr_t* x, const acm_csr_t* xt, int32_t n_slots,
+                                    const acm_small_step_t* shape, const void* table, acm_stream_t stream) {
+    const int st = batch_shape_check(a, x, xt, n_slots, shape);
+    if (st != ACM_OK) return st;
+    ACM_REQUIRE(table, ACM_EINVAL, "acm_small_batch_step: NULL table");
+    const SmallBatchEntry* tb = (const SmallBatchEntry*)table;
+    hipStream_t s = (hipStream_t)stream;
+    const bool train = shape->train != 0, four = shape->n_channels == 4, variant = shape->relu_before != 0;
+    const Grids gr = grids_of(a, x, xt, train);
+    const int form = form_of(four, variant, train);
+    const unsigned B = (unsigned)n_slots;
+    const dim3 wide(gr.wide, B), graph(gr.graph, B), blk(64 * WAVES);
+    // launch 1
+    hipLaunchKernelGGL(small_proj1_batch_kernel, dim3(gr.proj, B), dim3(256), 0, s, tb, form);
+    // launch 2
+    if (four && variant) hipLaunchKernelGGL((small_conv1_fwd_batch_kernel<true, true>), wide, blk, 0, s, tb, form);
+    else if (four) hipLaunchKernelGGL((small_conv1_fwd_batch_kernel<true, false>), wide, blk, 0, s, tb, form);
+    else if (variant) hipLaunchKernelGGL((small_conv1_fwd_batch_kernel<false, true>), wide, blk, 0, s, tb, form);
+    else hipLaunchKernelGGL((small_conv1_fwd_batch_kernel<false, false>), wide, blk, 0, s, tb, form);
+    // launch 3
+    if (four) hipLaunchKernelGGL(small_conv2_fwd_batch_kernel<true>, graph, blk, 0, s, tb, form);
+    else hipLaunchKernelGGL(small_conv2_fwd_batch_kernel<false>, graph, blk, 0, s, tb, form);
+    if (train) {
+        // launch 4
+        if (four) hipLaunchKernelGGL(small_conv2_bwd_batch_kernel<true>, graph, blk, 0, s, tb, form);
+        else hipLaunchKernelGGL(small_conv2_bwd_batch_kernel<false>, graph, blk, 0, s, tb, form);
+        // launch 5
+        if (four && variant) hipLaunchKernelGGL((small_conv1_bwd_batch_kernel<true, true>), wide, blk, 0, s, tb, form);
+        else if (four) hipLaunchKernelGGL((small_conv1_bwd_batch_kernel<true, false>), wide, blk, 0, s, tb, form);
+        else if (variant) hipLaunchKernelGGL((small_conv1_bwd_batch_kernel<false, true>), wide, blk, 0, s, tb, form);
+        else hipLaunchKernelGGL((small_conv1_bwd_batch_kernel<false, false>), wide, blk, 0, s, tb, form);
+        // launch 6
+        hipLaunchKernelGGL(small_finish_batch_kernel, dim3(gr.item_blocks + gr.red_blocks, B), dim3(256), 0, s, tb, form, gr.item_blocks,
+                           gr.red_blocks);
     }
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;

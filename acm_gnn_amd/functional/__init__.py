@@ -19,7 +19,7 @@ from ._context import (CallContext, DeferredReductions, InputPipeline, Tape, Tap
 from .ops import (DropoutState, _drop_spec, agg_pad_width, bce_loss, bce_loss_and_grad, cast_bf16, dropout, eval_metrics,  # noqa: F401
                   eval_metrics_buffers, eval_rocauc, gemm, gemm_drop_supported, gemm_split, masked_bce, masked_nll, mm, nll_loss_and_grad, proj3, proj_bwd,
                   proj_bwd_supported, proj_fwd, rocauc_buffers, spmm, spmm_v)
-from .select import SelectionState, copy_if  # noqa: F401
+from .select import BatchMetrics, BatchSelection, SelectionState, copy_if  # noqa: F401
 from .linear import residual_add_linear, residual_add_supported, residual_linear, residual_mlp, residual_mlp_supported  # noqa: F401
 from .gcn import aggregate, dense_act, gcn_bwd, gcn_fwd, gcn_two_layer, gemm_act, low_t_product, mask_bwd, sparse_mm  # noqa: F401
 from ._conv_shared import AcmConfig, _flat_views, _gather_rows, _ptr_array  # noqa: F401

@@ -136,3 +136,117 @@ class SelectionState:
             for p, s in zip(self.params, self.snapshot):
                 p.copy_(s)
         return True
+
+
+def _upload(table, host):
+    """Device table <- host ctypes array (a stream-ordered copy; between two replays of a captured epoch, after the
+    synchronising look at the runs' state)."""
+    table.copy_(torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8))
+
+
+class BatchMetrics:
+    """``acm_eval_metrics`` for the slots of a batch of runs on one graph as ONE launch (acm_eval_metrics_batch): per-slot
+    logits and set weights, shared labels; results ``out[slot] = [m_tr, m_va, m_te, val_loss]`` and workspaces allocated as
+    one block.  The per-slot argument blocks live in a device table, so a captured launch survives :meth:`set_slot`."""
+
+    def __init__(self, n_slots, n_rows, n_classes, n_sets, labels, loss_set=1):
+        _check_device(labels, "labels")
+        if labels.dtype != torch.int64 or labels.dim() != 1 or labels.shape[0] != n_rows or not labels.is_contiguous():
+            raise ValueError("BatchMetrics: labels must be a contiguous int64 [n] tensor")
+        dev = labels.device
+        self.n_slots, self.n, self.c, self.k, self.loss_set = int(n_slots), int(n_rows), int(n_classes), int(n_sets), int(loss_set)
+        self.labels, self.device = labels, dev
+        from ._launch import _workspace_bytes
+        self._ws_bytes = _workspace_bytes("acm_eval_metrics_workspace_bytes", self.n, self.k)
+        self.out = torch.zeros(self.n_slots, self.k + 1, dtype=_F32, device=dev)
+        self.ws = torch.zeros(self.n_slots, (self._ws_bytes + 15) // 16 * 4, dtype=_F32, device=dev)
+        self._host = (_lib.EvalMetricsSlot * self.n_slots)()
+        self.table = torch.zeros(C.sizeof(self._host), dtype=torch.uint8, device=dev)
+        self._keep = [None] * self.n_slots
+
+    def set_slot(self, i, logits=None, weights=None):
+        """Slot ``i`` evaluates ``logits`` [n, C] on the sets ``weights`` [k, n]; None: an empty slot.  :meth:`flush` uploads."""
+        e = self._host[i]
+        if logits is None:
+            e.logits = e.weights = e.labels = e.out = e.workspace = None
+            self._keep[i] = None
+            return
+        for t, name in ((logits, "logits"), (weights, "weights")):
+            _check_device(t, name)
+        if logits.dtype != _F32 or tuple(logits.shape) != (self.n, self.c) or not logits.is_contiguous() or logits.device != self.device:
+            raise ValueError(f"BatchMetrics: logits must be contiguous fp32 [{self.n}, {self.c}] on {self.device}")
+        if weights.dtype != _F32 or tuple(weights.shape) != (self.k, self.n) or not weights.is_contiguous() or weights.device != self.device:
+            raise ValueError(f"BatchMetrics: weights must be contiguous fp32 [{self.k}, {self.n}] on {self.device}")
+        e.logits, e.weights, e.labels = logits.data_ptr(), weights.data_ptr(), self.labels.data_ptr()
+        e.out, e.workspace = self.out[i].data_ptr(), self.ws[i].data_ptr()
+        self._keep[i] = (logits, weights)
+
+    def flush(self):
+        _upload(self.table, self._host)
+
+    def launch(self):
+        launch("acm_eval_metrics_batch", f"eval_metrics_batch/{self.n}x{self.c}k{self.k}b{self.n_slots}", self.device, self.n, self.c,
+               self.c, self.n, self.k, self.loss_set, self.n_slots, _vp(self.table), self._ws_bytes)
+        return self.out
+
+
+class BatchSelection:
+    """:class:`SelectionState` for the slots of a batch of runs: ``ctrl`` int32[B, 8], ``best`` float64[B, 2], ``history``
+    float64[B, epochs, 5] allocated as one block each, folded by ONE launch per epoch (acm_select_step_batch: one block per
+    slot, each the single kernel), looked at with ONE device-to-host copy (:meth:`poll`)."""
+
+    def __init__(self, rule, early_stopping, epochs, n_slots, device):
+        if rule not in RULES:
+            raise ValueError(f"rule must be one of {RULES}, not {rule!r}")
+        if int(epochs) < 1 or int(early_stopping) < 0:
+            raise ValueError("BatchSelection: epochs must be >= 1 and early_stopping >= 0")
+        self.rule, self.early_stopping, self.epochs = RULES.index(rule), int(early_stopping), int(epochs)
+        self.n_slots, self.device = int(n_slots), torch.device(device)
+        self.ctrl = torch.zeros(self.n_slots, 8, dtype=torch.int32, device=self.device)
+        self.best = torch.zeros(self.n_slots, 2, dtype=torch.float64, device=self.device)
+        self.history = torch.zeros(self.n_slots, self.epochs, 5, dtype=torch.float64, device=self.device)
+        self._ctrl0 = torch.tensor([0, 0, -1, 0, 0, 0, 0, 0], dtype=torch.int32, device=self.device)
+        self._host = (_lib.Select * self.n_slots)()
+        self.table = torch.zeros(C.sizeof(self._host), dtype=torch.uint8, device=self.device)
+        self._keep = [None] * self.n_slots
+
+    def reset(self, i):
+        """Slot ``i`` back to the start of a run (torch copies: not capturable)."""
+        self.ctrl[i].copy_(self._ctrl0)
+        self.best[i].zero_()
+
+    def set_slot(self, i, train_loss=None, result=None):
+        """Slot ``i`` folds (``train_loss`` fp32 scalar, ``result`` fp32 [4]) from the start of a run; None: an empty slot."""
+        e = self._host[i]
+        self.reset(i)
+        if train_loss is None:
+            e.result = e.result_f64 = e.train_loss = e.ctrl = e.best = e.history = None
+            self._keep[i] = None
+            return
+        for t, name in ((train_loss, "train_loss"), (result, "result")):
+            _check_device(t, name)
+            if t.device != self.device or not t.is_contiguous() or t.dtype != _F32:
+                raise ValueError(f"BatchSelection: {name} must be contiguous fp32 on {self.device}")
+        if train_loss.numel() != 1 or result.numel() != 4:
+            raise ValueError("BatchSelection: train_loss is one scalar, result holds four numbers")
+        e.rule, e.early_stopping, e.epochs = self.rule, self.early_stopping, self.epochs
+        e.result, e.result_f64, e.train_loss = result.data_ptr(), None, train_loss.data_ptr()
+        e.ctrl, e.best, e.history = self.ctrl[i].data_ptr(), self.best[i].data_ptr(), self.history[i].data_ptr()
+        self._keep[i] = (train_loss, result)
+
+    def flush(self):
+        _upload(self.table, self._host)
+
+    def launch(self):
+        launch("acm_select_step_batch", f"select_step_batch/{self.n_slots}", self.device, self.n_slots, _vp(self.table))
+
+    def poll(self):
+        """[(epoch, stopped)] of every slot: ONE device-to-host copy, which waits for what was enqueued on the current stream."""
+        return [(c[_CTRL_EPOCH], bool(c[_CTRL_STOPPED])) for c in self.ctrl.tolist()]
+
+    def result(self, i):
+        """(selected, history rows, best_epoch) of slot ``i``, as :meth:`SelectionState.result`."""
+        ctrl = self.ctrl[i].tolist()
+        selected = self.best[i].tolist()[1]
+        rows = [tuple(r) for r in self.history[i, :ctrl[_CTRL_EPOCH]].tolist()]
+        return selected, rows, ctrl[_CTRL_BEST_EPOCH]

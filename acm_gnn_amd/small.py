@@ -176,7 +176,13 @@ class SmallPlan:
         p.x_vals = x.values.data_ptr()
         if self._xt is not None:
             p.xt_src_pos = self._xt._src_pos_ptr
-            self.xt_vals = x.values.index_select(0, self._xt.src_pos)      # the (static) values in the transposed order
+            # the (static) values in the transposed order: made once per feature object and shared by its plans (the slots of
+            # a SmallBatch must name the same buffer), remade when the values were replaced or edited in place
+            key = (x.values.data_ptr(), x.values._version)
+            held = x.__dict__.get("_small_xt_vals")
+            if held is None or held[0] != key:
+                held = x.__dict__["_small_xt_vals"] = (key, x.values.index_select(0, self._xt.src_pos))
+            self.xt_vals = held[1]
             p.xt_vals = self.xt_vals.data_ptr()
         p.row_scale = ops.row_scale.data_ptr()
         p.logits, p.att1, p.att2, p.loss = self.logits.data_ptr(), self.att1.data_ptr(), self.att2.data_ptr(), self.loss.data_ptr()
@@ -276,3 +282,118 @@ class SmallPlan:
         for layer, att in ((l0, self.att1), (l1, self.att2)):
             layer._att_raw, layer._att_inv, layer._att_k = att, None, self.cfg.n_channels
         return self.loss if self.train else self.logits
+
+
+class SmallBatch:
+    """B <= 32 :class:`SmallPlan` s over the SAME feature and operator objects -- all training plans or all evaluation plans --
+    whose steps go through ONE set of six (three) launches (``acm_small_batch_step``): grid row k is plan k's single step, bit
+    for bit.  The runs of the reference's ten-split loop (ACM-Pytorch/train.py:49-139) and of its hyper-parameter grid
+    (hyperparameter_searching.py:51-70) share the graph and the features and nothing else: ``lr``, ``betas``, ``eps``,
+    ``weight_decay``, Adam or AdamW, the dropout probability and the dropout state are per slot.
+
+    The per-slot arguments live in a device table this object owns.  ``run()`` is one C call; it binds the table again first
+    (``acm_small_batch_bind``) when a plan is ``stale()`` or a plan's hyper-parameters changed -- the ``refresh_hyper`` rule of
+    the single plan: read on every eager call, baked at capture.  ``set_slot(i, plan_or_None)`` hands a slot to another run
+    (None: an empty slot, which every launch skips); a captured ``run()`` keeps replaying, the table's address is all it
+    baked in."""
+
+    @staticmethod
+    def why_not(plans):
+        """None if the plans can share launches, else the first reason they cannot (a string)."""
+        plans = [p for p in plans if p is not None]
+        if not plans:
+            return "no plan"
+        if len(plans) > _lib.SMALL_BATCH_MAX:
+            return f"{len(plans)} plans (<= {_lib.SMALL_BATCH_MAX} slots)"
+        first = plans[0]
+        for p in plans[1:]:
+            if (p.cfg.n_channels, p.cfg.relu_before, p.cfg.layernorm, p.cfg.scale) != \
+                    (first.cfg.n_channels, first.cfg.relu_before, first.cfg.layernorm, first.cfg.scale):
+                return "the models are configured differently"
+            if p.C != first.C:
+                return f"{p.C} and {first.C} classes"
+            if p.x is not first.x:
+                return "different feature objects"
+            if p.ops is not first.ops or p.low is not first.low:
+                return "different operator objects"
+            if (p.train, p.update) != (first.train, first.update):
+                return "training and evaluation plans (or updating and gradient-only plans) mixed"
+        return None
+
+    def __init__(self, plans, n_slots=None):
+        why = self.why_not(plans)
+        if why is not None:
+            raise ValueError(f"SmallBatch: {why}")
+        lib = _lib.load()
+        self.n_slots = int(n_slots) if n_slots is not None else len(plans)
+        if not 1 <= self.n_slots <= _lib.SMALL_BATCH_MAX or len(plans) > self.n_slots:
+            raise ValueError(f"SmallBatch: {len(plans)} plans in {self.n_slots} slots (1 .. {_lib.SMALL_BATCH_MAX})")
+        self.plans = list(plans) + [None] * (self.n_slots - len(plans))
+        first = self._first()
+        self.low, self.x, self._xt, self.train = first.low, first.x, first._xt, first.train
+        nbytes = C.c_size_t()
+        _lib.check(lib.acm_small_batch_table_bytes(self.n_slots, C.byref(nbytes)), "acm_small_batch_table_bytes")
+        self.table = torch.zeros(nbytes.value, dtype=torch.uint8, device=first.logits.device)     # zero: every slot empty
+        self._slots = (C.POINTER(_lib.SmallStep) * self.n_slots)()
+        self._bound = None
+
+    def _first(self):
+        return next(p for p in self.plans if p is not None)
+
+    def set_slot(self, i, plan):
+        """Slot ``i`` belongs to ``plan`` from the next ``run()`` / replay on (None: empty).  Table bytes only: call it when
+        nothing that reads the table is in flight (after the synchronising look at the runs' state)."""
+        if plan is not None:
+            others = [p for k, p in enumerate(self.plans) if k != i and p is not None]
+            why = self.why_not(others[:1] + [plan])
+            if why is not None:
+                raise ValueError(f"SmallBatch.set_slot: {why}")
+        self.plans[i] = plan
+        if any(p is not None for p in self.plans):
+            self.bind()
+        else:
+            self.table.zero_()
+            self._bound = None
+
+    def _state(self):
+        return tuple(bytes(p.p) if p is not None else None for p in self.plans)
+
+    def bind(self):
+        """Write the table from the plans as they are now (not capturable)."""
+        for i, p in enumerate(self.plans):
+            if p is not None:
+                if p.stale():
+                    p._bind_parameters()
+                p.refresh_hyper()
+                l0, l1 = p.model.gcns
+                for layer, att in ((l0, p.att1), (l1, p.att2)):
+                    layer._att_raw, layer._att_inv, layer._att_k = att, None, p.cfg.n_channels
+            self._slots[i] = C.pointer(p.p) if p is not None else None
+        dev = self.table.device
+        with _device_ctx(dev):
+            st = _lib.load().acm_small_batch_bind(self.low.handle, self.x.csr.handle, self._xt.handle if self._xt is not None else None,
+                                                  self.n_slots, self._slots, self.table.data_ptr(), self.table.numel(), _stream())
+        _lib.check(st, "acm_small_batch_bind")
+        self._bound = self._state()
+
+    def _changed(self):
+        for p in self.plans:
+            if p is not None:
+                if p.stale():
+                    return True
+                p.refresh_hyper()
+        return self._bound is None or self._state() != self._bound
+
+    def run(self):
+        """One call = every slot's step (training plans) or forward (evaluation plans).  Results are in the plans' own
+        buffers (``plan.loss`` / ``plan.logits``)."""
+        capturing = self.table.is_cuda and torch.cuda.is_current_stream_capturing()
+        if not capturing and self._changed():
+            self.bind()
+        if self._bound is None:
+            raise RuntimeError("SmallBatch.run: bind() the table before capturing a run")
+        from .functional import _Timed
+        with _device_ctx(self.table.device), _Timed("small_batch_step" if self.train else "small_batch_forward"):
+            st = _lib.load().acm_small_batch_step(self.low.handle, self.x.csr.handle, self._xt.handle if self._xt is not None else None,
+                                                  self.n_slots, C.byref(self._first().p), self.table.data_ptr(), _stream())
+        _lib.check(st, "acm_small_batch_step")

@@ -912,3 +912,191 @@ def fit_concurrent(runs, x, adj, labels, epochs, rule="min_val_loss", early_stop
                 results[sl["k"]] = (sl["selected"], sl["history"])
                 slots[i] = None
     return results
+
+
+# The smallest measured batch size within 3 % of the best one on the Squirrel-shaped workload (scripts/bench_batched_fit.py on
+# the MI355X, profiles/batched_fit.jsonl; EXPERIMENTS.md "A batch of runs in the same six launches" has the table).
+DEFAULT_BATCH = 8
+
+
+class _BatchedSlotRun:
+    """One run of ``fit_batched`` while it holds a slot: its (un-captured) training step and evaluation pass objects -- made
+    exactly as ``fit`` makes them, so the run's plans, optimizer state and dropout state are what ``fit`` would train."""
+
+    def __init__(self, k, run, x, adj, labels, fused_dropout):
+        model, opt, tr, va, te = run
+        self.k, self.model, self.enqueued = k, model, 0
+        w = row_weights(tr, x.shape[0], device=labels.device)
+        self.step = TrainStep(model, opt, x, adj, labels, w, use_graph=False, fused_dropout=fused_dropout)
+        self.ev = EvalStep(model, x, adj, labels, (tr, va, te), loss_set=1, use_graph=False)
+        self.refused = self.step.small_refused or self.ev.small_refused
+
+
+def fit_batched(runs, x, adj, labels, epochs, rule="min_val_loss", early_stopping=0, batch=DEFAULT_BATCH, sync_every=32,
+                fused_dropout=None, keep_best=False, criterion="nll", metric="acc"):
+    """Several independent training runs on the same small graph -- the reference's ten splits (ACM-Pytorch/train.py:49-139),
+    or the learning-rate x weight-decay x dropout grid of its hyperparameter_searching.py:51-70 -- ``batch`` at a time IN THE
+    SAME LAUNCHES: one captured epoch graph holds the batched six-launch step (small.SmallBatch: grid row = run), the batched
+    evaluation forward, the batched metrics and the batched selection, 11 launches per epoch whatever ``batch`` is (streams,
+    ``fit_concurrent``, cannot remove launches; they saturate at two runs).
+
+    ``runs``: ``[(model, optimizer, train_idx, val_idx, test_idx)]`` as in ``fit_concurrent``; per run the learning rate, betas,
+    eps, weight decay, Adam or AdamW, dropout probability and dropout state may differ freely.  Returns ``[(selected,
+    history)]`` in the order of ``runs``; each equals ``fit(..., use_graph=True, sync_every=sync_every)`` of that run alone,
+    bit for bit (a grid row executes the single step's instructions in the single step's order).  The graph is replayed
+    ``sync_every`` times, then ONE device-to-host copy reads every slot's selection state; runs that stopped or used their
+    budget up hand their slot to the next pending run by table writes -- nothing is re-captured.  A stopped run's state is
+    frozen on the device while its slot keeps stepping until that look (as with ``fit(sync_every > 1)``).
+
+    ``batch``: slots (1 .. 32).  Default 8: the smallest measured size within 3 % of the best size on the Squirrel-shaped
+    workload (scripts/bench_batched_fit.py, profiles/batched_fit.jsonl).
+
+    Where ``SmallPlan.why_not`` or ``SmallBatch.why_not`` objects (a model outside the small-graph envelope, runs that differ in
+    configuration) the call is ``fit_concurrent(..., sync_every=sync_every)`` and the reason is left in
+    ``fit_batched.last_refusal`` (None otherwise).  ``keep_best=True``, ``criterion="bce"`` and ``metric="rocauc"`` are not
+    implemented here: use ``fit_concurrent``."""
+    from .small import SmallBatch
+    if keep_best or criterion != "nll" or metric != "acc":
+        raise NotImplementedError('fit_batched: keep_best=True, criterion="bce" and metric="rocauc" are not implemented for the '
+                                  "batched loop; use fit_concurrent")
+    _resident_loop(sync_every, False)
+    batch = int(batch)
+    if not 1 <= batch <= _lib_batch_max():
+        raise ValueError(f"fit_batched: batch must be 1 .. {_lib_batch_max()}, not {batch}")
+    fit_batched.last_refusal = None
+    if int(epochs) < 1 or not runs:
+        return [(0.0, []) for _ in runs]
+
+    def fallback(why):
+        fit_batched.last_refusal = why
+        return fit_concurrent(runs, x, adj, labels, epochs, rule=rule, early_stopping=early_stopping, fused_dropout=fused_dropout,
+                              sync_every=sync_every)
+
+    if _is_sharded(adj):
+        return fallback("row-sharded operators")
+    # one operator set and one feature object for every run (TrainStep would build them per run: the plans must SHARE them)
+    ops = adj
+    if not isinstance(adj, FilterOperators) and isinstance(adj, torch.Tensor) and hasattr(runs[0][0], "structure_info"):
+        m0 = runs[0][0]
+        four = m0.structure_info and getattr(m0, "model_type", "") in ("acmgcnp", "acmgcnpp")
+        ops = operators_for(adj, None, adj if four else None)
+    xs = runs[0][0].auto_csr(x, ops if isinstance(ops, FilterOperators) else None) if hasattr(runs[0][0], "auto_csr") else x
+    # every run against the envelope before anything is built: the fallback is decided here, not in the middle of the loop
+    from .small import SmallPlan
+    shape0 = None
+    for k, (model, opt, _, _, _) in enumerate(runs):
+        why = SmallPlan.why_not(model, xs, ops, opt, need_dropout_state=False)
+        if why is None:
+            cfg = model.gcns[0]._config()
+            shape = (cfg.n_channels, cfg.relu_before, cfg.layernorm, cfg.scale, model.gcns[1].out_features)
+            shape0 = shape if shape0 is None else shape0
+            if shape != shape0:
+                why = "the models are configured differently"
+        if why is not None:
+            return fallback(f"run {k}: {why}")
+    n_slots = min(batch, len(runs))
+    dev = labels.device
+    pending = list(range(len(runs)))
+    results = [None] * len(runs)
+    live = [None] * n_slots
+
+    def enter(k):
+        return _BatchedSlotRun(k, runs[k], xs, ops, labels, fused_dropout)
+
+    first = [enter(pending.pop(0)) for _ in range(n_slots)]
+    why = next((r.refused for r in first if r.refused), None) or SmallBatch.why_not([r.step.small for r in first]) \
+        or SmallBatch.why_not([r.ev.small for r in first])
+    if why is not None:
+        return fallback(why)
+    for i, r in enumerate(first):
+        live[i] = r
+    train_b = SmallBatch([r.step.small for r in first], n_slots)
+    eval_b = SmallBatch([r.ev.small for r in first], n_slots)
+    n, n_classes = first[0].step.small.n, first[0].step.small.C
+    metrics = AF.BatchMetrics(n_slots, n, n_classes, 3, first[0].ev.labels, loss_set=1)
+    select = AF.BatchSelection(rule, early_stopping, epochs, n_slots, dev)
+
+    def bind_slot(i, r):
+        if r is None:
+            metrics.set_slot(i)
+            select.set_slot(i)
+        else:
+            metrics.set_slot(i, r.ev.small.logits, r.ev.w)
+            select.set_slot(i, r.step.small.loss, metrics.out[i])
+
+    def epoch():
+        train_b.run()
+        eval_b.run()
+        metrics.launch()
+        select.launch()
+
+    for i, r in enumerate(live):
+        bind_slot(i, r)
+    metrics.flush(), select.flush()
+    train_b.bind(), eval_b.bind()
+    graph = None
+    if labels.is_cuda:
+        # as TrainStep._capture: warm up on a snapshot of every run in a slot, put it back, then capture -- no run sees the
+        # warm-up steps; the selection states are reset (the warm-up folded epochs in)
+        snaps = [r.step._snapshot() for r in live]
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                epoch()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        for r, snap in zip(live, snaps):
+            r.step._restore(snap)
+        for i in range(n_slots):
+            select.reset(i)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, **_capture_mode()):
+            epoch()
+    while any(r is not None for r in live):
+        todo = min(int(sync_every), max(int(epochs) - r.enqueued for r in live if r is not None))
+        for _ in range(todo):
+            if graph is not None:
+                graph.replay()
+            else:
+                epoch()
+        for r in live:
+            if r is not None:
+                r.enqueued += todo
+                ds = getattr(r.model, "dropout_state", None)
+                if ds is not None and r.step.small.update:
+                    ds.host_steps += todo
+        state = select.poll()                          # the ONE synchronising copy of the look
+        changed = False
+        for i, r in enumerate(live):
+            if r is None:
+                continue
+            _, stopped = state[i]
+            if stopped or r.enqueued >= int(epochs):
+                selected, history, _ = select.result(i)
+                results[r.k] = (selected, history)
+                r.model.eval()
+                live[i] = enter(pending.pop(0)) if pending else None
+                nxt = live[i]
+                if nxt is not None:
+                    why = nxt.refused or SmallBatch.why_not([train_b._first(), nxt.step.small]) \
+                        or SmallBatch.why_not([eval_b._first(), nxt.ev.small])
+                    if why is not None:
+                        raise RuntimeError(f"fit_batched: run {nxt.k} cannot share the launches of the runs before it ({why}); "
+                                           "sort such runs into calls of their own")
+                train_b.set_slot(i, nxt.step.small if nxt is not None else None)
+                eval_b.set_slot(i, nxt.ev.small if nxt is not None else None)
+                bind_slot(i, nxt)
+                changed = True
+        if changed:
+            metrics.flush(), select.flush()
+    return results
+
+
+fit_batched.last_refusal = None
+
+
+def _lib_batch_max():
+    from . import _lib
+    return _lib.SMALL_BATCH_MAX

@@ -858,6 +858,24 @@ int acm_eval_metrics(int64_t n_rows, int n_classes, const float* logits, int64_t
                      const float* weights, int64_t ld_weights, int n_sets, int loss_set, float* out,
                      void* workspace, size_t workspace_bytes, acm_stream_t stream);
 
+/* The same for a BATCH of runs on one graph (added under ABI 29; the evaluation of every split of ACM-Pytorch/train.py:49-139
+ * and of every grid point of hyperparameter_searching.py:51-70 behind acm_small_batch_step's evaluation forward) as ONE
+ * launch whose grid is (acm_eval_metrics' grid, n_slots).  `table`: DEVICE array of n_slots blocks, read by the kernel (a
+ * captured call survives a slot changing hands: only table bytes change); a block with logits == NULL is an empty slot (its
+ * grid row returns at once).  Grid row k runs acm_eval_metrics' kernel on block k: the same per-block partials, the same
+ * tree, bit-identical results.  Sizes and pitches are shared by all slots; `workspace_bytes` is what the caller vouches for
+ * per slot (checked against acm_eval_metrics_workspace_bytes), every slot's workspace zero-initialised once. */
+typedef struct {
+    const float*   logits;       /* [n_rows, ld_logits]; NULL: empty slot */
+    const float*   weights;      /* [n_sets, ld_weights]                 */
+    const int64_t* labels;       /* [n_rows]                             */
+    float*         out;          /* [n_sets + 1]                         */
+    void*          workspace;
+} acm_eval_metrics_slot_t;
+
+int acm_eval_metrics_batch(int64_t n_rows, int n_classes, int64_t ld_logits, int64_t ld_weights, int n_sets, int loss_set,
+                           int32_t n_slots, const acm_eval_metrics_slot_t* table, size_t workspace_bytes, acm_stream_t stream);
+
 /* ------------------------------------------------ masked BCE-with-logits (ABI 29) --
  * The reference's second protocol (genius, twitch-e, yelp-chi, --rocauc): nn.BCEWithLogitsLoss() on the one-hot labels,
  *     true_label = F.one_hot(label, label.max() + 1).squeeze(1);  loss = criterion(out[train_idx], true_label[train_idx].float())
@@ -1042,6 +1060,38 @@ int acm_small_step_workspace_bytes(const acm_csr_t* a_low, const acm_csr_t* x, c
  * train = 0).  Errors: ACM_EUNSUPPORTED outside the envelope (explicit values, > 8 classes, > 16384 rows, ...). */
 int acm_small_step(const acm_csr_t* a_low, const acm_csr_t* x, const acm_csr_t* x_t, const acm_small_step_t* p,
                    acm_stream_t stream);
+
+/* ------------------------------------- a BATCH of small-graph runs in the same six launches (added under ABI 29) --
+ * The workload on these graphs is never one run: ACM-Pytorch/train.py:49-139 trains ten splits of up to 5 000 epochs each
+ * with a fresh model per split, and ACM-Pytorch/hyperparameter_searching.py:51-70 wraps that in a grid of 3 learning rates x
+ * 9 weight decays x 10 dropouts -- 2 700 runs on the same graph and the same features.  Here B <= ACM_SMALL_BATCH_MAX such
+ * runs go through ONE set of six (train = 0: three) launches whose grid is (the single step's grid, n_slots): grid row k
+ * executes, instruction for instruction, the single step of slot k, on slot k's own parameters, optimizer state, labels, row
+ * weights, dropout specification, hyper-parameters, workspace and outputs -- so slot k is bit for bit acm_small_step on the
+ * same inputs.  No state is shared between slots but the read-only operator, features and row scale.
+ *
+ * The per-slot arguments live in a DEVICE table (acm_small_batch_table_bytes), not in the kernel arguments: a captured call
+ * bakes in the table's address only, so a slot can be handed to another run between two replays by writing table bytes
+ * (acm_small_batch_bind again) -- nothing is re-captured.  An EMPTY slot (NULL in `slots`) returns at once in every launch
+ * and touches no memory but its table entry.
+ *
+ * acm_small_batch_bind   validates every active slot exactly as acm_small_step does, requires the fields that choose the
+ *                        kernels and the grids to agree across slots (n_classes, n_channels, relu_before, layernorm, train,
+ *                        update, f_in, x_vals / xt_vals / xt_src_pos / row_scale), refuses two active slots whose workspace,
+ *                        logits or loss ranges overlap, and writes the table (a copy ordered on `stream`, complete on return:
+ *                        NOT capturable).  `slots`: HOST array of n_slots pointers.  The table also records the grids and
+ *                        the kernel form it was bound for: a grid row whose launch does not match them does nothing.
+ * acm_small_batch_step   launches only (capturable).  `shape`: any active slot's block, read for the shared fields alone.
+ *                        The handles must be those of the bind.
+ * Errors (all before any launch): ACM_EINVAL NULL argument / n_slots < 1 / every slot empty / slots that disagree or overlap
+ * / what acm_small_step objects to; ACM_EUNSUPPORTED n_slots > ACM_SMALL_BATCH_MAX or outside acm_small_step's envelope;
+ * ACM_ESHAPE table_bytes or a workspace too small. */
+#define ACM_SMALL_BATCH_MAX 32
+int acm_small_batch_table_bytes(int32_t n_slots, size_t* bytes);
+int acm_small_batch_bind(const acm_csr_t* a_low, const acm_csr_t* x, const acm_csr_t* x_t, int32_t n_slots,
+                         const acm_small_step_t* const* slots, void* table, size_t table_bytes, acm_stream_t stream);
+int acm_small_batch_step(const acm_csr_t* a_low, const acm_csr_t* x, const acm_csr_t* x_t, int32_t n_slots,
+                         const acm_small_step_t* shape, const void* table, acm_stream_t stream);
 
 /* ------------------------------------- homophily measures on the device (added under ABI 29) --
  * synthetic-experiments/homophily.py without its dense n x n matrices (label @ label.T at :16, A.nonzero() at :31 / :44 /
@@ -1292,6 +1342,13 @@ typedef struct {
 } acm_select_t;
 
 int acm_select_step(const acm_select_t* p, acm_stream_t stream);
+
+/* acm_select_step for a BATCH of runs (the bookkeeping of every split of ACM-Pytorch/train.py:49-139 and every grid point of
+ * hyperparameter_searching.py:51-70 in one launch): one 64-lane block per slot, block k on table[k].  `table`: DEVICE array
+ * of n_slots acm_select_t, read by the kernel (so the caller validates the blocks as acm_select_step would before writing
+ * them); a block whose `result` and `result_f64` are both NULL is an empty slot.  Each block is acm_select_step's kernel:
+ * bit-identical state.  n_slots 1 .. ACM_SMALL_BATCH_MAX. */
+int acm_select_step_batch(int32_t n_slots, const acm_select_t* table, acm_stream_t stream);
 
 /* dst[i] = src[i] (as bits: NaN payloads and -0.0 survive) for every tensor of the table if *flag != 0; nothing is read or
  * written otherwise (`flag` is device memory, read once per block: acm_select_t.ctrl + 3 makes the copy "snapshot the
