@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = (
     "acm_select_step", "acm_copy_if",
     "acm_small_batch_table_bytes", "acm_small_batch_bind", "acm_small_batch_step", "acm_eval_metrics_batch", "acm_select_step_batch",
     "acm_bnorm_stats_workspace_bytes", "acm_bnorm_stats", "acm_bnorm_fold", "acm_bnorm_param_bwd", "acm_bnorm_bwd_workspace_bytes", "acm_bnorm_bwd",
+    "acm_proj_blocks_fwd", "acm_proj_blocks_bwd_workspace_bytes", "acm_proj_blocks_bwd",
 )
 
 
@@ -197,6 +198,17 @@ class ReduceList(C.Structure):
     _fields_ = [("n", C.c_int32), ("cap", C.c_int32), ("segs", C.POINTER(ReduceSeg))]
 
 
+PROJ_BLOCKS_MAX = 8
+
+
+class ProjBlocks(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("f", C.c_int32), ("f_block", C.c_int32), ("f_in", C.c_int32),
+                ("w_low", C.c_void_p), ("w_high", C.c_void_p), ("w_mlp", C.c_void_p), ("ldw", C.c_int64),
+                ("h", C.c_void_p * PROJ_BLOCKS_MAX), ("ld_h", C.c_int64 * PROJ_BLOCKS_MAX),
+                ("width", C.c_int32 * PROJ_BLOCKS_MAX), ("row0", C.c_int32 * PROJ_BLOCKS_MAX),
+                ("d_h", C.c_void_p * PROJ_BLOCKS_MAX), ("ld_dh", C.c_int64 * PROJ_BLOCKS_MAX)]
+
+
 class SpmmOpts(C.Structure):
     _fields_ = [("vals", C.c_void_p), ("row_scale", C.c_void_p), ("sub", C.c_void_p), ("ld_sub", C.c_int64),
                 ("sub_scale", C.c_void_p), ("relu", C.c_int32), ("g_bf16", C.c_int32)]
@@ -303,6 +315,9 @@ def _declare(lib):
     lib.acm_proj_fwd.argtypes = [i64, i64, i32, vp, i64, vp, vp, vp, i64, i32, vp, i64, vp, i64, vp]
     lib.acm_proj_fwd_at.argtypes = [i64, i64, i32, vp, i64, vp, vp, vp, i64, i32, vp, i64, i64, vp, i64, vp]
     lib.acm_proj_bwd.argtypes = [i64, i64, i32, vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, i64, i64, vp, sz, vp, vp]
+    lib.acm_proj_blocks_fwd.argtypes = [i64, C.POINTER(ProjBlocks), vp, i64, i32, i32, vp]
+    lib.acm_proj_blocks_bwd_workspace_bytes.argtypes = [i64, C.POINTER(ProjBlocks), C.POINTER(sz)]
+    lib.acm_proj_blocks_bwd.argtypes = [i64, C.POINTER(ProjBlocks), vp, i64, vp, i64, i64, i64, vp, sz, vp, vp]
     lib.acm_gemm_split.argtypes = [i32, i32, i64, i64, i64, vp, i64, vp, i64, vp, i64, i64, vp, i64, i32, vp, sz, vp]
     lib.acm_gemm_blocks.argtypes = [i32, i32, i64, i64, i64, vp, i64, vp, i64, vp, i64, i64, i64, i32, vp, sz, vp]
     lib.acm_gemm_drop.argtypes = [i32, i32, i64, i64, i64, vp, i64, vp, i64, vp, i64, i64, i64, i32, C.POINTER(Dropout), vp, sz, vp]

@@ -9,7 +9,7 @@ Beside the three device seams (``_device_ctx`` / ``_require_cuda`` / ``_stream``
 time, so that a test double replaces them in one place) and ``_gather_rows`` (the routes call it through this namespace, where
 a test counts halo exchanges), this file only re-exports what the project and the tests reach as ``functional.NAME``: ``_launch`` (the launch block, its
 timing and argument marshalling), ``_context`` (step- and call-scoped state), ``ops`` (single-kernel operators), ``select`` (a run's selection state on the device), ``linear`` (the
-residual branch), ``gcn`` (the one-channel layers of the study's baselines), ``conv`` (the layer's entry point) over ``_conv_shared``, ``conv_agg`` and ``conv_literal`` (its four routes).
+residual branch), ``gcn`` (the one-channel layers of the study's baselines), ``blocks`` (the projection of a block input), ``conv`` (the layer's entry point) over ``_conv_shared``, ``conv_agg`` and ``conv_literal`` (its four routes).
 """
 from .. import _lib, tuning  # noqa: F401
 from ..graph import CsrGraph, FilterOperators, SparseFeatures, _device_ctx, _require_cuda, _stream  # noqa: F401  (the seams)
@@ -25,4 +25,5 @@ from .gcn import aggregate, dense_act, gcn_bwd, gcn_fwd, gcn_two_layer, gemm_act
 from ._conv_shared import AcmConfig, _flat_views, _gather_rows, _ptr_array  # noqa: F401
 from .conv_agg import AGG_WIDE_MIN_DEGREE, _AcmAggWide, agg_wide_supported  # noqa: F401
 from .conv_literal import _AcmAcmii  # noqa: F401
+from .blocks import check_blocks, project_blocks  # noqa: F401
 from .conv import _conv_route, acm_conv, in_drop_supported  # noqa: F401

@@ -9,7 +9,7 @@ from .. import _lib
 from .. import functional as _pkg            # (_gather_rows is called through the package, where tests replace it)
 from ..graph import SparseFeatures
 from ._context import _call_or_ambient, _sum_over_ranks
-from ._launch import _F32, _Timed, _as_f32c, _vp, launch
+from ._launch import _F32, _Timed, _as_f32_rows, _as_f32c, _vp, launch
 from .ops import _drop_now, _drop_spec, cast_bf16, spmm
 
 
@@ -115,6 +115,16 @@ def _chan_block(f):
     return f
 
 
+def _z_pitch(f, fb):
+    """Row pitch of the one-table Z = [Z_L | Z_H | Z_I]: for narrow layers the gathered block [Z_L | Z_H] (2F floats) must be one
+    aligned vector fetch, so rows are padded to a multiple of that block."""
+    if f in (2, 4, 8):
+        return -(-3 * f // (2 * f)) * (2 * f)
+    if fb != f:
+        return -(-(2 * fb + f) // 4) * 4
+    return 3 * f
+
+
 def _narrow_tables(n, fb, f, dev, packed):
     """The gathered tables of a narrow layer: ([c0 | c1] block rows, third-channel rows or None).  ``packed`` (four channels
     of two columns: the output layer of a two-class model with structure_info): views of ONE table of 32-byte rows
@@ -201,6 +211,7 @@ def _struc_grad(ops, cfg, gs):
 
 
 _NONE4 = (None,) * 4
+PROJECTED = object()              # in the layer Functions' ``pregathered`` slot: ``x`` is the projection Z of a block input
 _NO_GRADS = (None,) * 28          # one per argument of the layer Functions (see acm_conv)
 
 
@@ -253,8 +264,9 @@ def _k3_setup(cfg, ops, k, f, n, dev, f_in_w, pre, zi, vecs, lnw, lnb, mix, grad
                 general=general, ones=ones, grad_out=grad_out)
 
 
-def _conv_prologue(ctx, x, w_low, ops, post_relu, post_scale, post_drop, call, in_drop):
+def _conv_prologue(ctx, x, w_low, ops, post_relu, post_scale, post_drop, call, in_drop, projected=False):
     """What the narrow forms (aggregate-first, ACMII, literal) check and record first; returns the input as float32.
+    ``projected``: ``x`` is the projection Z of a block input (functional.blocks), not the layer's input: no width check.
 
     ``call``: the model call's context (deferral list, loss-tail request, input pipeline, projection hand-off);
     ``in_drop = (p, tag, DropoutState)``: the caller's INPUT dropout (models.py:54), left to this layer -- the forms that gather
@@ -264,7 +276,7 @@ def _conv_prologue(ctx, x, w_low, ops, post_relu, post_scale, post_drop, call, i
     ctx.in_drop = in_drop if (in_drop is not None and in_drop[0] > 0) else None
     sparse_x = isinstance(x, SparseFeatures)
     if not sparse_x:
-        x = _as_f32c(x, "input")
+        x = _as_f32_rows(x, "input") if projected else _as_f32c(x, "input")      # (Z keeps its row pitch)
     n, f = x.shape[0], w_low.shape[1]
     if post_scale is not None:
         post_scale = _as_f32c(post_scale, "post_scale")
@@ -275,7 +287,7 @@ def _conv_prologue(ctx, x, w_low, ops, post_relu, post_scale, post_drop, call, i
     if n != ops.n_local:
         raise ValueError(f"input has {n} rows but the graph operator has {ops.n_local}")
     ctx.x_width = x.shape[1]
-    if x.shape[1] != w_low.shape[0] and (sparse_x or x.shape[1] < w_low.shape[0]):   # (dropout(..., pad_to=...): zero columns)
+    if not projected and x.shape[1] != w_low.shape[0] and (sparse_x or x.shape[1] < w_low.shape[0]):   # (dropout(..., pad_to=...): zero columns)
         raise ValueError(f"input has {x.shape[1]} columns but the weights have {w_low.shape[0]} rows")
     return x
 

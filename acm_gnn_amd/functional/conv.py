@@ -4,8 +4,9 @@ import torch
 
 from .. import tuning
 from ..graph import SparseFeatures
-from ._context import _run
-from ._conv_shared import _chan_block
+from ._context import _call_or_ambient, _run
+from .blocks import project_blocks
+from ._conv_shared import PROJECTED, _chan_block
 from ._launch import _F32
 from .conv_agg import _AcmAggFirst, _AcmAggWide, agg_wide_supported
 from .conv_literal import _AcmAcmii, _AcmLiteral
@@ -70,10 +71,24 @@ def acm_conv(x, params, ops, cfg, post_relu=False, post_scale=None, post_drop=No
     call: the model call's CallContext (default: the thread's ambient one); tail_layer: the caller is an output layer without
     post-op working in the operator's numbering (it may take call.tail); agg_holder: layers.GraphConvolution's {"agg": P-or-None}
     of a pass over a static input; in_drop = (p, tag, DropoutState): the caller's input dropout, left to this layer
-    (in_drop_supported).  The layer runs as the autograd Function of its route (_conv_route)."""
+    (in_drop_supported).  The layer runs as the autograd Function of its route (_conv_route).  ``x`` may be a list / tuple of
+    column blocks standing for their concatenation (functional.blocks.project_blocks): the literal route then."""
     p = params
-    fn = _ROUTES[_conv_route(x, ops, cfg, p["weight_low"].shape[0], p["weight_low"].shape[1], post_scale, call, tail_layer)]
-    pregathered, ops._pregathered = getattr(ops, "_pregathered", None), None     # one-shot hand-over from models.GCN
+    if isinstance(x, (list, tuple)):
+        # column blocks [x | h_0 | ...] (ACM-Snowball): their projection without the concatenation (functional.blocks), adopted by
+        # the literal layer, whose backward hands dZ back to the projection's
+        if ops.sharded:
+            raise NotImplementedError("row-sharded operators with a block input are out of scope: concatenate the blocks, or "
+                                      "run the block input on one device")
+        if in_drop is not None:
+            raise NotImplementedError("in_drop with a block input: the caller applies the dropout to the feature block")
+        call = _call_or_ambient(call)
+        x = project_blocks(x, (p["weight_low"], p["weight_high"], p["weight_mlp"]), relu=cfg.relu_before, call=call, mask_grad=False)
+        fn, agg_holder, pregathered = _AcmLiteral, None, PROJECTED
+    else:
+        fn = _ROUTES[_conv_route(x, ops, cfg, p["weight_low"].shape[0], p["weight_low"].shape[1], post_scale, call, tail_layer)]
+        pregathered = getattr(ops, "_pregathered", None)                          # one-shot hand-over from models.GCN
+    ops._pregathered = None
     return _run(
         fn, x, p["weight_low"], p["weight_high"], p["weight_mlp"], p["att_vec_low"], p["att_vec_high"],
         p["att_vec_mlp"], p["att_struc_low"], p["struc_low"], p["att_vec"],

@@ -10,7 +10,7 @@ from ..graph import SparseFeatures
 from ._context import _current_tape, _take_pre_proj
 from ._conv_shared import _NO_GRADS, _chan_block, _conv_prologue, _flat_views, _gathered_input, _grads, _head_params, _hop_buffer, \
     _k3_setup, _low_product, _narrow_tables, _pack_head, _reduce_replicated, _set_head, _set_post, _struc_grad, _struc_rows, \
-    _unpack_head
+    _unpack_head, _z_pitch, PROJECTED
 from ._launch import _F32, _as_f32c, _capturing, _vp, _workspace, _workspace_bytes, launch
 from .ops import _drop_now, _drop_spec, cast_bf16, gemm, gemm_drop_supported, gemm_split, proj3, proj_bwd, proj_bwd_supported, \
     proj_fwd, spmm, spmm_v
@@ -19,8 +19,15 @@ from .ops import _drop_now, _drop_spec, cast_bf16, gemm, gemm_drop_supported, ge
 def _literal_project(ctx, x, w3, ops, cfg):
     """K1 of the literal form: Z = X [W_L | W_H | W_I] (ReLU'd for ACMII), with the caller's input dropout drawn in the operand
     load where the projection can (else applied here first), then the k-hop chain's low-pass products.  Returns
-    (x as saved for the backward, [Z_L | Z_H], Z_I, the gathered [Z_L | Z_H] or [A_low^(k-1) Z_L | Z_H]); sets ctx.fb."""
+    (x as saved for the backward, [Z_L | Z_H], Z_I, the gathered [Z_L | Z_H] or [A_low^(k-1) Z_L | Z_H]); sets ctx.fb.
+    A block input (ctx.blocks_z): ``x`` IS Z, projected by functional.blocks.project_blocks in the CSR route's one-table layout."""
     call, hops = ctx.call, ctx.hops
+    if ctx.blocks_z:
+        f = w3[0].shape[1]
+        fb = ctx.fb = _chan_block(f)
+        if x.shape[1] != 2 * fb + f:
+            raise ValueError(f"the projected block input has {x.shape[1]} columns, the layer's Z has {2 * fb + f}")
+        return x, x[:, : 2 * fb], x[:, 2 * fb:], _hop_chain(ops, x[:, : 2 * fb], f, fb, hops)
     sparse_x = isinstance(x, SparseFeatures)
     n, dev = x.shape[0], w3[0].device
     f_in, f = w3[0].shape
@@ -32,11 +39,7 @@ def _literal_project(ctx, x, w3, ops, cfg):
     fb = ctx.fb = _chan_block(f)                  # column distance of the two gathered channels
     # Row pitch of Z: for narrow layers the gathered block [Z_L | Z_H] (2F floats) must be
     # one aligned vector fetch, so rows are padded to a multiple of that block.
-    ldz = 3 * f
-    if f in (2, 4, 8):
-        ldz = -(-3 * f // (2 * f)) * (2 * f)
-    elif fb != f:
-        ldz = -(-(2 * fb + f) // 4) * 4
+    ldz = _z_pitch(f, fb)
     pre = _take_pre_proj(call, x, w3, cfg.relu_before) if use_proj else None
     drop_spec = _drop_spec(ctx.in_drop, ops.row_offset) if ctx.in_drop is not None else None
     # [Z_L | Z_H] as a compact table of its own (what a narrow gather / the k-hop chain walks: 16-byte-block rows at
@@ -92,6 +95,13 @@ def _literal_project(ctx, x, w3, ops, cfg):
                 gemm(x, wcat, relu=cfg.relu_before, out=z, a_drop=drop_spec)        # [n, 3F] view
                 ctx.in_drop_used = drop_spec is not None
             zlh, zi = z[:, : 2 * fb], z[:, 2 * fb:]
+    return x, zlh, zi, _hop_chain(ops, zlh, f, fb, hops)
+
+
+def _hop_chain(ops, zlh, f, fb, hops):
+    """The table the layer's gather walks: [Z_L | Z_H] itself, or (the k-hop chain) [A_low^(k-1) Z_L | Z_H]; all-gathered
+    when row-sharded."""
+    n, dev = zlh.shape[0], zlh.device
     if hops > 2:
         # [A_low^(k-1) Z_L | Z_H] in place: the last of the k - 1 >= 2 products reads a hop buffer and writes over
         # Z_L (which nothing reads again: no ReLU mask in the k-hop layer) -- no copy of Z_H into a second table
@@ -106,7 +116,7 @@ def _literal_project(ctx, x, w3, ops, cfg):
         zg = _pkg._gather_rows(ops, zc)
     else:
         zg = _pkg._gather_rows(ops, zlh) if ops.sharded else zlh                 # gathered [Z_L|Z_H]
-    return x, zlh, zi, zg
+    return zg
 
 
 class _AcmLiteral(torch.autograd.Function):
@@ -120,7 +130,9 @@ class _AcmLiteral(torch.autograd.Function):
     def forward(ctx, x, w_low, w_high, w_mlp, v_low, v_high, v_mlp, v_struc, struc_low, att_mix, lnw_low, lnw_high, lnw_mlp,
                 lnw_struc, lnb_low, lnb_high, lnb_mlp, lnb_struc, ops, cfg, post_relu, post_scale, post_drop, call, tail_layer,
                 agg_holder, in_drop, pregathered):
-        x = _conv_prologue(ctx, x, w_low, ops, post_relu, post_scale, post_drop, call, in_drop)
+        # a block input (functional.blocks): ``x`` is its projection Z, whose Function takes dZ from this layer's backward
+        blocks_z = ctx.blocks_z = pregathered is PROJECTED
+        x = _conv_prologue(ctx, x, w_low, ops, post_relu, post_scale, post_drop, call, in_drop, projected=blocks_z)
         call, post_scale = ctx.call, ctx.post_scale
         sparse_x = isinstance(x, SparseFeatures)
         dev, n = x.device, x.shape[0]
@@ -135,7 +147,7 @@ class _AcmLiteral(torch.autograd.Function):
             raise NotImplementedError("hops > 1 is the ACM-SGC chain: model_type 'acmsgc' only")
         if general and ops.sharded:
             raise NotImplementedError("general operator pairs are not row-sharded")
-        zero_padded = x.shape[1] != f_in
+        zero_padded = x.shape[1] != f_in and not blocks_z
         if zero_padded:
             x = x[:, :f_in].contiguous()
         w3 = tuple(_as_f32c(t, "weight") for t in (w_low, w_high, w_mlp))
@@ -253,7 +265,8 @@ def _fwd_tail(ctx, ops, cfg, graph, p, ws, tail_req, w3, pre, zi, vecs, lnw, lnb
     call = ctx.call
     (n, f), k, dev = out.shape, cfg.n_channels, out.device
     dlog = torch.empty(n, f, dtype=_F32, device=dev)
-    st3 = _k3_setup(cfg, ops, k, f, n, dev, w3[0].shape[0], pre, zi, vecs, lnw, lnb, mix, dlog, False, None, None, fb=ctx.fb)
+    st3 = _k3_setup(cfg, ops, k, f, n, dev, 0 if ctx.blocks_z else w3[0].shape[0], pre, zi, vecs, lnw, lnb, mix, dlog, False, None, None,
+                    fb=ctx.fb)
     loss = torch.empty((), dtype=_F32, device=dev)
     lo = _lib.Loss()
     lo.n_classes = f
@@ -293,7 +306,9 @@ def _k3_backward(ctx, grad_out):
     grad_out = _as_f32c(grad_out, "grad_out")
     tail = ctx.tail
     done = tail is not None and grad_out.data_ptr() == tail["grad_out"].data_ptr()
-    st3 = tail if done else _k3_setup(cfg, ops, k, f, n, dev, wl.shape[0], pre, zi, vecs, lnw, lnb, mix, grad_out,
+    # (a block input: the weight gradients belong to the projection's own Function -- no room for them in this layer's buffer)
+    f_in_w = 0 if getattr(ctx, "blocks_z", False) else wl.shape[0]
+    st3 = tail if done else _k3_setup(cfg, ops, k, f, n, dev, f_in_w, pre, zi, vecs, lnw, lnb, mix, grad_out,
                                       ctx.post_relu, ctx.post_scale, ctx.post_drop, fb=ctx.fb)
     if done:
         ctx.tail = None
@@ -387,6 +402,17 @@ def _literal_backward(ctx, grad_out):
         if last == 0:
             dz[:, :f] = t
 
+    if getattr(ctx, "blocks_z", False):
+        # a block input: dZ (masked above for ACMII) goes to the projection's backward (functional.blocks._ProjectBlocks), in Z's
+        # layout -- channel blocks of fb columns; no gemm / proj_bwd here, and no weight gradient from this Function
+        if fb == f:
+            d_z = dz
+        else:
+            d_z = dz.new_zeros(n, 2 * fb + f)
+            for c in range(3):
+                d_z[:, c * fb:c * fb + f] = dz[:, c * f:(c + 1) * f]
+        _reduce_replicated(flat, ops, defer)
+        return _grads(d_z, (None, None, None), s["d_vec"], d_struc, s["d_mix"], s["d_lnw"], s["d_lnb"])
     if ctx.sparse_x is not None:                                          # dWcat = X_csr^T dZ
         xs = ctx.sparse_x
         xt = xs.csr_t

@@ -158,7 +158,10 @@ class GraphConvolution(nn.Module):
         """Reference signature plus optional keyword arguments: ``post_relu`` / ``post_scale`` fuse the
         caller's ``dropout(relu(out))`` (post_scale = keep-mask / (1 - p)) into the kernel epilogue;
         ``post_drop = (p, tag, functional.DropoutState)`` does the same with the mask generated in registers.
-        ``input`` may carry zero columns beyond ``in_features`` (functional.dropout(..., pad_to=...)).
+        ``input`` may carry zero columns beyond ``in_features`` (functional.dropout(..., pad_to=...)).  A list / tuple of column
+        blocks means their concatenation (widths summing to ``in_features``): the first a SparseFeatures or a dense tensor -- the
+        features, no gradient --, the rest dense fp32; they are projected block by block (functional.project_blocks) and never
+        concatenated.  A bad width, dtype, device or row count raises ValueError naming the block.
         ``rows_permuted``: the operators are relabelled (graph.relabel_by_degree) and the caller already works in
         that numbering -- input, post_scale and the result are rows of the relabelled graph (models.GCN keeps the
         hidden activations there); otherwise the layer translates at its boundary.
@@ -176,7 +179,16 @@ class GraphConvolution(nn.Module):
                 raise RuntimeError("model_type 'sgc'/'gcn' multiplies with torch.mm: adj_low must be dense")
             return AF.mm(adj_low, AF.mm(input, self.weight_low))
         cfg = self._config()
-        if isinstance(input, torch.Tensor) and input.layout != torch.strided:
+        blocks = isinstance(input, (list, tuple))
+        if blocks:
+            # column blocks standing for their concatenation (ACM-Snowball: [x | h_0 | ...]); a bad block raises ValueError
+            n_rows = adj_low.n_local if isinstance(adj_low, FilterOperators) else None
+            AF.check_blocks(input, self.in_features, self.weight_low.device, n_rows)
+            if input_drop is not None:
+                raise NotImplementedError("input_drop with a block input: apply the dropout to the feature block")
+            if isinstance(input[0], torch.Tensor) and input[0].layout != torch.strided:
+                input = [SparseFeatures.from_torch(input[0])] + list(input[1:])
+        elif isinstance(input, torch.Tensor) and input.layout != torch.strided:
             input = SparseFeatures.from_torch(input)          # torch-sparse features: CSR projection
         elif (isinstance(input, torch.Tensor) and input_drop is None and not rows_permuted
                 and not (isinstance(adj_low, FilterOperators) and adj_low.sharded)):
@@ -192,7 +204,8 @@ class GraphConvolution(nn.Module):
             if cfg.n_channels == 4:                       # struc_low is a parameter in the caller's numbering
                 params["struc_low"] = self.struc_low.index_select(0, ops.perm)
             if translate:
-                input = input.permute_rows(ops.perm) if isinstance(input, SparseFeatures) else input.index_select(0, ops.perm)
+                rows = lambda b: b.permute_rows(ops.perm) if isinstance(b, SparseFeatures) else b.index_select(0, ops.perm)  # noqa: E731
+                input = [rows(b) for b in input] if blocks else rows(input)
                 if post_scale is not None:
                     post_scale = post_scale.index_select(0, ops.perm)
         # an output layer without post-op may take a pending functional.fused_loss_tail request (row phase + loss + K3);

@@ -180,32 +180,42 @@ class GCN(nn.Module):
     def _forward_snowball(self, x, adj_low, adj_high, fused, call):
         """models.py:57-64: h_k = dropout(relu(layer_k([x | h_0 | ... | h_{k-1}]))), out = layer_last([x | h_0 | ...]).
         The ReLU + dropout after every hidden layer ride that layer's epilogue (post_relu / post_scale / post_drop);
-        the concatenations are plain copies."""
-        if isinstance(x, SparseFeatures):
-            raise NotImplementedError("acmsnowball concatenates the input with the hidden blocks: dense features only")
+        for a dense ``x`` the concatenations are plain copies; SparseFeatures make every layer after the first read the list
+        [x, h_0, ...] (layers.GraphConvolution's block input): no [n, nfeat + k nhid] tensor, forward or backward."""
         p, st = self.dropout, self.dropout_state
         off = adj_low.row_offset if isinstance(adj_low, FilterOperators) else 0
-        if fused:
+        sparse = isinstance(x, SparseFeatures)
+        if sparse and isinstance(adj_low, FilterOperators) and adj_low.sharded:
+            raise NotImplementedError("acmsnowball on CSR features hands its layers column blocks: row-sharded operators are out of "
+                                      "scope for a block input (dense features keep the concatenation)")
+        if sparse:
+            # CSR features: dropout of the stored values (as _forward_fused_dropout), and the layers read the blocks
+            # [x, h_0, ...] one by one (functional.project_blocks) instead of their concatenation
+            vals = AF.dropout(x.values.reshape(-1, 1), p, st, tag=0).reshape(-1) if fused else F.dropout(x.values, p, training=self.training)
+            x = x.with_values(vals)
+        elif fused:
             x = AF.dropout(x, p, st, tag=0, row_offset=off)
         else:
             x = F.dropout(x, p, training=self.training)
+        cat = (lambda bl: [x] + bl) if sparse else (lambda bl: torch.cat([x] + bl, 1))
+        n_rows, dev = x.shape[0], (x.values.device if sparse else x.device)
         blocks = []
         for k in range(self.nlayers):
-            inp = x if k == 0 else torch.cat([x] + blocks, 1)
+            inp = x if k == 0 else cat(blocks)
             if fused:
                 h = self.gcns[k](inp, adj_low, adj_high, None, post_relu=True, post_drop=(p, 1 + k, st), rows_permuted=self._rows_permuted, call=call)
             else:
                 scale = None
                 if self.training and p > 0:
-                    scale = F.dropout(self._ones_like_hidden(x.shape[0], self.gcns[k].out_features, x.device), p, training=True)
+                    scale = F.dropout(self._ones_like_hidden(n_rows, self.gcns[k].out_features, dev), p, training=True)
                 h = self.gcns[k](inp, adj_low, adj_high, None, post_relu=True, post_scale=scale, rows_permuted=self._rows_permuted, call=call)
             blocks.append(h)
-        return self.gcns[-1](torch.cat([x] + blocks, 1), adj_low, adj_high, None, rows_permuted=self._rows_permuted, call=call)
+        return self.gcns[-1](cat(blocks), adj_low, adj_high, None, rows_permuted=self._rows_permuted, call=call)
 
     def auto_csr(self, x, ops):
         """Wide, mostly-zero features handed over dense -> their CSR twin (graph.SparseFeatures.auto, tuning key
-        ``csr_features``), where this model has the CSR route: not acmsnowball (it concatenates the input with the hidden
-        blocks), not an mlpX stack neither residual kernel covers, not row-sharded operators (a rank's block keeps the
+        ``csr_features``), where this model takes it by itself: not acmsnowball (a dense input keeps the concatenation with the
+        hidden blocks; its CSR route is for the caller who hands over SparseFeatures), not an mlpX stack neither residual kernel covers, not row-sharded operators (a rank's block keeps the
         dense halo exchange), and not while someone has replaced ``F.dropout`` (a mask-replay harness hands out masks of
         the dense shape: the input stays what the masks were recorded for)."""
         if not isinstance(x, torch.Tensor) or F.dropout is not _TORCH_DROPOUT or self.model_type == "acmsnowball":

@@ -331,6 +331,52 @@ int acm_proj_bwd(int64_t n_rows, int64_t f_in, int n_out, const float* X, int64_
                  float* dX, int64_t lddx, float* dW, int64_t lddw, int64_t dw_col_block, int64_t dw_block_stride,
                  void* workspace, size_t workspace_bytes, acm_reduce_list_t* defer, acm_stream_t stream);
 
+/* ------------------------------------------------ projection of column blocks --
+ * The layers of ACM-Snowball read the concatenation [x | h_0 | ... | h_{k-1}] (ACM-Geometric/models.py:57-64:
+ * torch.cat([x] + blocks, 1) in front of every layer) and project it with the three torch.mm(input, W_c) of the layer's
+ * generic branch, ACM-Geometric/layers.py:96-104 (ACM-Pytorch/models/layers.py:179-194; the linear form: layers.py:87-89).  Since
+ *     [x | h_0 | ...] W = x W[0 : nfeat] + sum_j h_j W[r_j : r_j + w_j]
+ * neither the concatenation nor its full-width gradient has to exist: the feature block's term is an existing product
+ * (acm_spmm_v for CSR features, acm_gemm for dense ones) and these two entry points add the dense blocks' terms.
+ *
+ * Z and dZ are [n_rows, 2 f_block + f]-wide tables with channel c (0 low, 1 high, 2 mlp) at column c * f_block -- the layout
+ * the CSR route of the literal layer produces; W_c are the layer's three [f_in, f] weights, pitch ldw, read where they are.
+ *   acm_proj_blocks_fwd   Z = act(accumulate ? Z + S : S), S = sum_j H_j [W_L | W_H | W_I][r_j : r_j + w_j, :], act = ReLU
+ *                         over every channel (`relu`: the ACMII form) or the identity, applied once to the complete sum;
+ *                         without `accumulate` the pad columns f .. f_block of the first two channels are written as zeros.
+ *                         d_h / ld_dh are not read.
+ *   acm_proj_blocks_bwd   dH_j = sum_c dZ_c W_c[r_j : r_j + w_j, :]^T for every block with d_h[j] != NULL, and the weight
+ *                         gradient rows dW_c[r_j : r_j + w_j, :] = H_j^T dZ_c into `dW` = row 0 of the layer's gradient,
+ *                         [f_in, 3 f] (dw_col_block 0, lddw >= 3 f) or column blocks as acm_gemm_blocks writes them
+ *                         ([3, f_in, f]: dw_col_block f, lddw f, dw_block_stride f_in * f).  dZ is taken as it is (the ACMII
+ *                         mask is the caller's).  Per-workgroup partial sums in fixed slots of the workspace, summed by the
+ *                         second phase of acm_reduce (deferrable); no atomics: the same inputs give the same bits.
+ * Every block must satisfy row0[j] + width[j] <= f_in (ACM_ESHAPE otherwise).
+ * Envelope: 1 <= f <= 64, at most ACM_PROJ_BLOCKS_MAX blocks of 4, 8, ... 64 columns, any n_rows; ACM_EUNSUPPORTED otherwise
+ * (the caller then composes the result from acm_gemm, one call per block).  fp32 on v_mfma_f32_16x16x4_f32. */
+#define ACM_PROJ_BLOCKS_MAX 8
+typedef struct {
+    int32_t n_blocks;                            /* dense blocks H_j                                                      */
+    int32_t f, f_block;                          /* columns per weight; column distance of the channels inside Z / dZ     */
+    int32_t f_in;                                /* rows of the weights (and of dW): every block's rows lie inside them    */
+    const float* w_low;
+    const float* w_high;
+    const float* w_mlp;
+    int64_t ldw;
+    const float* h[ACM_PROJ_BLOCKS_MAX];         /* H_j [n_rows, width[j]], row-major, pitch ld_h[j]                      */
+    int64_t ld_h[ACM_PROJ_BLOCKS_MAX];
+    int32_t width[ACM_PROJ_BLOCKS_MAX];
+    int32_t row0[ACM_PROJ_BLOCKS_MAX];           /* r_j: first weight row of block j                                      */
+    float* d_h[ACM_PROJ_BLOCKS_MAX];             /* backward: dH_j (pitch ld_dh[j]) or NULL: no gradient for this block   */
+    int64_t ld_dh[ACM_PROJ_BLOCKS_MAX];
+} acm_proj_blocks_t;
+int acm_proj_blocks_fwd(int64_t n_rows, const acm_proj_blocks_t* p, float* Z, int64_t ldz, int accumulate, int relu,
+                        acm_stream_t stream);
+int acm_proj_blocks_bwd_workspace_bytes(int64_t n_rows, const acm_proj_blocks_t* p, size_t* bytes);
+int acm_proj_blocks_bwd(int64_t n_rows, const acm_proj_blocks_t* p, const float* dZ, int64_t lddz, float* dW, int64_t lddw,
+                        int64_t dw_col_block, int64_t dw_block_stride, void* workspace, size_t workspace_bytes,
+                        acm_reduce_list_t* defer, acm_stream_t stream);
+
 /* ------------------------------------------------ ACM-GCN++ residual branch --
  * xX = F.dropout(F.relu(self.mlpX(x)))  with mlpX = one nn.Linear  (ACM-Geometric/models.py:26-27,55-56,73;
  * ACM-Pytorch/models/models.py:50-53,150-152,165).
