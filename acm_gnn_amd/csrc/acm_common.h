@@ -6,6 +6,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "acm_dispatch.h"
 #include "acm_hip.h"
 
 #define ACM_WAVE 64

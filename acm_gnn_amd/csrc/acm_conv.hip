@@ -224,18 +224,15 @@ extern "C" int acm_conv_fwd(const acm_csr_t* a, const acm_conv_fwd_t* p, void* w
                 "acm_conv_fwd: structure channel pointers are NULL");
     const GatherSrc g = {{p->g_low, p->g_high, k == 4 ? p->g_struc : nullptr}, {p->ld_g_low, p->ld_g_high, k == 4 ? p->ld_g_struc : 0}};
     hipStream_t s = (hipStream_t)stream;
-    int st = ACM_OK;
-    if (F > 8) {
-        acm_with_k(k, [&](auto kc) {
-            st = launch_gather<decltype(kc)::value - 1, EpiFwd>(a, g, F, *p, workspace, workspace_bytes, s, "acm_conv_fwd", nullptr, p->gather_bf16 != 0);
-        });
-        return st;
-    }
+    if (F > 8)
+        return acm_pick([&](auto kc) {
+            return launch_gather<kc() - 1, EpiFwd>(a, g, F, *p, workspace, workspace_bytes, s, "acm_conv_fwd", nullptr, p->gather_bf16 != 0);
+        }, acm_k_of(k));
     // narrow layers, two phases: gather raw sums into `pre`, then one thread per row
     ACM_REQUIRE(!p->gather_bf16, ACM_EUNSUPPORTED, "acm_conv_fwd: bf16 operands need F > 8");
-    acm_with_k(k, [&](auto kc) {
-        st = launch_gather<decltype(kc)::value - 1, EpiRaw>(a, g, F, *p, workspace, workspace_bytes, s, "acm_conv_fwd", nullptr, false, true);
-    });
+    const int st = acm_pick([&](auto kc) {
+        return launch_gather<kc() - 1, EpiRaw>(a, g, F, *p, workspace, workspace_bytes, s, "acm_conv_fwd", nullptr, false, true);
+    }, acm_k_of(k));
     if (st != ACM_OK || a->n_rows == 0) return st;
     const int grid = (int)((a->n_rows + 255) / 256), n = (int)a->n_rows;
     CsrView cv = acm_view(a);
@@ -243,12 +240,10 @@ extern "C" int acm_conv_fwd(const acm_csr_t* a, const acm_conv_fwd_t* p, void* w
     const bool done = narrow_finishes_long_rows(a);     // the gather left complete raw sums for every row
     if (done) cv.long_index = nullptr;
     const int tail = done ? 0 : (int)((a->n_long + 15) / 16);
-    acm_with_fp(F, [&](auto fp) {
-        acm_with_k(k, [&](auto kc) {
-            hipLaunchKernelGGL((conv_fwd_rows_kernel<decltype(fp)::value, decltype(kc)::value - 1>), dim3(grid + tail), dim3(256), 0, s, *p, n,
-                               cv, part, grid);
-        });
-    });
+    acm_pick([&](auto fp, auto kc) {
+        hipLaunchKernelGGL((conv_fwd_rows_kernel<fp(), kc() - 1>), dim3(grid + tail), dim3(256), 0, s, *p, n, cv, part, grid);
+        return ACM_OK;
+    }, acm_fp_of(F), acm_k_of(k));
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }
@@ -403,13 +398,13 @@ extern "C" int acm_conv_fwd_tail(const acm_csr_t* a, const acm_conv_fwd_t* p, co
     float* loss_partial = (float*)tail_workspace;
     float* k3_partial = loss_partial + nblk;
     const size_t lds = (size_t)4 * npg * sizeof(float);
-    acm_with_fp(F, [&](auto fp) {
-        if constexpr (decltype(fp)::value == 8)
+    acm_pick([&](auto fp) {
+        if constexpr (fp() == 8)
             hipLaunchKernelGGL((conv_tail_packed8_kernel<2>), dim3(nblk), dim3(256), lds, s, *p, *l, *b, n, loss_partial, k3_partial);
         else
-            hipLaunchKernelGGL((conv_tail_rows_kernel<decltype(fp)::value, 2>), dim3(nblk), dim3(256), lds, s, *p, *l, *b, n, loss_partial,
-                               k3_partial);
-    });
+            hipLaunchKernelGGL((conv_tail_rows_kernel<fp(), 2>), dim3(nblk), dim3(256), lds, s, *p, *l, *b, n, loss_partial, k3_partial);
+        return ACM_OK;
+    }, acm_fp_of(F));
     ACM_CHECK_HIP(hipGetLastError());
     const acm_reduce_seg_t seg = {loss_partial, nblk, 1, 0, 1, l->loss, 1, 0, 0, 0};
     st = acm_reduce_emit(b->defer, &seg, 1, s);

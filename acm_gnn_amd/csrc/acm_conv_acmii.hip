@@ -319,11 +319,5 @@ extern "C" int acm_conv_acmii_fwd(const acm_csr_t* a, const acm_conv_acmii_fwd_t
     if (K == 3) hipLaunchKernelGGL(acmii_fwd_kernel<3>, dim3(grid), dim3(256), 0, s, *p, cv, (float*)workspace);
     else hipLaunchKernelGGL(acmii_fwd_kernel<4>, dim3(grid), dim3(256), 0, s, *p, cv, (float*)workspace);
     ACM_CHECK_HIP(hipGetLastError());
-    if (a->n_long) {
-        const dim3 fg((unsigned)((a->n_long + 3) / 4));
-        if (K == 3) hipLaunchKernelGGL(acmii_fixup_kernel<3>, fg, dim3(256), 0, s, *p, cv, (const float*)workspace);
-        else hipLaunchKernelGGL(acmii_fixup_kernel<4>, fg, dim3(256), 0, s, *p, cv, (const float*)workspace);
-        ACM_CHECK_HIP(hipGetLastError());
-    }
-    return ACM_OK;
+    return acm_acmii_fixup_launch(a, p, (const float*)workspace, s);
 }

@@ -690,14 +690,11 @@ extern "C" int acm_conv_agg_fwd(const acm_csr_t* a, const acm_conv_agg_fwd_t* p,
             // every block stages the weights and head parameters (8.4 KB) before it starts: 12 blocks per CU keep that
             // prologue small against the gather (8192 blocks: 125 us, 3072: 115 us, 1024: 125 us on the twitch graph)
             if (grid > 3072) grid = 3072;
-            const bool full = p->f_out == 64;
-            if (p->f_pad == 4) {
-                if (full) hipLaunchKernelGGL((agg_fused_kernel<4, true>), dim3(grid), dim3(256), 0, s, *p, cv);
-                else hipLaunchKernelGGL((agg_fused_kernel<4, false>), dim3(grid), dim3(256), 0, s, *p, cv);
-            } else {                                  // 32-byte rows: two lanes per neighbour
-                if (full) hipLaunchKernelGGL((agg_fused_pair_kernel<true>), dim3(grid), dim3(256), 0, s, *p, cv);
-                else hipLaunchKernelGGL((agg_fused_pair_kernel<false>), dim3(grid), dim3(256), 0, s, *p, cv);
-            }
+            acm_pick([&](auto full) {
+                if (p->f_pad == 4) hipLaunchKernelGGL((agg_fused_kernel<4, full()>), dim3(grid), dim3(256), 0, s, *p, cv);
+                else hipLaunchKernelGGL((agg_fused_pair_kernel<full()>), dim3(grid), dim3(256), 0, s, *p, cv);   // 32-byte rows: two lanes per neighbour
+                return ACM_OK;
+            }, acm_flag(p->f_out == 64));
             ACM_CHECK_HIP(hipGetLastError());
             return next_projection(a, p, stream);
         }
@@ -729,19 +726,12 @@ extern "C" int acm_conv_agg_fwd(const acm_csr_t* a, const acm_conv_agg_fwd_t* p,
     int grid = (int)((a->n_rows + 15) / 16);
     if (grid > 2048) grid = 2048;
     const CsrView cv = acm_view(a);
-#define ACM_EPI(FPv)                                                                                           \
-    do {                                                                                                       \
-        if (p->n_channels == 3)                                                                                \
-            hipLaunchKernelGGL((agg_epilogue_kernel<FPv, 3>), dim3(grid), dim3(256), 0, s, *p, (int)a->n_rows, cv, \
-                               defer ? (const float*)workspace : nullptr);                                     \
-        else                                                                                                   \
-            hipLaunchKernelGGL((agg_epilogue_kernel<FPv, 4>), dim3(grid), dim3(256), 0, s, *p, (int)a->n_rows, cv, \
-                               (const float*)nullptr);                                                         \
-    } while (0)
-    if (p->f_pad == 4) ACM_EPI(4);
-    else if (p->f_pad == 8) ACM_EPI(8);
-    else ACM_EPI(16);
-#undef ACM_EPI
+    st = acm_pick([&](auto FP, auto NC) {
+        hipLaunchKernelGGL((agg_epilogue_kernel<FP(), NC()>), dim3(grid), dim3(256), 0, s, *p, (int)a->n_rows, cv,
+                           NC() == 3 && defer ? (const float*)workspace : nullptr);
+        return ACM_OK;
+    }, acm_one_of<4, 8, 16>(p->f_pad), acm_one_of<3, 4>(p->n_channels));
+    ACM_REQUIRE(st == ACM_OK, ACM_EUNSUPPORTED, "acm_conv_agg_fwd: no epilogue kernel for f_pad %d, %d channels", p->f_pad, p->n_channels);
     ACM_CHECK_HIP(hipGetLastError());
     if (p->next_x) {                              // the four-rows-per-wave stage does not carry the refill: a launch of its own
         st = acm_dropout(a->n_rows, p->f_in, p->next_x, p->ld_next_x, const_cast<float*>(p->xs), p->ld_xs, p->f_pad, &p->next_drop, stream);
@@ -789,6 +779,13 @@ extern "C" int acm_conv_agg_bwd(int64_t n_rows, const acm_conv_agg_bwd_t* p, voi
     int nblk = agg_bwd_blocks(n_rows, p->n_channels, lds);
     hipStream_t s = (hipStream_t)stream;
     float* partial = (float*)workspace;
+    // what follows the sixteen-rows-per-wave backward: d_params, and the following layer's weight gradient behind it
+    const auto emit16 = [&](int nb16) {
+        const int off2 = (npg + 31) / 32 * 32, n2 = p->proj_dz ? 3 * p->f_out * p->proj_f : 0;
+        const acm_reduce_seg_t segs[2] = {{partial, nb16, 32, 0, npg, p->d_params, npg, 0, 0, 0, nb16 * 32, 0},
+                                          {partial, nb16, 32, off2, n2, p->proj_d_w, n2 > 0 ? n2 : 1, 0, 0, 0, nb16 * 32, 0}};
+        return acm_reduce_emit(p->defer, segs, n2 > 0 ? 2 : 1, s);
+    };
     if (p->next_agg) {                            // the next step's input gather rides along (header: acm_conv_agg_bwd_t.next_agg)
         const acm_csr_t* na = p->next_a;
         ACM_REQUIRE(na && p->next_xg, ACM_EINVAL, "acm_conv_agg_bwd: next_agg without next_a / next_xg");
@@ -815,12 +812,7 @@ extern "C" int acm_conv_agg_bwd(int64_t n_rows, const acm_conv_agg_bwd_t* p, voi
         {   // eight-wave workgroups of the sixteen-rows-per-wave backward + the gather role (acm_conv_agg16.hip)
             const int nb16 = acm_agg_bwd16(p, n_rows, partial, agg_bwd_blocks(n_rows, 3, 0), s, &gr, nblk);
             if (nb16 < 0) return -nb16;
-            if (nb16 > 0) {
-                const int off2 = (npg + 31) / 32 * 32, n2 = p->proj_dz ? 3 * p->f_out * p->proj_f : 0;
-                const acm_reduce_seg_t segs[2] = {{partial, nb16, 32, 0, npg, p->d_params, npg, 0, 0, 0, nb16 * 32, 0},
-                                                  {partial, nb16, 32, off2, n2, p->proj_d_w, n2 > 0 ? n2 : 1, 0, 0, 0, nb16 * 32, 0}};
-                return acm_reduce_emit(p->defer, segs, n2 > 0 ? 2 : 1, s);
-            }
+            if (nb16 > 0) return emit16(nb16);
         }
         ACM_REQUIRE(false, ACM_EUNSUPPORTED, "acm_conv_agg_bwd: the carried gather (next_agg) needs the sixteen-rows-per-wave backward "
                     "(head_stats, the forward's `out` behind a fused ReLU or no post-op at all, acm_tuning_t.rows16 bit 2)");
@@ -828,30 +820,15 @@ extern "C" int acm_conv_agg_bwd(int64_t n_rows, const acm_conv_agg_bwd_t* p, voi
     if (!p->next_agg) {                           // sixteen rows per wave, transposed matrix-core layout (acm_conv_agg16.hip)
         const int nb16 = acm_agg_bwd16(p, n_rows, partial, nblk, s, nullptr, 0);
         if (nb16 < 0) return -nb16;
-        if (nb16 > 0) {
-            const int off2 = (npg + 31) / 32 * 32, n2 = p->proj_dz ? 3 * p->f_out * p->proj_f : 0;
-            const acm_reduce_seg_t segs[2] = {{partial, nb16, 32, 0, npg, p->d_params, npg, 0, 0, 0, nb16 * 32, 0},
-                                              {partial, nb16, 32, off2, n2, p->proj_d_w, n2 > 0 ? n2 : 1, 0, 0, 0, nb16 * 32, 0}};
-            return acm_reduce_emit(p->defer, segs, n2 > 0 ? 2 : 1, s);
-        }
+        if (nb16 > 0) return emit16(nb16);
     }
     ACM_REQUIRE(!p->proj_dz, ACM_EUNSUPPORTED, "acm_conv_agg_bwd: proj_dz needs the sixteen-rows-per-wave kernel (three channels, "
                 "f_pad 8, f_out 64, head_stats, `out`, proj_f <= 2); run acm_proj_bwd and pass grad_out");
-#define ACM_BWDK(FPv)                                                                                                  \
-    do {                                                                                                              \
-        if (K == 3 && p->f_out == 64)                                                                                  \
-            hipLaunchKernelGGL((agg_bwd_kernel<FPv, 3, true>), dim3(nblk), dim3(256), lds, s, *p, (int)n_rows, partial); \
-        else if (K == 3)                                                                                              \
-            hipLaunchKernelGGL((agg_bwd_kernel<FPv, 3, false>), dim3(nblk), dim3(256), lds, s, *p, (int)n_rows, partial); \
-        else if (p->f_out == 64)                                                                                      \
-            hipLaunchKernelGGL((agg_bwd_kernel<FPv, 4, true>), dim3(nblk), dim3(256), lds, s, *p, (int)n_rows, partial); \
-        else                                                                                                          \
-            hipLaunchKernelGGL((agg_bwd_kernel<FPv, 4, false>), dim3(nblk), dim3(256), lds, s, *p, (int)n_rows, partial); \
-    } while (0)
-    if (p->f_pad == 4) ACM_BWDK(4);
-    else if (p->f_pad == 8) ACM_BWDK(8);
-    else ACM_BWDK(16);
-#undef ACM_BWDK
+    st = acm_pick([&](auto FP, auto NC, auto full) {
+        hipLaunchKernelGGL((agg_bwd_kernel<FP(), NC(), full()>), dim3(nblk), dim3(256), lds, s, *p, (int)n_rows, partial);
+        return ACM_OK;
+    }, acm_one_of<4, 8, 16>(p->f_pad), acm_one_of<3, 4>(K), acm_flag(p->f_out == 64));
+    ACM_REQUIRE(st == ACM_OK, ACM_EUNSUPPORTED, "acm_conv_agg_bwd: no backward kernel for f_pad %d, %d channels", p->f_pad, K);
     ACM_CHECK_HIP(hipGetLastError());
     const acm_reduce_seg_t seg = {partial, nblk, 32, 0, npg, p->d_params, npg, 0, 0, 0, nblk * 32, 0};   // d_params[q] = sum_b partial[q / 32][b][q % 32]
     return acm_reduce_emit(p->defer, &seg, 1, s);

@@ -733,26 +733,11 @@ int acm_agg_epi16(const acm_conv_agg_fwd_t* p, int64_t n_rows, bool* next_done, 
     const bool next = p->next_f > 0;
     int grid = (int)((n_rows + 63) / 64);
     if (grid > 1024) grid = 1024;                    // four workgroups (sixteen waves) per CU
-#define ACM_E16_L(NCv, FPv)                                                                                                   \
-    do {                                                                                                                     \
-        if (p->layernorm) {                                                                                                  \
-            if (next) hipLaunchKernelGGL((agg_epi16_kernel<NCv, FPv, true, true>), dim3(grid), dim3(256), 0, s, *p, (int)n_rows);   \
-            else hipLaunchKernelGGL((agg_epi16_kernel<NCv, FPv, true, false>), dim3(grid), dim3(256), 0, s, *p, (int)n_rows);       \
-        } else {                                                                                                             \
-            if (next) hipLaunchKernelGGL((agg_epi16_kernel<NCv, FPv, false, true>), dim3(grid), dim3(256), 0, s, *p, (int)n_rows);  \
-            else hipLaunchKernelGGL((agg_epi16_kernel<NCv, FPv, false, false>), dim3(grid), dim3(256), 0, s, *p, (int)n_rows);      \
-        }                                                                                                                    \
-    } while (0)
-#define ACM_E16(NCv)                            \
-    do {                                        \
-        if (FP == 4) ACM_E16_L(NCv, 4);         \
-        else if (FP == 8) ACM_E16_L(NCv, 8);    \
-        else ACM_E16_L(NCv, 16);                \
-    } while (0)
-    if (NC == 3) ACM_E16(3);
-    else ACM_E16(4);
-#undef ACM_E16
-#undef ACM_E16_L
+    const int st = acm_pick([&](auto nc, auto fp, auto ln, auto nx) {
+        hipLaunchKernelGGL((agg_epi16_kernel<nc(), fp(), ln(), nx()>), dim3(grid), dim3(256), 0, s, *p, (int)n_rows);
+        return ACM_OK;
+    }, acm_one_of<3, 4>(NC), acm_one_of<4, 8, 16>(FP), acm_flag(p->layernorm != 0), acm_flag(next));
+    if (st != ACM_OK) return -1;
     ACM_CHECK_HIP(hipGetLastError());
     *next_done = next;
     return ACM_OK;
@@ -792,44 +777,26 @@ int acm_agg_bwd16(const acm_conv_agg_bwd_t* p, int64_t n_rows, float* partial, i
         if (gather_blocks < 1 || gather_blocks > max_blocks) return 0;
         grid = gather_blocks;
     }
-    const bool ln = p->layernorm != 0;
-#define ACM_B16_BASE(NCv, FPv)                                                                                                     \
-    do {                                                                                                                          \
-        if (ln) {                                                                                                                 \
-            if (out_mask) hipLaunchKernelGGL((agg_bwd16_kernel<NCv, FPv, true, true, false>), dim3(grid), dim3(256), 0, s, q, (int)n_rows, partial);   \
-            else hipLaunchKernelGGL((agg_bwd16_kernel<NCv, FPv, true, false, false>), dim3(grid), dim3(256), 0, s, q, (int)n_rows, partial);           \
-        } else {                                                                                                                  \
-            if (out_mask) hipLaunchKernelGGL((agg_bwd16_kernel<NCv, FPv, false, true, false>), dim3(grid), dim3(256), 0, s, q, (int)n_rows, partial);  \
-            else hipLaunchKernelGGL((agg_bwd16_kernel<NCv, FPv, false, false, false>), dim3(grid), dim3(256), 0, s, q, (int)n_rows, partial);          \
-        }                                                                                                                         \
-    } while (0)
-    // the carriers (FP = 8, the output read behind a fused ReLU): + proj_*, + next_agg, or both
-#define ACM_B16_CARRY(NCv)                                                                                                          \
-    do {                                                                                                                          \
-        if (gr) {                                                                                                                 \
-            if (ln) { if (proj) hipLaunchKernelGGL((agg_bwd16_gather_kernel<NCv, true, true>), dim3(grid), dim3(512), 0, s, q, (int)n_rows, partial, *gr);   \
-                      else hipLaunchKernelGGL((agg_bwd16_gather_kernel<NCv, true, false>), dim3(grid), dim3(512), 0, s, q, (int)n_rows, partial, *gr); }       \
-            else { if (proj) hipLaunchKernelGGL((agg_bwd16_gather_kernel<NCv, false, true>), dim3(grid), dim3(512), 0, s, q, (int)n_rows, partial, *gr);     \
-                   else hipLaunchKernelGGL((agg_bwd16_gather_kernel<NCv, false, false>), dim3(grid), dim3(512), 0, s, q, (int)n_rows, partial, *gr); }         \
-        } else {                                                                                                                  \
-            if (ln) hipLaunchKernelGGL((agg_bwd16_kernel<NCv, 8, true, true, true>), dim3(grid), dim3(256), 0, s, q, (int)n_rows, partial);                   \
-            else hipLaunchKernelGGL((agg_bwd16_kernel<NCv, 8, false, true, true>), dim3(grid), dim3(256), 0, s, q, (int)n_rows, partial);                     \
-        }                                                                                                                         \
-    } while (0)
-    if (proj || gr) {
-        if (NC == 3) ACM_B16_CARRY(3);
-        else ACM_B16_CARRY(4);
-    } else if (NC == 3) {
-        if (FP == 4) ACM_B16_BASE(3, 4);
-        else if (FP == 8) ACM_B16_BASE(3, 8);
-        else ACM_B16_BASE(3, 16);
-    } else {
-        if (FP == 4) ACM_B16_BASE(4, 4);
-        else if (FP == 8) ACM_B16_BASE(4, 8);
-        else ACM_B16_BASE(4, 16);
-    }
-#undef ACM_B16_BASE
-#undef ACM_B16_CARRY
+    const auto nc_of = acm_one_of<3, 4>(NC);
+    const auto ln_of = acm_flag(p->layernorm != 0);
+    int st;
+    // the carriers (FP = 8, the output read behind a fused ReLU): + next_agg (with or without proj_*), or proj_* alone
+    if (gr)
+        st = acm_pick([&](auto nc, auto ln, auto pj) {
+            hipLaunchKernelGGL((agg_bwd16_gather_kernel<nc(), ln(), pj()>), dim3(grid), dim3(512), 0, s, q, (int)n_rows, partial, *gr);
+            return ACM_OK;
+        }, nc_of, ln_of, acm_flag(proj));
+    else if (proj)
+        st = acm_pick([&](auto nc, auto ln) {
+            hipLaunchKernelGGL((agg_bwd16_kernel<nc(), 8, ln(), true, true>), dim3(grid), dim3(256), 0, s, q, (int)n_rows, partial);
+            return ACM_OK;
+        }, nc_of, ln_of);
+    else
+        st = acm_pick([&](auto nc, auto fp, auto ln, auto om) {
+            hipLaunchKernelGGL((agg_bwd16_kernel<nc(), fp(), ln(), om(), false>), dim3(grid), dim3(256), 0, s, q, (int)n_rows, partial);
+            return ACM_OK;
+        }, nc_of, acm_one_of<4, 8, 16>(FP), ln_of, acm_flag(out_mask));
+    if (st != ACM_OK) return 0;
     if (hipGetLastError() != hipSuccess) return -ACM_EHIP;
     return grid;
 }

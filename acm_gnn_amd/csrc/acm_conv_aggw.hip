@@ -570,26 +570,14 @@ extern "C" int acm_conv_aggw_fwd(int64_t n_rows, int64_t f_in, int64_t f_pad, co
     const int64_t npan = (n_rows + 15) / 16;
     int grid = (int)((npan + 7) / 8);
     if (grid > 256) grid = 256;
-#define ACM_AGGW(LNv, KBv)                                                                                                        \
-    do {                                                                                                                          \
-        ACM_CHECK_HIP(hipFuncSetAttribute((const void*)aggw_head_kernel<LNv, KBv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((aggw_head_kernel<LNv, KBv>), dim3(grid), dim3(512), lds, st, (int)n_rows, (int)f_pad, (int)f_in, agg,      \
-                           (long)ld_agg, xs, (long)ld_xs, w_low, w_high, w_mlp, (long)ld_w, zi, (long)ld_zi, *p);                   \
-    } while (0)
-#define ACM_AGGW_KB(LNv)                    \
-    switch (n_kb) {                         \
-        case 1: ACM_AGGW(LNv, 1); break;    \
-        case 2: ACM_AGGW(LNv, 2); break;    \
-        case 3: ACM_AGGW(LNv, 3); break;    \
-        default: ACM_AGGW(LNv, 4); break;   \
-    }
-    if (p->layernorm) {
-        ACM_AGGW_KB(true)
-    } else {
-        ACM_AGGW_KB(false)
-    }
-#undef ACM_AGGW_KB
-#undef ACM_AGGW
+    const int rc = acm_pick([&](auto LN, auto KB) {
+        ACM_CHECK_HIP(hipFuncSetAttribute((const void*)aggw_head_kernel<LN(), KB()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((aggw_head_kernel<LN(), KB()>), dim3(grid), dim3(512), lds, st, (int)n_rows, (int)f_pad, (int)f_in, agg,
+                           (long)ld_agg, xs, (long)ld_xs, w_low, w_high, w_mlp, (long)ld_w, zi, (long)ld_zi, *p);
+        return ACM_OK;
+    }, acm_flag(p->layernorm != 0), acm_one_of<1, 2, 3, 4>(n_kb));
+    ACM_REQUIRE(rc != ACM_NO_INSTANTIATION, ACM_EUNSUPPORTED, "acm_conv_aggw_fwd: no kernel for %d feature blocks", n_kb);
+    if (rc != ACM_OK) return rc;
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }
@@ -629,25 +617,14 @@ extern "C" int acm_conv_aggw_bwd(int64_t n_rows, int64_t f_in, int64_t f_pad, co
     float* part_w = (float*)workspace;                                  // (grouped slabs: 16-byte aligned lines)
     float* part_head = part_w + (size_t)nblk * 3 * kt * 16 * 64;
     const size_t lds = (size_t)AWB_GS * 16 + (576 + 192) * sizeof(float);
-#define ACM_AGGWB(LNv, KTv)                                                                                                       \
-    do {                                                                                                                          \
-        ACM_CHECK_HIP(hipFuncSetAttribute((const void*)aggw_bwd_kernel<LNv, KTv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((aggw_bwd_kernel<LNv, KTv>), dim3(nblk), dim3(512), lds, st, *p, (int)n_rows, (int)f_pad, agg, (long)ld_agg, \
-                           xs, (long)ld_xs, part_head, part_w);                                                                   \
-    } while (0)
-#define ACM_AGGWB_KT(LNv)                                                                                   \
-    switch (kt) {                                                                                           \
-        case 1: ACM_AGGWB(LNv, 1); break;  case 2: ACM_AGGWB(LNv, 2); break;  case 3: ACM_AGGWB(LNv, 3); break; \
-        case 4: ACM_AGGWB(LNv, 4); break;  case 5: ACM_AGGWB(LNv, 5); break;  case 6: ACM_AGGWB(LNv, 6); break; \
-        case 7: ACM_AGGWB(LNv, 7); break;  default: ACM_AGGWB(LNv, 8); break;                                \
-    }
-    if (p->layernorm) {
-        ACM_AGGWB_KT(true)
-    } else {
-        ACM_AGGWB_KT(false)
-    }
-#undef ACM_AGGWB_KT
-#undef ACM_AGGWB
+    const int rc = acm_pick([&](auto LN, auto KT) {
+        ACM_CHECK_HIP(hipFuncSetAttribute((const void*)aggw_bwd_kernel<LN(), KT()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((aggw_bwd_kernel<LN(), KT()>), dim3(nblk), dim3(512), lds, st, *p, (int)n_rows, (int)f_pad, agg, (long)ld_agg,
+                           xs, (long)ld_xs, part_head, part_w);
+        return ACM_OK;
+    }, acm_flag(p->layernorm != 0), acm_one_of<1, 2, 3, 4, 5, 6, 7, 8>(kt));
+    ACM_REQUIRE(rc != ACM_NO_INSTANTIATION, ACM_EUNSUPPORTED, "acm_conv_aggw_bwd: no kernel for %d feature tiles", kt);
+    if (rc != ACM_OK) return rc;
     ACM_CHECK_HIP(hipGetLastError());
     // second phases: the head-parameter sums (the segments of acm_conv_bwd_local) and the three weight gradients (rows < f_in)
     acm_reduce_seg_t segs[13];

@@ -320,17 +320,18 @@ extern "C" int acm_conv_bwd_local(int64_t n_rows, const acm_conv_bwd_local_t* p,
                     "acm_conv_bwd_local: rows x leading dimension exceeds 2^31");
         const size_t hl = (size_t)3 * k * 64 * sizeof(float);
         if (hl > lds) lds = hl;
-        acm_with_k(k, [&](auto kc) {
-            hipLaunchKernelGGL((conv_bwd_local_grouped_kernel<decltype(kc)::value>), dim3(nblk), dim3(256), lds, st, *p, (int)n_rows, partial);
-        });
+        acm_pick([&](auto kc) {
+            hipLaunchKernelGGL((conv_bwd_local_grouped_kernel<kc()>), dim3(nblk), dim3(256), lds, st, *p, (int)n_rows, partial);
+            return ACM_OK;
+        }, acm_k_of(k));
         ACM_CHECK_HIP(hipGetLastError());
         return acm_bwd_local_reduce(p, partial, nblk, st);
     }
     auto launch = [&](auto lay, auto rpw) {
-        acm_with_k(k, [&](auto kc) {
-            hipLaunchKernelGGL((conv_bwd_local_kernel<decltype(lay), decltype(rpw)::value, decltype(kc)::value>), dim3(nblk), dim3(256),
-                               lds, st, *p, (int)n_rows, partial);
-        });
+        acm_pick([&](auto kc) {
+            hipLaunchKernelGGL((conv_bwd_local_kernel<decltype(lay), rpw(), kc()>), dim3(nblk), dim3(256), lds, st, *p, (int)n_rows, partial);
+            return ACM_OK;
+        }, acm_k_of(k));
     };
     if (F > 128) launch(LayWide<4>{}, acm_int<1>{});
     else if (F > 64) launch(LayWide<2>{}, acm_int<1>{});

@@ -753,19 +753,21 @@ __global__ __launch_bounds__(256) void spmm_narrow_pair3_kernel(CsrView csr, con
 }
 
 // ------------------------------------------------------------------ host-side dispatch
-// A run-time size picks a template argument at several places.  Each ladder is written once; it hands its choice to a
-// generic lambda as a std::integral_constant.
+// A run-time size picks a template argument at several places.  Each rounding is written once, as the choice acm_pick takes
+// (acm_dispatch.h): the size rounded to its instantiation, with the list of instantiations.
 template <int V>
 using acm_int = std::integral_constant<int, V>;
 // narrow layers (F <= 8): the row padded to FP = 2, 4 or 8 columns
-template <class Fn> void acm_with_fp(int F, Fn&& fn) { F <= 2 ? fn(acm_int<2>{}) : (F <= 4 ? fn(acm_int<4>{}) : fn(acm_int<8>{})); }
-inline int acm_fp(int F) { int FP; acm_with_fp(F, [&](auto fp) { FP = decltype(fp)::value; }); return FP; }
+inline auto acm_fp_of(int F) { return acm_one_of<2, 4, 8>(F <= 2 ? 2 : (F <= 4 ? 4 : 8)); }
+inline int acm_fp(int F) { return acm_fp_of(F).v; }
 // wide layers (8 < F <= 256), lane l owns columns l + 64 r: NREG = 1, 2 or 4 registers per channel
-template <class Fn> void acm_with_nreg(int F, Fn&& fn) { F <= 64 ? fn(acm_int<1>{}) : (F <= 128 ? fn(acm_int<2>{}) : fn(acm_int<4>{})); }
+inline auto acm_nreg_of(int F) { return acm_one_of<1, 2, 4>(F <= 64 ? 1 : (F <= 128 ? 2 : 4)); }
 // wide layers, vector form: NB = 1 .. 4 blocks of 64 columns
-template <class Fn> void acm_with_nb(int F, Fn&& fn) { F <= 64 ? fn(acm_int<1>{}) : (F <= 128 ? fn(acm_int<2>{}) : (F <= 192 ? fn(acm_int<3>{}) : fn(acm_int<4>{}))); }
+inline auto acm_nb_of(int F) { return acm_one_of<1, 2, 3, 4>(F <= 64 ? 1 : (F <= 128 ? 2 : (F <= 192 ? 3 : 4))); }
 // k = 3 channels of the layer, or 4 with the structure channel (k - 1 of them are gathered)
-template <class Fn> void acm_with_k(int k, Fn&& fn) { k == 4 ? fn(acm_int<4>{}) : fn(acm_int<3>{}); }
+inline auto acm_k_of(int k) { return acm_one_of<3, 4>(k); }
+// lanes per work item of the narrow gather (narrow_lanes)
+inline auto acm_lanes_of(int lanes) { return acm_one_of<8, 16, 32>(lanes); }
 
 // lanes per work item of the narrow gather: 8 for very sparse graphs, 16 up to an average degree of 160 (a power-law
 // graph with mean 82 has median 30: with 32 lanes x 2 neighbours most lanes of most rows idle), 32 beyond
@@ -777,7 +779,7 @@ inline int narrow_lanes(int64_t n_rows, int64_t nnz) {
 inline bool narrow_finishes_long_rows(const acm_csr* a) { return narrow_lanes(a->n_rows, a->nnz) == ACM_WINDOW; }
 
 // Which kernel of the family a gather takes.  The template arguments that depend on F alone (FP, NB, NREG) follow from the
-// ladders above at the launch.
+// roundings above at the launch.
 struct GatherForm {
     enum Kind { NARROW, PAIR3, VEC16, VEC, PAIR_BF16, PAIR_F32, WIDE } kind;
     int lanes;      // NARROW: lanes per work item (8, 16 or 32)
@@ -877,9 +879,10 @@ template <int NG, class Epi>
 int finish_window_rows(const acm_csr* a, const CsrView& v, int F, const typename Epi::Args& ea, const float* partial, hipStream_t st) {
     if (a->n_multi == 0) return ACM_OK;
     const int grid = (int)((a->n_long + 15) / 16);
-    acm_with_fp(F, [&](auto fp) {
-        hipLaunchKernelGGL((spmm_fixup_windows_kernel<decltype(fp)::value, NG, Epi>), dim3(grid), dim3(256), 0, st, v, F, ea, partial);
-    });
+    acm_pick([&](auto fp) {
+        hipLaunchKernelGGL((spmm_fixup_windows_kernel<fp(), NG, Epi>), dim3(grid), dim3(256), 0, st, v, F, ea, partial);
+        return ACM_OK;
+    }, acm_fp_of(F));
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }
@@ -909,6 +912,7 @@ int launch_gather(const acm_csr* a, const GatherSrc& g, int F, const typename Ep
     auto wide = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((int)((a->n_items + 3) / 4)), dim3(256), 0, st, v, g, F, ea, partial); };
     if constexpr (epi_wide_only<Epi>::value)
         ACM_REQUIRE(F > 8, ACM_EUNSUPPORTED, "%s: this epilogue exists for more than 8 columns (got %d)", who, F);
+    int rc = ACM_OK;
     switch (form.kind) {
     case GatherForm::PAIR3: {
       if constexpr (!epi_wide_only<Epi>::value) {
@@ -922,27 +926,26 @@ int launch_gather(const acm_csr* a, const GatherSrc& g, int F, const typename Ep
     }
     case GatherForm::NARROW:
       if constexpr (!epi_wide_only<Epi>::value)
-        acm_with_fp(F, [&](auto fp) {
-            auto launch = [&](auto gs) {
-                constexpr int FP = decltype(fp)::value, GS = decltype(gs)::value, gpb = 256 / GS;
-                int grid = (int)((a->n_items + gpb - 1) / gpb);
-                if (grid > NARROW_MAX_BLOCKS) grid = NARROW_MAX_BLOCKS;
-                if (form.merged)
-                    hipLaunchKernelGGL((spmm_narrow_kernel<FP, NG, GS, (NG >= 2), Epi>), dim3(grid), dim3(256), 0, st, v, g, F,
-                                       form.vecmask, ea, partial);
-                else
-                    hipLaunchKernelGGL((spmm_narrow_kernel<FP, NG, GS, false, Epi>), dim3(grid), dim3(256), 0, st, v, g, F,
-                                       form.vecmask, ea, partial);
-            };
-            form.lanes == 8 ? launch(acm_int<8>{}) : (form.lanes == 16 ? launch(acm_int<16>{}) : launch(acm_int<32>{}));
-        });
+        rc = acm_pick([&](auto fp, auto gs) {
+            constexpr int FP = decltype(fp)::value, GS = decltype(gs)::value, gpb = 256 / GS;
+            int grid = (int)((a->n_items + gpb - 1) / gpb);
+            if (grid > NARROW_MAX_BLOCKS) grid = NARROW_MAX_BLOCKS;
+            if (form.merged)
+                hipLaunchKernelGGL((spmm_narrow_kernel<FP, NG, GS, (NG >= 2), Epi>), dim3(grid), dim3(256), 0, st, v, g, F,
+                                   form.vecmask, ea, partial);
+            else
+                hipLaunchKernelGGL((spmm_narrow_kernel<FP, NG, GS, false, Epi>), dim3(grid), dim3(256), 0, st, v, g, F,
+                                   form.vecmask, ea, partial);
+            return ACM_OK;
+        }, acm_fp_of(F), acm_lanes_of(form.lanes));
         break;
     case GatherForm::VEC16: wide(spmm_vec_kernel<NG, 1, Epi, true>); break;
-    case GatherForm::VEC: acm_with_nb(F, [&](auto nb) { wide(spmm_vec_kernel<NG, decltype(nb)::value, Epi>); }); break;
+    case GatherForm::VEC: acm_pick([&](auto nb) { wide(spmm_vec_kernel<NG, nb(), Epi>); return ACM_OK; }, acm_nb_of(F)); break;
     case GatherForm::PAIR_BF16: wide(spmm_pair_kernel<NG, Epi, true>); break;
     case GatherForm::PAIR_F32: wide(spmm_pair_kernel<NG, Epi, false>); break;
-    case GatherForm::WIDE: acm_with_nreg(F, [&](auto nreg) { wide(spmm_wide_kernel<decltype(nreg)::value, NG, Epi>); }); break;
+    case GatherForm::WIDE: acm_pick([&](auto nreg) { wide(spmm_wide_kernel<nreg(), NG, Epi>); return ACM_OK; }, acm_nreg_of(F)); break;
     }
+    ACM_REQUIRE(rc == ACM_OK, ACM_EUNSUPPORTED, "%s: no narrow gather for %d lanes per item", who, form.lanes);
     ACM_CHECK_HIP(hipGetLastError());
     // sixteen lanes per item: the narrow gather has finished the long rows itself, except the rows of several windows
     if constexpr (!epi_wide_only<Epi>::value)
@@ -950,15 +953,16 @@ int launch_gather(const acm_csr* a, const GatherSrc& g, int F, const typename Ep
     if (defer_fixup || !a->n_long) return ACM_OK;      // (deferred: the caller's next kernel adds the partial slots of the long rows)
     if (F <= 8) {
       if constexpr (!epi_wide_only<Epi>::value)
-        acm_with_fp(F, [&](auto fp) {
-            hipLaunchKernelGGL((spmm_fixup_narrow_kernel<decltype(fp)::value, NG, Epi>), dim3((int)((a->n_long + 15) / 16)), dim3(256), 0,
-                               st, v, F, ea, partial);
-        });
+        acm_pick([&](auto fp) {
+            hipLaunchKernelGGL((spmm_fixup_narrow_kernel<fp(), NG, Epi>), dim3((int)((a->n_long + 15) / 16)), dim3(256), 0, st, v, F, ea,
+                               partial);
+            return ACM_OK;
+        }, acm_fp_of(F));
     } else {
-        acm_with_nreg(F, [&](auto nreg) {
-            hipLaunchKernelGGL((spmm_fixup_kernel<decltype(nreg)::value, NG, Epi>), dim3((int)((a->n_long + 3) / 4)), dim3(256), 0, st,
-                               v, F, ea, partial);
-        });
+        acm_pick([&](auto nreg) {
+            hipLaunchKernelGGL((spmm_fixup_kernel<nreg(), NG, Epi>), dim3((int)((a->n_long + 3) / 4)), dim3(256), 0, st, v, F, ea, partial);
+            return ACM_OK;
+        }, acm_nreg_of(F));
     }
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;

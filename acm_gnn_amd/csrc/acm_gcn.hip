@@ -253,27 +253,26 @@ extern "C" int acm_gcn_bwd(const acm_csr_t* a, const acm_gcn_bwd_t* p, void* wor
         const GatherSrc g = {{p->dy, nullptr, nullptr}, {(long)p->ld_dy, 0, 0}};
         const GatherForm form = choose_gather_form(a->n_rows, a->n_cols, a->nnz, a->n_long, a->long_index, g, 1, F, false, 0, false);
         EpiGcnBwd::Args ea = {rec, pl.gs, 0};
-        acm_with_fp(F, [&](auto fp) {
-            auto launch = [&](auto gs) {
-                constexpr int FP = decltype(fp)::value, GS = decltype(gs)::value;
-                if constexpr (!(FP == 8 && GS == 16))          // (never chosen: gcn_bwd_plan)
-                    hipLaunchKernelGGL((spmm_narrow_kernel<FP, 1, GS, false, EpiGcnBwd>), dim3(pl.grid), dim3(256), 0, s, v, g, F,
-                                       form.vecmask, ea, partial);
-            };
-            pl.gs == 8 ? launch(acm_int<8>{}) : (pl.gs == 16 ? launch(acm_int<16>{}) : launch(acm_int<32>{}));
-        });
+        const int rc = acm_pick([&](auto fp, auto gs) {
+            constexpr int FP = decltype(fp)::value, GS = decltype(gs)::value;
+            if constexpr (!(FP == 8 && GS == 16))          // (never chosen: gcn_bwd_plan)
+                hipLaunchKernelGGL((spmm_narrow_kernel<FP, 1, GS, false, EpiGcnBwd>), dim3(pl.grid), dim3(256), 0, s, v, g, F,
+                                   form.vecmask, ea, partial);
+            return ACM_OK;
+        }, acm_fp_of(F), acm_lanes_of(pl.gs));
+        ACM_REQUIRE(rc == ACM_OK, ACM_EUNSUPPORTED, "acm_gcn_bwd: no narrow gather for %d lanes per item", pl.gs);
         ACM_CHECK_HIP(hipGetLastError());
         if (pl.fix_blocks) {                      // the long rows the gather left in partial slots: groups of sixteen lanes
             ea.gs = 16;
             ea.slab_base = pl.grid * (256 / pl.gs);
             const bool windows = pl.gs == ACM_WINDOW;
-            acm_with_fp(F, [&](auto fp) {
-                constexpr int FP = decltype(fp)::value;
+            acm_pick([&](auto fp) {
                 if (windows)
-                    hipLaunchKernelGGL((spmm_fixup_windows_kernel<FP, 1, EpiGcnBwd>), dim3(pl.fix_blocks), dim3(256), 0, s, v, F, ea, partial);
+                    hipLaunchKernelGGL((spmm_fixup_windows_kernel<fp(), 1, EpiGcnBwd>), dim3(pl.fix_blocks), dim3(256), 0, s, v, F, ea, partial);
                 else
-                    hipLaunchKernelGGL((spmm_fixup_narrow_kernel<FP, 1, EpiGcnBwd>), dim3(pl.fix_blocks), dim3(256), 0, s, v, F, ea, partial);
-            });
+                    hipLaunchKernelGGL((spmm_fixup_narrow_kernel<fp(), 1, EpiGcnBwd>), dim3(pl.fix_blocks), dim3(256), 0, s, v, F, ea, partial);
+                return ACM_OK;
+            }, acm_fp_of(F));
             ACM_CHECK_HIP(hipGetLastError());
         }
     }

@@ -232,14 +232,11 @@ template <int WM, int WN, int WVM, int WVN>
 void launch_shape(int ta, int tb, const GemmPlan& p, hipStream_t st, int M, int N, int K, const float* A,
                   long lda, const float* B, long ldb, float* C, long ldc, int relu, float* slabs, int cb, long cbs,
                   int split, float* C2, long ldc2, const float* bias, const acm_dropout_t& drop) {
-#define ACM_GEMM_LAUNCH(TAv, TBv)                                                                        \
-    hipLaunchKernelGGL((gemm_kernel<WM, WN, WVM, WVN, TAv, TBv>), p.grid, dim3(256), 0, st, M, N, K, A, \
-                       lda, B, ldb, C, ldc, relu, p.k_per_split, slabs, cb, cbs, split, C2, ldc2, bias, drop)
-    if (!ta && !tb) ACM_GEMM_LAUNCH(false, false);
-    else if (ta && !tb) ACM_GEMM_LAUNCH(true, false);
-    else if (!ta && tb) ACM_GEMM_LAUNCH(false, true);
-    else ACM_GEMM_LAUNCH(true, true);
-#undef ACM_GEMM_LAUNCH
+    acm_pick([&](auto TA, auto TB) {
+        hipLaunchKernelGGL((gemm_kernel<WM, WN, WVM, WVN, TA(), TB()>), p.grid, dim3(256), 0, st, M, N, K, A, lda, B, ldb, C,
+                           ldc, relu, p.k_per_split, slabs, cb, cbs, split, C2, ldc2, bias, drop);
+        return ACM_OK;
+    }, acm_flag(ta != 0), acm_flag(tb != 0));
 }
 
 }  // namespace

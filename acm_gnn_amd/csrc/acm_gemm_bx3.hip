@@ -433,19 +433,14 @@ static int bx3_nn_ex(int64_t M, int64_t N, int64_t K, const float* A, int64_t ld
     int grid = (int)((npan + 7) / 8);
     if (grid > 256 * per_cu) grid = 256 * per_cu;
     const int vecc = ldc % 4 == 0 && ((uintptr_t)C) % 16 == 0;
-#define ACM_BX3(NTv, NAv)                                                                                                    \
-    do {                                                                                                                \
-        ACM_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bx3_nn_kernel<NTv, NAv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((gemm_bx3_nn_kernel<NTv, NAv>), dim3(grid), dim3(512), lds, st, (int)M, (int)N, (int)K, A, (long)lda, B,  \
-                           (long)ldb, C, (long)ldc, relu, drop, vecc, cs);                                                \
-    } while (0)
-    switch (ntr) {
-        case 2: ACM_BX3(2, 1); break;
-        case 4: ACM_BX3(4, 1); break;
-        case 8: ACM_BX3(8, 1); break;
-        default: ACM_BX3(12, 1); break;
-    }
-#undef ACM_BX3
+    const int rc = acm_pick([&](auto NT) {
+        ACM_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bx3_nn_kernel<NT(), na>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((gemm_bx3_nn_kernel<NT(), na>), dim3(grid), dim3(512), lds, st, (int)M, (int)N, (int)K, A, (long)lda, B,
+                           (long)ldb, C, (long)ldc, relu, drop, vecc, cs);
+        return ACM_OK;
+    }, acm_one_of<2, 4, 8, 12>(ntr));
+    ACM_REQUIRE(rc != ACM_NO_INSTANTIATION, ACM_EUNSUPPORTED, "acm_gemm_bx3_nn: no kernel for %d column tiles", nt);
+    if (rc != ACM_OK) return rc;
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }
@@ -476,19 +471,14 @@ int acm_gemm_bx3_tn(int64_t n_rows, int64_t K, int64_t N, const float* X, int64_
     int64_t rpb = (n_rows + blocks - 1) / blocks;
     rpb = (rpb + 31) / 32 * 32;
     const size_t lds = (size_t)2 * 3 * (128 + 16 * ntr) * 20 * sizeof(unsigned);
-#define ACM_BX3T(NTv)                                                                                                   \
-    do {                                                                                                                \
-        ACM_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bx3_tn_kernel<NTv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((gemm_bx3_tn_kernel<NTv>), dim3(blocks, (unsigned)((K + 127) / 128)), dim3(512), lds, st, (int)n_rows, (int)K, (int)N, X,  \
-                           (long)ldx, Dz, (long)lddz, slabs, (int)rpb, drop);                                        \
-    } while (0)
-    switch (ntr) {
-        case 2: ACM_BX3T(2); break;
-        case 4: ACM_BX3T(4); break;
-        case 8: ACM_BX3T(8); break;
-        default: ACM_BX3T(12); break;
-    }
-#undef ACM_BX3T
+    const int rc = acm_pick([&](auto NT) {
+        ACM_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bx3_tn_kernel<NT()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((gemm_bx3_tn_kernel<NT()>), dim3(blocks, (unsigned)((K + 127) / 128)), dim3(512), lds, st, (int)n_rows, (int)K, (int)N, X,
+                           (long)ldx, Dz, (long)lddz, slabs, (int)rpb, drop);
+        return ACM_OK;
+    }, acm_one_of<2, 4, 8, 12>(ntr));
+    ACM_REQUIRE(rc != ACM_NO_INSTANTIATION, ACM_EUNSUPPORTED, "acm_gemm_bx3_tn: no kernel for %d column tiles", nt);
+    if (rc != ACM_OK) return rc;
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }

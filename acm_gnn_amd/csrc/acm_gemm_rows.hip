@@ -316,6 +316,8 @@ __global__ __launch_bounds__(256) void gemm_rows_tn_kernel(int n_rows, int K, in
 // Shapes these kernels are written for: up to 192 columns; rows of B / dZ that are 16-byte aligned multiples of 4 floats are
 // staged with 16-byte loads, anything else with guarded scalars.
 static bool rows_shape_ok(int64_t N) { return N >= 1 && N <= 192; }
+// the instantiated tile counts: nt column tiles rounded up to one of them (rows_shape_ok: at most 12)
+static auto rows_tiles(int nt) { return acm_one_of<1, 2, 3, 4, 6, 8, 10, 12>(nt <= 4 ? nt : (nt + 1) & ~1); }
 static int rows_vecb(int64_t N, const float* B, int64_t ldb) { return N % 4 == 0 && ((uintptr_t)B) % 16 == 0 && ldb % 4 == 0; }
 
 bool acm_gemm_rows_nn_ok(int64_t M, int64_t N, int64_t K, const float* B, int64_t ldb) {
@@ -329,50 +331,32 @@ int acm_gemm_rows_nn(int64_t M, int64_t N, int64_t K, const float* A, int64_t ld
     if (drop_in) drop = *drop_in;
     const int nt = (int)((N + 15) / 16);
     int grid = (int)((M + RBM - 1) / RBM);
-    const int ntr = nt <= 4 ? nt : (nt <= 6 ? 6 : (nt <= 8 ? 8 : (nt <= 10 ? 10 : 12)));      // the instantiated tile counts
+    const int ntr = rows_tiles(nt).v;
     if (K <= 128) {          // B resident, persistent workgroups
         const int kp = (int)((K + 63) / 64 * 64);
         const size_t lds_w = ((size_t)kp * (((ntr * 16 + 31) / 32) * 32 + 16) + (size_t)kp * (RBM + 17)) * sizeof(float);
         const int blocks_per_cu = lds_w <= 48 * 1024 ? 3 : (lds_w <= 78 * 1024 ? 2 : 1);
         if (grid > 256 * blocks_per_cu) grid = 256 * blocks_per_cu;
-#define ACM_RNW(NTv)                                                                                                    \
-    do {                                                                                                                \
-        ACM_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_rows_nn_wres_kernel<NTv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w)); \
-        hipLaunchKernelGGL((gemm_rows_nn_wres_kernel<NTv>), dim3(grid), dim3(256), lds_w, st, (int)M, (int)N, (int)K, A, (long)lda, B, \
-                           (long)ldb, C, (long)ldc, relu, drop, rows_vecb(N, B, ldb));                                  \
-    } while (0)
-        switch (ntr) {
-            case 1: ACM_RNW(1); break;
-            case 2: ACM_RNW(2); break;
-            case 3: ACM_RNW(3); break;
-            case 4: ACM_RNW(4); break;
-            case 6: ACM_RNW(6); break;
-            case 8: ACM_RNW(8); break;
-            case 10: ACM_RNW(10); break;
-            default: ACM_RNW(12); break;
-        }
-#undef ACM_RNW
+        const int rc = acm_pick([&](auto NT) {
+            ACM_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_rows_nn_wres_kernel<NT()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w));
+            hipLaunchKernelGGL((gemm_rows_nn_wres_kernel<NT()>), dim3(grid), dim3(256), lds_w, st, (int)M, (int)N, (int)K, A, (long)lda, B,
+                               (long)ldb, C, (long)ldc, relu, drop, rows_vecb(N, B, ldb));
+            return ACM_OK;
+        }, rows_tiles(nt));
+        ACM_REQUIRE(rc != ACM_NO_INSTANTIATION, ACM_EUNSUPPORTED, "acm_gemm_rows_nn: no kernel for %d column tiles", nt);
+        if (rc != ACM_OK) return rc;
         ACM_CHECK_HIP(hipGetLastError());
         return ACM_OK;
     }
     const size_t lds = ((size_t)RBK * (RBM + 16) + (size_t)RBK * (((ntr * 16 + 31) / 32) * 32 + 16)) * sizeof(float);
-#define ACM_RNN(NTv)                                                                                                    \
-    do {                                                                                                                \
-        ACM_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_rows_nn_kernel<NTv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((gemm_rows_nn_kernel<NTv>), dim3(grid), dim3(256), lds, st, (int)M, (int)N, (int)K, A, (long)lda, B,  \
-                           (long)ldb, C, (long)ldc, relu, drop, rows_vecb(N, B, ldb));                                                        \
-    } while (0)
-    switch (nt) {
-        case 1: ACM_RNN(1); break;
-        case 2: ACM_RNN(2); break;
-        case 3: ACM_RNN(3); break;
-        case 4: ACM_RNN(4); break;
-        case 5: case 6: ACM_RNN(6); break;
-        case 7: case 8: ACM_RNN(8); break;
-        case 9: case 10: ACM_RNN(10); break;
-        default: ACM_RNN(12); break;
-    }
-#undef ACM_RNN
+    const int rc = acm_pick([&](auto NT) {
+        ACM_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_rows_nn_kernel<NT()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((gemm_rows_nn_kernel<NT()>), dim3(grid), dim3(256), lds, st, (int)M, (int)N, (int)K, A, (long)lda, B,
+                           (long)ldb, C, (long)ldc, relu, drop, rows_vecb(N, B, ldb));
+        return ACM_OK;
+    }, rows_tiles(nt));
+    ACM_REQUIRE(rc != ACM_NO_INSTANTIATION, ACM_EUNSUPPORTED, "acm_gemm_rows_nn: no kernel for %d column tiles", nt);
+    if (rc != ACM_OK) return rc;
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }
@@ -394,23 +378,14 @@ int acm_gemm_rows_tn(int64_t n_rows, int64_t K, int64_t N, const float* X, int64
     int64_t rpb = (n_rows + blocks - 1) / blocks;
     rpb = (rpb + RBK - 1) / RBK * RBK;
     const size_t lds = ((size_t)RBK * (128 + 16) + (size_t)RBK * (((nt * 16 + 31) / 32) * 32 + 16)) * sizeof(float);
-#define ACM_RTN(NTv)                                                                                                    \
-    do {                                                                                                                \
-        ACM_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_rows_tn_kernel<NTv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((gemm_rows_tn_kernel<NTv>), dim3(blocks), dim3(256), lds, st, (int)n_rows, (int)K, (int)N, X,   \
-                           (long)ldx, Dz, (long)lddz, slabs, (int)rpb, drop, rows_vecb(N, Dz, lddz));                                           \
-    } while (0)
-    switch (nt) {
-        case 1: ACM_RTN(1); break;
-        case 2: ACM_RTN(2); break;
-        case 3: ACM_RTN(3); break;
-        case 4: ACM_RTN(4); break;
-        case 5: case 6: ACM_RTN(6); break;
-        case 7: case 8: ACM_RTN(8); break;
-        case 9: case 10: ACM_RTN(10); break;
-        default: ACM_RTN(12); break;
-    }
-#undef ACM_RTN
+    const int rc = acm_pick([&](auto NT) {
+        ACM_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_rows_tn_kernel<NT()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((gemm_rows_tn_kernel<NT()>), dim3(blocks), dim3(256), lds, st, (int)n_rows, (int)K, (int)N, X,
+                           (long)ldx, Dz, (long)lddz, slabs, (int)rpb, drop, rows_vecb(N, Dz, lddz));
+        return ACM_OK;
+    }, rows_tiles(nt));
+    ACM_REQUIRE(rc != ACM_NO_INSTANTIATION, ACM_EUNSUPPORTED, "acm_gemm_rows_tn: no kernel for %d column tiles", nt);
+    if (rc != ACM_OK) return rc;
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }

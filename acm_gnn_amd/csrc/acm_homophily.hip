@@ -524,16 +524,12 @@ extern "C" int acm_class_score(int64_t n_rows, int n_features, int n_classes, co
     const size_t lds = (size_t)T * 16 * FS * sizeof(float);           // <= 64 x 256 x 4 B = 64 KB
     const int nb = hom_blocks(n_rows, 64, lds > 16384 ? 512 : 2048);
     const int vec4 = (F % 4 == 0) && (ld_z % 4 == 0) && (((uintptr_t)z & 15) == 0);
-#define ACM_SCORE_LAUNCH(TT)                                                                                                  \
-    hipLaunchKernelGGL(score_kernel<TT>, dim3(nb), dim3(256), lds, st, (long)n_rows, F, C, z, (long)ld_z, mu, (long)ld_mu,    \
-                       (const long long*)class_count, labels, (unsigned char*)row_hit, (unsigned long long*)counts, vec4)
-    switch (T) {
-        case 1: ACM_SCORE_LAUNCH(1); break;
-        case 2: ACM_SCORE_LAUNCH(2); break;
-        case 3: ACM_SCORE_LAUNCH(3); break;
-        default: ACM_SCORE_LAUNCH(4); break;
-    }
-#undef ACM_SCORE_LAUNCH
+    const int rc = acm_pick([&](auto TT) {
+        hipLaunchKernelGGL(score_kernel<TT()>, dim3(nb), dim3(256), lds, st, (long)n_rows, F, C, z, (long)ld_z, mu, (long)ld_mu,
+                           (const long long*)class_count, labels, (unsigned char*)row_hit, (unsigned long long*)counts, vec4);
+        return ACM_OK;
+    }, acm_one_of<1, 2, 3, 4>(T));
+    ACM_REQUIRE(rc == ACM_OK, ACM_EUNSUPPORTED, "acm_class_score: no score_kernel for %d class tiles", T);
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }

@@ -209,20 +209,12 @@ extern "C" int acm_proj_fwd_at(int64_t n_rows, int64_t f_in, int f_out, const fl
     if (n_rows == 0) return ACM_OK;
     hipStream_t s = (hipStream_t)stream;
     const int nblk = proj_blocks(n_rows);
-#define ACM_PF(Fv)                                                                                                  \
-    hipLaunchKernelGGL((proj_fwd_kernel<Fv>), dim3(nblk), dim3(256), 0, s, (int)n_rows, (int)f_in, X, (long)ldx, w_low, \
-                       w_high, w_mlp, (long)ldw, relu, Z_lh, (long)ld_lh, Z_i, (long)ld_i, (int)h_col)
-    switch (f_out) {
-        case 1: ACM_PF(1); break;
-        case 2: ACM_PF(2); break;
-        case 3: ACM_PF(3); break;
-        case 4: ACM_PF(4); break;
-        case 5: ACM_PF(5); break;
-        case 6: ACM_PF(6); break;
-        case 7: ACM_PF(7); break;
-        default: ACM_PF(8); break;
-    }
-#undef ACM_PF
+    const int rc = acm_pick([&](auto F) {
+        hipLaunchKernelGGL((proj_fwd_kernel<F()>), dim3(nblk), dim3(256), 0, s, (int)n_rows, (int)f_in, X, (long)ldx, w_low,
+                           w_high, w_mlp, (long)ldw, relu, Z_lh, (long)ld_lh, Z_i, (long)ld_i, (int)h_col);
+        return ACM_OK;
+    }, acm_one_of<1, 2, 3, 4, 5, 6, 7, 8>(f_out));
+    ACM_REQUIRE(rc == ACM_OK, ACM_EUNSUPPORTED, "acm_proj_fwd: no kernel for f_out = %d", f_out);
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }
@@ -254,17 +246,12 @@ extern "C" int acm_proj_bwd(int64_t n_rows, int64_t f_in, int n_out, const float
     hipStream_t s = (hipStream_t)stream;
     float* partial = (float*)workspace;
     const int nblk = proj_blocks(n_rows);
-#define ACM_PROJ(Qv)                                                                                              \
-    hipLaunchKernelGGL((proj_bwd_kernel<Qv>), dim3(nblk), dim3(256), 0, s, (int)n_rows, (int)f_in, X, (long)ldx, dZ, \
-                       (long)lddz, w_low, w_high, w_mlp, (long)ldw, dX, (long)lddx, partial)
-    switch (n_out) {
-        case 3: ACM_PROJ(3); break;
-        case 6: ACM_PROJ(6); break;
-        case 9: ACM_PROJ(9); break;
-        case 12: ACM_PROJ(12); break;
-        default: ACM_PROJ(15); break;
-    }
-#undef ACM_PROJ
+    st = acm_pick([&](auto Q) {
+        hipLaunchKernelGGL((proj_bwd_kernel<Q()>), dim3(nblk), dim3(256), 0, s, (int)n_rows, (int)f_in, X, (long)ldx, dZ,
+                           (long)lddz, w_low, w_high, w_mlp, (long)ldw, dX, (long)lddx, partial);
+        return ACM_OK;
+    }, acm_one_of<3, 6, 9, 12, 15>(n_out));
+    ACM_REQUIRE(st == ACM_OK, ACM_EUNSUPPORTED, "acm_proj_bwd: no kernel for n_out = %d", n_out);
     ACM_CHECK_HIP(hipGetLastError());
     // dW[j][q] = sum_b partial[(j * n_out + q) / 32][b][(j * n_out + q) % 32], optionally in the column-block layout of dW
     const acm_reduce_seg_t seg = {partial, nblk, 32, 0, (int32_t)(f_in * n_out), dW, n_out,

@@ -256,12 +256,11 @@ extern "C" int acm_proj_blocks_fwd(int64_t n_rows, const acm_proj_blocks_t* p, f
     hipStream_t s = (hipStream_t)stream;
     const int nblk = (int)((n_rows + PB_FWD_ROWS - 1) / PB_FWD_ROWS);
     const int tiles = (3 * p->f + 15) / 16;
-#define ACM_PBF(Tv)                                                                                                        \
-    hipLaunchKernelGGL((proj_blocks_fwd_kernel<Tv>), dim3(nblk), dim3(256), 0, s, *p, (int)n_rows, Z, (long)ldz, accumulate, relu)
-    if (tiles <= 3) ACM_PBF(3);
-    else if (tiles <= 6) ACM_PBF(6);
-    else ACM_PBF(12);
-#undef ACM_PBF
+    const int rc = acm_pick([&](auto T) {
+        hipLaunchKernelGGL((proj_blocks_fwd_kernel<T()>), dim3(nblk), dim3(256), 0, s, *p, (int)n_rows, Z, (long)ldz, accumulate, relu);
+        return ACM_OK;
+    }, acm_one_of<3, 6, 12>(tiles <= 3 ? 3 : (tiles <= 6 ? 6 : (tiles <= 12 ? 12 : tiles))));
+    ACM_REQUIRE(rc == ACM_OK, ACM_EUNSUPPORTED, "acm_proj_blocks_fwd: no kernel for %d column tiles", tiles);
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }

@@ -1338,29 +1338,23 @@ extern "C" int acm_small_step(const acm_csr_t* a, const acm_csr_t* x, const acm_
     hipStream_t s = (hipStream_t)stream;
     const Grids gr = grids_of(a, x, xt, p->train != 0);
     const int graph_wg = gr.graph, wide_wg = gr.wide;
-    const bool four = p->n_channels == 4, variant = p->relu_before != 0;
-    // launch 1
-    hipLaunchKernelGGL(small_proj1_kernel, dim3(gr.proj), dim3(256), 0, s, d1);
-    // launch 2
-    if (four && variant) hipLaunchKernelGGL((small_conv1_fwd_kernel<true, true>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
-    else if (four) hipLaunchKernelGGL((small_conv1_fwd_kernel<true, false>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
-    else if (variant) hipLaunchKernelGGL((small_conv1_fwd_kernel<false, true>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
-    else hipLaunchKernelGGL((small_conv1_fwd_kernel<false, false>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
-    // launch 3
-    if (four) hipLaunchKernelGGL(small_conv2_fwd_kernel<true>, dim3(graph_wg), dim3(64 * WAVES), 0, s, d);
-    else hipLaunchKernelGGL(small_conv2_fwd_kernel<false>, dim3(graph_wg), dim3(64 * WAVES), 0, s, d);
-    if (p->train) {
-        // launch 4
-        if (four) hipLaunchKernelGGL(small_conv2_bwd_kernel<true>, dim3(graph_wg), dim3(64 * WAVES), 0, s, d, z1);
-        else hipLaunchKernelGGL(small_conv2_bwd_kernel<false>, dim3(graph_wg), dim3(64 * WAVES), 0, s, d, z1);
-        // launch 5
-        if (four && variant) hipLaunchKernelGGL((small_conv1_bwd_kernel<true, true>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
-        else if (four) hipLaunchKernelGGL((small_conv1_bwd_kernel<true, false>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
-        else if (variant) hipLaunchKernelGGL((small_conv1_bwd_kernel<false, true>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
-        else hipLaunchKernelGGL((small_conv1_bwd_kernel<false, false>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
-        // launch 6
-        hipLaunchKernelGGL(small_finish_kernel, dim3(gr.item_blocks + gr.red_blocks), dim3(256), 0, s, d, gr.item_blocks, gr.red_blocks);
-    }
+    acm_pick([&](auto four, auto variant) {
+        // launch 1
+        hipLaunchKernelGGL(small_proj1_kernel, dim3(gr.proj), dim3(256), 0, s, d1);
+        // launch 2
+        hipLaunchKernelGGL((small_conv1_fwd_kernel<four(), variant()>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
+        // launch 3
+        hipLaunchKernelGGL(small_conv2_fwd_kernel<four()>, dim3(graph_wg), dim3(64 * WAVES), 0, s, d);
+        if (p->train) {
+            // launch 4
+            hipLaunchKernelGGL(small_conv2_bwd_kernel<four()>, dim3(graph_wg), dim3(64 * WAVES), 0, s, d, z1);
+            // launch 5
+            hipLaunchKernelGGL((small_conv1_bwd_kernel<four(), variant()>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
+            // launch 6
+            hipLaunchKernelGGL(small_finish_kernel, dim3(gr.item_blocks + gr.red_blocks), dim3(256), 0, s, d, gr.item_blocks, gr.red_blocks);
+        }
+        return ACM_OK;
+    }, acm_flag(p->n_channels == 4), acm_flag(p->relu_before != 0));
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }
@@ -1416,29 +1410,24 @@ extern "C" int acm_small_batch_step(const acm_csr_t* a, const acm_csr_t* x, cons
     const int form = form_of(four, variant, train);
     const unsigned B = (unsigned)n_slots;
     const dim3 wide(gr.wide, B), graph(gr.graph, B), blk(64 * WAVES);
-    // launch 1
-    hipLaunchKernelGGL(small_proj1_batch_kernel, dim3(gr.proj, B), dim3(256), 0, s, tb, form);
-    // launch 2
-    if (four && variant) hipLaunchKernelGGL((small_conv1_fwd_batch_kernel<true, true>), wide, blk, 0, s, tb, form);
-    else if (four) hipLaunchKernelGGL((small_conv1_fwd_batch_kernel<true, false>), wide, blk, 0, s, tb, form);
-    else if (variant) hipLaunchKernelGGL((small_conv1_fwd_batch_kernel<false, true>), wide, blk, 0, s, tb, form);
-    else hipLaunchKernelGGL((small_conv1_fwd_batch_kernel<false, false>), wide, blk, 0, s, tb, form);
-    // launch 3
-    if (four) hipLaunchKernelGGL(small_conv2_fwd_batch_kernel<true>, graph, blk, 0, s, tb, form);
-    else hipLaunchKernelGGL(small_conv2_fwd_batch_kernel<false>, graph, blk, 0, s, tb, form);
-    if (train) {
-        // launch 4
-        if (four) hipLaunchKernelGGL(small_conv2_bwd_batch_kernel<true>, graph, blk, 0, s, tb, form);
-        else hipLaunchKernelGGL(small_conv2_bwd_batch_kernel<false>, graph, blk, 0, s, tb, form);
-        // launch 5
-        if (four && variant) hipLaunchKernelGGL((small_conv1_bwd_batch_kernel<true, true>), wide, blk, 0, s, tb, form);
-        else if (four) hipLaunchKernelGGL((small_conv1_bwd_batch_kernel<true, false>), wide, blk, 0, s, tb, form);
-        else if (variant) hipLaunchKernelGGL((small_conv1_bwd_batch_kernel<false, true>), wide, blk, 0, s, tb, form);
-        else hipLaunchKernelGGL((small_conv1_bwd_batch_kernel<false, false>), wide, blk, 0, s, tb, form);
-        // launch 6
-        hipLaunchKernelGGL(small_finish_batch_kernel, dim3(gr.item_blocks + gr.red_blocks, B), dim3(256), 0, s, tb, form, gr.item_blocks,
-                           gr.red_blocks);
-    }
+    acm_pick([&](auto four_c, auto variant_c) {
+        // launch 1
+        hipLaunchKernelGGL(small_proj1_batch_kernel, dim3(gr.proj, B), dim3(256), 0, s, tb, form);
+        // launch 2
+        hipLaunchKernelGGL((small_conv1_fwd_batch_kernel<four_c(), variant_c()>), wide, blk, 0, s, tb, form);
+        // launch 3
+        hipLaunchKernelGGL(small_conv2_fwd_batch_kernel<four_c()>, graph, blk, 0, s, tb, form);
+        if (train) {
+            // launch 4
+            hipLaunchKernelGGL(small_conv2_bwd_batch_kernel<four_c()>, graph, blk, 0, s, tb, form);
+            // launch 5
+            hipLaunchKernelGGL((small_conv1_bwd_batch_kernel<four_c(), variant_c()>), wide, blk, 0, s, tb, form);
+            // launch 6
+            hipLaunchKernelGGL(small_finish_batch_kernel, dim3(gr.item_blocks + gr.red_blocks, B), dim3(256), 0, s, tb, form, gr.item_blocks,
+                               gr.red_blocks);
+        }
+        return ACM_OK;
+    }, acm_flag(four), acm_flag(variant));
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }
