@@ -9,16 +9,19 @@
 // level of the step (a level ends where the next one needs rows of OTHER nodes), everything row-local folded into the
 // gather that produces its input, every update applied where its gradient becomes final.
 //
-// Layout conventions (wave = 64 lanes = four 16-lane groups g, lane m of a group):
-//   * wide rows (64 columns): lane (g, m) owns columns 4m .. 4m+3 -- one 16-byte load per lane and row.  In a GATHER group
-//     g takes every fourth neighbour (one wave instruction fetches four 256-byte rows); in ROW MATH group g owns channel g
-//     (low, high, identity, structure): the per-channel LayerNorm / attention sums are 16-lane DPP sums, the 4 (or 3)
-//     channels run side by side, per-row scalars travel through v_readlane.
+// Layout conventions (wave = 64 lanes = four 16-lane groups g, lane m of a group).  The hidden width F is a template
+// parameter of every launch but the third, given as V = F / 16, the columns a lane owns: V = 4 (F = 64) and V = 2 (F = 32)
+// are instantiated; acm_small_step_t::hidden chooses.
+//   * wide rows (F columns): lane (g, m) owns columns V m .. V m + V - 1 -- one 4 V-byte load per lane and row.  In a GATHER
+//     group g takes every fourth neighbour (one wave instruction fetches four 4 F-byte rows); in ROW MATH group g owns
+//     channel g (low, high, identity, structure): the per-channel LayerNorm / attention sums are 16-lane DPP sums, the 4
+//     (or 3) channels run side by side, per-row scalars travel through v_readlane.
 //   * narrow rows (<= 8 columns per channel): tables of 16-byte blocks [L 8 | H 8 | S 8]; lane (e, q) fetches block q of
 //     the neighbour in slot e (eight neighbours per wave instruction); row math runs with lane c = column c.
 //   * long rows: the handle's work items (acm_csr.cpp: build_items) cut them into pieces; a piece leaves its partial sums
 //     in its slot (write-through stores), arrives at the row's counter, and the LAST piece to arrive adds the slots in slot
-//     order and runs the row's epilogue -- no second launch, no float atomics, deterministic.
+//     order and runs the row's epilogue -- no second launch, no float atomics, deterministic.  A slot is SLOT_PITCH floats
+//     whatever the width: a wide piece uses 3 F of them, a narrow one 24.
 #include <algorithm>
 #include <vector>
 
@@ -29,8 +32,15 @@
 namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
+typedef float f2 __attribute__((ext_vector_type(2)));
+// a lane's V consecutive columns of a wide row
+template <int V> struct vec_of;
+template <> struct vec_of<4> { typedef f4 type; };
+template <> struct vec_of<2> { typedef f2 type; };
+template <int V> using fv = typename vec_of<V>::type;
 
-constexpr int F = 64;                 // hidden width
+constexpr int F_MAX = 64;             // the widest hidden width: sizes the workspace for every width
+constexpr int SLOT_PITCH = 3 * F_MAX; // floats of a long row's slot
 constexpr int C8 = 8;                 // padded class count
 constexpr int WAVES = 8;              // per workgroup of the gather phases (two per SIMD: the second hides the first's latency chain)
 constexpr int MAX_WG = 512;           // workgroups of the phases that leave per-workgroup partial sums (launches 3, 4): beyond that a
@@ -38,10 +48,10 @@ constexpr int MAX_WG = 512;           // workgroups of the phases that leave per
 constexpr int MAX_WG_WIDE = 2048;     // ... of the wide gather phases (launches 2, 5): one work item per wave up to 16384 items (a
                                       // wave's item is a chain of ~2 000 dependent instructions; more waves, not longer loops, hide it)
 constexpr int RED_EL = 8;             // elements of the partial-sum vectors per reducing block of the last launch (x 32 producer lanes)
-constexpr int PART4 = 3 * F * C8 + 3 * 4 * F + 16;      // dW2 [3][64][8] | dv1 [4][64] | dgamma1 | dbeta1 | dmix1 [4][4]
+constexpr int part4_of(int f) { return 3 * f * C8 + 3 * 4 * f + 16; }      // dW2 [3][F][8] | dv1 [4][F] | dgamma1 | dbeta1 | dmix1 [4][4]
 constexpr int PART3 = 3 * 4 * C8 + 16 + 1;              // dv2 [4][8] | dgamma2 | dbeta2 | dmix2 | loss
 constexpr int PART3_PITCH = 128;
-constexpr int LONG4 = PART4;                            // a long row's record of launch 4: the row's terms in the layout of a partial
+                                                        // (= a long row's record of launch 4: the row's terms in the layout of a partial)
 
 struct SmallTensor {
     float* p;
@@ -105,15 +115,32 @@ __device__ __forceinline__ T take(const ACM_CONST_AS T& v) {
     return out;
 }
 
-__device__ __forceinline__ f4 ld4(const float* p) { return *reinterpret_cast<const f4*>(p); }
-__device__ __forceinline__ void st4(float* p, f4 v) { *reinterpret_cast<f4*>(p) = v; }
-__device__ __forceinline__ f4 zero4() { return f4{0.f, 0.f, 0.f, 0.f}; }
-__device__ __forceinline__ f4 relu4(f4 v) { return f4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)}; }
-__device__ __forceinline__ float hsum4(f4 v) { return (v.x + v.y) + (v.z + v.w); }
-__device__ __forceinline__ f4 sel4(int g, f4 a, f4 b, f4 c, f4 d) { return g == 0 ? a : (g == 1 ? b : (g == 2 ? c : d)); }
-__device__ __forceinline__ f4 xsum4(f4 v) {      // over the four 16-lane groups
+// the V-wide forms (ldv<4> .. are the 16-byte ld4 .. of the narrow rows, whose blocks are four floats at every width)
+template <int V> __device__ __forceinline__ fv<V> ldv(const float* p) { return *reinterpret_cast<const fv<V>*>(p); }
+template <int V> __device__ __forceinline__ void stv(float* p, fv<V> v) { *reinterpret_cast<fv<V>*>(p) = v; }
+template <int V> __device__ __forceinline__ fv<V> zerov() {
+    if constexpr (V == 4) return f4{0.f, 0.f, 0.f, 0.f};
+    else return f2{0.f, 0.f};
+}
+__device__ __forceinline__ f4 reluv(f4 v) { return f4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)}; }
+__device__ __forceinline__ f2 reluv(f2 v) { return f2{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f)}; }
+__device__ __forceinline__ float hsumv(f4 v) { return (v.x + v.y) + (v.z + v.w); }
+__device__ __forceinline__ float hsumv(f2 v) { return v.x + v.y; }
+template <class T>
+__device__ __forceinline__ T selv(int g, T a, T b, T c, T d) { return g == 0 ? a : (g == 1 ? b : (g == 2 ? c : d)); }
+__device__ __forceinline__ f4 xsumv(f4 v) {      // over the four 16-lane groups
     return f4{acm_cross_row_sum(v.x), acm_cross_row_sum(v.y), acm_cross_row_sum(v.z), acm_cross_row_sum(v.w)};
 }
+__device__ __forceinline__ f2 xsumv(f2 v) { return f2{acm_cross_row_sum(v.x), acm_cross_row_sum(v.y)}; }
+// v where the element of `gate` is positive, else 0 (a ReLU's or a dropout mask's backward)
+__device__ __forceinline__ f4 wherev(f4 gate, f4 v) {
+    return f4{gate.x > 0.f ? v.x : 0.f, gate.y > 0.f ? v.y : 0.f, gate.z > 0.f ? v.z : 0.f, gate.w > 0.f ? v.w : 0.f};
+}
+__device__ __forceinline__ f2 wherev(f2 gate, f2 v) { return f2{gate.x > 0.f ? v.x : 0.f, gate.y > 0.f ? v.y : 0.f}; }
+__device__ __forceinline__ f4 ld4(const float* p) { return ldv<4>(p); }
+__device__ __forceinline__ void st4(float* p, f4 v) { stv<4>(p, v); }
+__device__ __forceinline__ f4 zero4() { return zerov<4>(); }
+__device__ __forceinline__ f4 relu4(f4 v) { return reluv(v); }
 __device__ __forceinline__ float bcast_f(float v, int u) { return __int_as_float(acm_row_bcast(__float_as_int(v), u)); }
 
 // slot traffic crosses workgroups (and XCDs: each has its own L2): write-through stores, cache-bypassing loads
@@ -121,20 +148,24 @@ __device__ __forceinline__ void st_coherent(float* p, float v) { __hip_atomic_st
 __device__ __forceinline__ float ld_coherent(const float* p) {
     return __hip_atomic_load(const_cast<float*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ void st4_coherent(float* p, f4 v) {
+__device__ __forceinline__ void st_coherent(float* p, f4 v) {
     st_coherent(p, v.x), st_coherent(p + 1, v.y), st_coherent(p + 2, v.z), st_coherent(p + 3, v.w);
 }
-__device__ __forceinline__ f4 ld4_coherent(const float* p) {
-    return f4{ld_coherent(p), ld_coherent(p + 1), ld_coherent(p + 2), ld_coherent(p + 3)};
+__device__ __forceinline__ void st_coherent(float* p, f2 v) { st_coherent(p, v.x), st_coherent(p + 1, v.y); }
+template <int V> __device__ __forceinline__ fv<V> ldv_coherent(const float* p) {
+    if constexpr (V == 4) return f4{ld_coherent(p), ld_coherent(p + 1), ld_coherent(p + 2), ld_coherent(p + 3)};
+    else return f2{ld_coherent(p), ld_coherent(p + 1)};
 }
+__device__ __forceinline__ void st4_coherent(float* p, f4 v) { st_coherent(p, v); }
+__device__ __forceinline__ f4 ld4_coherent(const float* p) { return ldv_coherent<4>(p); }
 
 // ------------------------------------------------------------------------------------------------ wide gather
-// acc[c] += sum over the entries [begin, end) of an id list of  w(pos) * T_c[id(pos), 4m .. 4m+3];  group g of the wave
+// acc[c] += sum over the entries [begin, end) of an id list of  w(pos) * T_c[id(pos), V m .. V m + V - 1];  group g of the wave
 // takes the entries 4u + g.  The ids are loaded TRANSPOSED (lane (g, u) holds the id step u needs in group g), so a step
 // is one row-broadcast DPP move per lane, no LDS crossbar.  Entries past `end` read row `safe` with weight 0.
-template <int NCH, int RELU_MASK, class W>
+template <int V, int NCH, int RELU_MASK, class W>
 __device__ __forceinline__ void wide_gather(const int32_t* __restrict__ ids, int begin, int end, const float* const (&tab)[3],
-                                            const int (&ld)[3], int safe, W&& weight, f4 (&acc)[3]) {
+                                            const int (&ld)[3], int safe, W&& weight, fv<V> (&acc)[3]) {
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
     int id = safe;
     float w = 0.f;
@@ -150,18 +181,18 @@ __device__ __forceinline__ void wide_gather(const int32_t* __restrict__ ids, int
         // item per wave nothing else hides it
 #define ACM_WG_BLOCK(U0, CNT)                                                                   \
         {                                                                                       \
-            f4 v[CNT][NCH];                                                                     \
+            fv<V> v[CNT][NCH];                                                                  \
             float ww[CNT];                                                                      \
             _Pragma("unroll") for (int s = 0; s < CNT; ++s) {                                   \
                 const int j = acm_row_bcast(id, U0 + s);                                        \
                 ww[s] = bcast_f(w, U0 + s);                                                     \
                 _Pragma("unroll") for (int c = 0; c < NCH; ++c)                                 \
-                    v[s][c] = ld4(tab[c] + (long)j * ld[c] + 4 * m);                            \
+                    v[s][c] = ldv<V>(tab[c] + (long)j * ld[c] + V * m);                         \
             }                                                                                   \
             _Pragma("unroll") for (int s = 0; s < CNT; ++s)                                     \
                 _Pragma("unroll") for (int c = 0; c < NCH; ++c) {                               \
-                    f4 x = v[s][c];                                                             \
-                    if ((RELU_MASK >> c) & 1) x = relu4(x);                                     \
+                    fv<V> x = v[s][c];                                                          \
+                    if ((RELU_MASK >> c) & 1) x = reluv(x);                                     \
                     acc[c] += ww[s] * x;                                                        \
                 }                                                                               \
         }
@@ -186,7 +217,7 @@ __device__ __forceinline__ void wide_gather(const int32_t* __restrict__ ids, int
 // partial sums, `epi(row, acc)` runs once per ROW with the complete sums (in every group).
 // `pre(row)`: the loads of the row's epilogue that depend on nothing but the row number, requested BEFORE the gather (they
 // travel while the item -> ids -> rows chain runs; with one item per wave that chain is the kernel's duration).
-template <int NCH, class Pre, class Gather, class Epi>
+template <int V, int NCH, class Pre, class Gather, class Epi>
 __device__ __forceinline__ void wide_items(const ItemView& iv, float* slots, int* counters, int wave, int n_waves, Pre&& pre,
                                            Gather&& gather, Epi&& epi) {
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
@@ -194,13 +225,14 @@ __device__ __forceinline__ void wide_items(const ItemView& iv, float* slots, int
         AcmItem item = iv.items[it];
         item.row = acm_uniform(item.row), item.begin = acm_uniform(item.begin), item.end = acm_uniform(item.end), item.slot = acm_uniform(item.slot);
         auto pf = pre(item.row);
-        f4 acc[3] = {zero4(), zero4(), zero4()};
+        constexpr int F = 16 * V;
+        fv<V> acc[3] = {zerov<V>(), zerov<V>(), zerov<V>()};
         gather(item, acc);
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) acc[c] = xsum4(acc[c]);
+        for (int c = 0; c < NCH; ++c) acc[c] = xsumv(acc[c]);
         if (item.slot >= 0) {                                        // a piece of a long row (uniform branch)
-            float* sp = slots + (long)item.slot * (3 * F);
-            if (g < NCH) st4_coherent(sp + g * F + 4 * m, sel4(g, acc[0], acc[1], acc[2], acc[2]));
+            float* sp = slots + (long)item.slot * SLOT_PITCH;
+            if (g < NCH) st_coherent(sp + g * F + V * m, selv(g, acc[0], acc[1], acc[2], acc[2]));
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             const int li = iv.long_index[item.row];
             const AcmLongRow lr = iv.long_rows[li];
@@ -209,11 +241,11 @@ __device__ __forceinline__ void wide_items(const ItemView& iv, float* slots, int
             old = __builtin_amdgcn_readfirstlane(old);
             if (old != lr.slot_end - lr.slot_begin - 1) continue;    // another piece will finish the row
             if (lane == 0) __hip_atomic_store(counters + li, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            acc[0] = acc[1] = acc[2] = zero4();
+            acc[0] = acc[1] = acc[2] = zerov<V>();
             for (int q = lr.slot_begin; q < lr.slot_end; ++q) {
-                const float* qp = slots + (long)q * (3 * F) + 4 * m;
+                const float* qp = slots + (long)q * SLOT_PITCH + V * m;
 #pragma unroll
-                for (int c = 0; c < NCH; ++c) acc[c] += ld4_coherent(qp + c * F);
+                for (int c = 0; c < NCH; ++c) acc[c] += ldv_coherent<V>(qp + c * F);
             }
         }
         epi(item.row, acc, pf);
@@ -284,7 +316,7 @@ __device__ __forceinline__ void narrow_items(const ItemView& iv, float* slots, i
         f4 acc = gather(item);
         int li = -1;
         if (item.slot >= 0) {
-            float* sp = slots + (long)item.slot * (3 * F);
+            float* sp = slots + (long)item.slot * SLOT_PITCH;
             if (lane < 8 && q < NQ) st4_coherent(sp + 4 * q, acc);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             li = iv.long_index[item.row];
@@ -296,7 +328,7 @@ __device__ __forceinline__ void narrow_items(const ItemView& iv, float* slots, i
             if (lane == 0) __hip_atomic_store(counters + li, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             acc = zero4();
             if (q < NQ)
-                for (int s = lr.slot_begin; s < lr.slot_end; ++s) acc += ld4_coherent(slots + (long)s * (3 * F) + 4 * q);
+                for (int s = lr.slot_begin; s < lr.slot_end; ++s) acc += ld4_coherent(slots + (long)s * SLOT_PITCH + 4 * q);
         }
         epi(item.row, acc, pf, li);
     }
@@ -317,23 +349,36 @@ __device__ __forceinline__ float gmax8(float v) {
 }
 
 // ------------------------------------------------------------------------------------------------ Adam in an epilogue
-// the update of four consecutive elements whose gradient `g` has just become final
-__device__ __forceinline__ void adam_four(const SmallTensor& t, long i, f4 g, const AdamFactors& f, float step_size, float bc2_sqrt) {
-    const f4 p4 = ld4(t.p + i), m4 = ld4(t.m + i), v4 = ld4(t.v + i);
-    float pp[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
-    const float gg[4] = {g.x, g.y, g.z, g.w};
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-        adam_one(pp[r], gg[r], mm[r], vv[r], f.decay_eff, f.wd, f.decoupled, f.w1, f.b2, f.w2, step_size, bc2_sqrt, f.eps);
-    st4(t.p + i, f4{pp[0], pp[1], pp[2], pp[3]}), st4(t.m + i, f4{mm[0], mm[1], mm[2], mm[3]}), st4(t.v + i, f4{vv[0], vv[1], vv[2], vv[3]});
-}
+// The update of a lane's V consecutive elements of tensor T at I, whose gradient G has just become final; PF holds the
+// elements and their moments as loaded before the gather (pp / mm / vv), FC the tensor's two step factors (V is the
+// enclosing template's).  Two branches with the vector's components NAMED, as the 64-wide code had them: with the components
+// subscripted in one V-sized loop (`PF.pp[r]`, `po[r] = pp[r]`) -- in this macro or in an inlined function, both were tried
+// -- the 64-wide small_finish and small_conv1_bwd<FOUR, .> take 170 registers instead of 168 and run two waves per SIMD
+// instead of three.  A further width is a further branch.
+#define ACM_SMALL_ADAM_LANE(T, I, PF, G, AF, FC)                                                                                     \
+    if constexpr (V == 4) {                                                                                                          \
+        float pp[4] = {PF.pp.x, PF.pp.y, PF.pp.z, PF.pp.w}, mm[4] = {PF.mm.x, PF.mm.y, PF.mm.z, PF.mm.w};                            \
+        float vv[4] = {PF.vv.x, PF.vv.y, PF.vv.z, PF.vv.w};                                                                          \
+        const float gg[4] = {G.x, G.y, G.z, G.w};                                                                                    \
+        _Pragma("unroll") for (int r = 0; r < 4; ++r)                                                                                \
+            adam_one(pp[r], gg[r], mm[r], vv[r], AF.decay_eff, AF.wd, AF.decoupled, AF.w1, AF.b2, AF.w2, FC[0], FC[1], AF.eps);      \
+        st4(T.p + I, f4{pp[0], pp[1], pp[2], pp[3]}), st4(T.m + I, f4{mm[0], mm[1], mm[2], mm[3]});                                  \
+        st4(T.v + I, f4{vv[0], vv[1], vv[2], vv[3]});                                                                                \
+    } else {                                                                                                                         \
+        float pp[2] = {PF.pp.x, PF.pp.y}, mm[2] = {PF.mm.x, PF.mm.y}, vv[2] = {PF.vv.x, PF.vv.y};                                    \
+        const float gg[2] = {G.x, G.y};                                                                                              \
+        _Pragma("unroll") for (int r = 0; r < 2; ++r)                                                                                \
+            adam_one(pp[r], gg[r], mm[r], vv[r], AF.decay_eff, AF.wd, AF.decoupled, AF.w1, AF.b2, AF.w2, FC[0], FC[1], AF.eps);      \
+        stv<2>(T.p + I, f2{pp[0], pp[1]}), stv<2>(T.m + I, f2{mm[0], mm[1]}), stv<2>(T.v + I, f2{vv[0], vv[1]});                     \
+    }
 
 // What the later launches of the step read as tables, written by the first workgroup of launch 1 (both change every step):
-//   W2T  [idx = ch * 8 + c][col]: layer 2's weights, classes padded to 8 -- a lane's four columns of one output are one
-//        16-byte load, for the forward projection (launch 2) and for dH = dZ2 W2^T (launch 4) alike
+//   W2T  [idx = ch * 8 + c][col < F]: layer 2's weights, classes padded to 8 -- a lane's V columns of one output are one
+//        load, for the forward projection (launch 2) and for dH = dZ2 W2^T (launch 4) alike
 //   FACT [layer * 17 + role][2]: the step-dependent Adam factors of every tensor (double-precision pow: once, not per block)
-template <class D>
+template <int V, class D>
 __device__ __forceinline__ void write_tables(const D& d) {
+    constexpr int F = 16 * V;
     if (blockIdx.x != 0) return;
     for (int e = threadIdx.x; e < 3 * F * C8; e += blockDim.x) {
         const int idx = e / F, col = e % F, ch = idx >> 3, c = idx & 7;
@@ -349,36 +394,40 @@ __device__ __forceinline__ void write_tables(const D& d) {
 }
 
 // ------------------------------------------------------------------------------------------------ launch 1: Z1 = drop(X) Wcat
-template <class D>
+template <int V, class D>
 __device__ __forceinline__ void small_proj1_body(const D& d) {
-    write_tables(d);
+    constexpr int F = 16 * V;
+    write_tables<V>(d);
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
     const int wave = (int)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int)gridDim.x * 4;
     const AcmDropCtx dc = acm_drop_ctx(take(d.drop_in));
     const float* tab[3] = {d.t[0][ACM_SR_W_LOW].p, d.t[0][ACM_SR_W_HIGH].p, d.t[0][ACM_SR_W_MLP].p};
     const int ld[3] = {F, F, F};
     const float* __restrict__ xv = d.x_vals;
-    wide_items<3>(
+    wide_items<V, 3>(
         take(d.x), d.slots, d.counters, wave, n_waves, [](int) { return 0; },
-        [&](const AcmItem& item, f4(&acc)[3]) {
-            wide_gather<3, 0>(d.x.indices, item.begin, item.end, tab, ld, 0,
-                              [&](int pos) { return xv[pos] * acm_drop1(dc, pos, 0); }, acc);
+        [&](const AcmItem& item, fv<V>(&acc)[3]) {
+            wide_gather<V, 3, 0>(d.x.indices, item.begin, item.end, tab, ld, 0,
+                                 [&](int pos) { return xv[pos] * acm_drop1(dc, pos, 0); }, acc);
         },
-        [&](int row, f4(&acc)[3], int) {
-            if (g < 3) st4(d.Z1 + (long)row * (3 * F) + g * F + 4 * m, sel4(g, acc[0], acc[1], acc[2], acc[2]));
+        [&](int row, fv<V>(&acc)[3], int) {
+            if (g < 3) stv<V>(d.Z1 + (long)row * (3 * F) + g * F + V * m, selv(g, acc[0], acc[1], acc[2], acc[2]));
             // the structure parameter of layer 2 as a block of the narrow table (refreshed every step: it is a parameter)
             if (d.k == 4 && g == 3 && m < C8) d.T2[(long)row * 24 + 16 + m] = m < d.C ? d.t[1][ACM_SR_STRUC].p[(long)row * d.C + m] : 0.f;
         });
 }
 
 // ------------------------------------------------------------------------------------------------ launch 2: layer 1 forward
-// per-row math of a WIDE layer (64 columns), group g = channel g.  `acc` = complete gathered sums (in every group).
+// per-row math of a WIDE layer (F columns), group g = channel g.  `acc` = complete gathered sums (in every group).
+template <int V>
 struct Pre2 {
     float rs;
-    f4 own;
+    fv<V> own;
 };
-template <bool FOUR, bool VARIANT, class D>
+template <int V, bool FOUR, bool VARIANT, class D>
 __device__ __forceinline__ void small_conv1_fwd_body(const D& d, const float* z1) {
+    constexpr int F = 16 * V;
+    typedef fv<V> vt;
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
     const int wave = (int)blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = (int)gridDim.x * WAVES;
     constexpr int NCH = FOUR ? 3 : 2;
@@ -387,49 +436,49 @@ __device__ __forceinline__ void small_conv1_fwd_body(const D& d, const float* z1
     const float* tab[3] = {z1, z1 + F, FOUR ? d.t[0][ACM_SR_STRUC].p : z1};
     const int ld[3] = {3 * F, 3 * F, F};
     const bool act = g < K;
-    // this lane's channel parameters (columns 4m .. 4m+3) and its share of layer 2's weights: output idx = g + 4t
-    const f4 av = act ? ld4(d.t[0][ACM_SR_V_LOW + g].p + 4 * m) : zero4();
-    f4 gam = zero4(), bet = zero4();
-    if (d.layernorm && act) gam = ld4(d.t[0][ACM_SR_LNW_LOW + g].p + 4 * m), bet = ld4(d.t[0][ACM_SR_LNB_LOW + g].p + 4 * m);
+    // this lane's channel parameters (columns V m .. V m + V - 1) and its share of layer 2's weights: output idx = g + 4t
+    const vt av = act ? ldv<V>(d.t[0][ACM_SR_V_LOW + g].p + V * m) : zerov<V>();
+    vt gam = zerov<V>(), bet = zerov<V>();
+    if (d.layernorm && act) gam = ldv<V>(d.t[0][ACM_SR_LNW_LOW + g].p + V * m), bet = ldv<V>(d.t[0][ACM_SR_LNB_LOW + g].p + V * m);
     float mix[K][K];
 #pragma unroll
     for (int a = 0; a < K; ++a)
 #pragma unroll
         for (int b = 0; b < K; ++b) mix[a][b] = d.t[0][ACM_SR_MIX].p[a * K + b];
-    f4 w2t[6];
+    vt w2t[6];
 #pragma unroll
-    for (int t = 0; t < 6; ++t) w2t[t] = ld4(d.W2T + (g + 4 * t) * F + 4 * m);
+    for (int t = 0; t < 6; ++t) w2t[t] = ldv<V>(d.W2T + (g + 4 * t) * F + V * m);
     // the row's own terms: group 1 its Z_H row, group 2 its Z_I row, group 3 its struc_low row
     const float* own_base = g == 1 ? z1 + F : (g == 2 ? z1 + 2 * F : (FOUR ? d.t[0][ACM_SR_STRUC].p : z1));
     const int own_ld = (g == 1 || g == 2) ? 3 * F : F;
-    wide_items<NCH>(
+    wide_items<V, NCH>(
         take(d.graph), d.slots, d.counters, wave, n_waves,
         [&](int row) {
-            Pre2 pf;
+            Pre2<V> pf;
             pf.rs = d.row_scale[row];
-            pf.own = (g == 0 || (!FOUR && g == 3)) ? zero4() : ld4(own_base + (long)row * own_ld + 4 * m);
+            pf.own = (g == 0 || (!FOUR && g == 3)) ? zerov<V>() : ldv<V>(own_base + (long)row * own_ld + V * m);
             return pf;
         },
-        [&](const AcmItem& item, f4(&acc)[3]) {
-            wide_gather<NCH, VARIANT ? 3 : 0>(d.graph.indices, item.begin, item.end, tab, ld, item.row, [](int) { return 1.f; }, acc);
+        [&](const AcmItem& item, vt(&acc)[3]) {
+            wide_gather<V, NCH, VARIANT ? 3 : 0>(d.graph.indices, item.begin, item.end, tab, ld, item.row, [](int) { return 1.f; }, acc);
         },
-        [&](int row, f4(&acc)[3], const Pre2& pf) {
+        [&](int row, vt(&acc)[3], const Pre2<V>& pf) {
             const float rs = pf.rs;
-            const f4 own = pf.own;
-            f4 h;
-            if (VARIANT) h = sel4(g, rs * acc[0], relu4(own) - rs * acc[1], relu4(own), relu4(acc[2] - own));
-            else h = sel4(g, relu4(rs * acc[0]), relu4(own - rs * acc[1]), relu4(own), relu4(acc[2] - own));
-            if (!act) h = zero4();
+            const vt own = pf.own;
+            vt h;
+            if (VARIANT) h = selv(g, rs * acc[0], reluv(own) - rs * acc[1], reluv(own), reluv(acc[2] - own));
+            else h = selv(g, reluv(rs * acc[0]), reluv(own - rs * acc[1]), reluv(own), reluv(acc[2] - own));
+            if (!act) h = zerov<V>();
             float mean = 0.f, rstd = 1.f;
-            f4 hn = h;
+            vt hn = h;
             if (d.layernorm) {
-                mean = acm_group_sum<16>(hsum4(h)) * (1.0f / F);
-                const f4 dd = h - mean;
-                const float var = acm_group_sum<16>(hsum4(dd * dd)) * (1.0f / F);
+                mean = acm_group_sum<16>(hsumv(h)) * (1.0f / F);
+                const vt dd = h - mean;
+                const float var = acm_group_sum<16>(hsumv(dd * dd)) * (1.0f / F);
                 rstd = 1.0f / sqrtf(var + ACM_LN_EPS);
                 hn = dd * rstd * gam + bet;
             }
-            const float logit = acm_group_sum<16>(hsum4(hn * av));
+            const float logit = acm_group_sum<16>(hsumv(hn * av));
             const float sg = 1.0f / (1.0f + expf(-logit));
             float sig[K], tt[K], al[K];
 #pragma unroll
@@ -449,15 +498,15 @@ __device__ __forceinline__ void small_conv1_fwd_body(const D& d, const float* z1
 #pragma unroll
             for (int b = 0; b < K; ++b) al[b] /= den;
             const float my_al = g == 0 ? al[0] : (g == 1 ? al[1] : (g == 2 ? al[2] : (K == 4 ? al[K - 1] : 0.f)));
-            f4 out = d.scale * xsum4(my_al * h);
-            // the caller's dropout(relu(.)) between the layers (models.py:70)
-            out = relu4(out);
+            vt out = d.scale * xsumv(my_al * h);
+            // the caller's dropout(relu(.)) between the layers (models.py:70): element (row, column) of an [n, F] activation
+            out = reluv(out);
             if (dh.on) {
-                out.x *= acm_drop1(dh, row, 4 * m), out.y *= acm_drop1(dh, row, 4 * m + 1);
-                out.z *= acm_drop1(dh, row, 4 * m + 2), out.w *= acm_drop1(dh, row, 4 * m + 3);
+#pragma unroll
+                for (int r = 0; r < V; ++r) out[r] *= acm_drop1(dh, row, V * m + r);
             }
-            if (g == 0) st4(d.OUT1 + (long)row * F + 4 * m, out);
-            if (act) st4(d.H1 + (long)row * (4 * F) + g * F + 4 * m, h);
+            if (g == 0) stv<V>(d.OUT1 + (long)row * F + V * m, out);
+            if (act) stv<V>(d.H1 + (long)row * (4 * F) + g * F + V * m, h);
             if (m == 0 && act) {
                 float* st = d.ST1 + (long)row * 16;
                 st[g] = mean, st[4 + g] = rstd, st[8 + g] = sg, st[12 + g] = my_al;
@@ -467,7 +516,7 @@ __device__ __forceinline__ void small_conv1_fwd_body(const D& d, const float* z1
 #pragma unroll
             for (int t = 0; t < 6; ++t) {
                 const int idx = g + 4 * t, ch = idx >> 3, c = idx & 7;
-                const float s = acm_group_sum<16>(hsum4(out * w2t[t]));
+                const float s = acm_group_sum<16>(hsumv(out * w2t[t]));
                 if (m == 0 && c < d.C) {
                     if (ch < 2) d.T2[(long)row * 24 + ch * 8 + c] = s;
                     else d.Z2I[(long)row * C8 + c] = s;
@@ -671,15 +720,18 @@ __device__ __forceinline__ void small_conv2_fwd_body(const D& d) {
 }
 
 // ------------------------------------------------------------------------------------------------ launch 4: layer 2 backward gather + dH + layer 1 K3
+template <int V>
 struct Pre4 {
     float rs, gH, dzI, zL, zH, gS, sp, sm, sv;
-    f4 o, h;
+    fv<V> o, h;
     float mean, rstd, sa[8];
 };
-template <bool FOUR, class D>
+template <int V, bool FOUR, class D>
 __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1) {
-    __shared__ __attribute__((aligned(16))) float red[WAVES / 2][PART4];  // the waves' sums side by side (two rounds: 37 KB)
-    __shared__ __attribute__((aligned(16))) float w2s[3 * F * C8];        // W2T [idx][col]: 24 rows of 64, read by every row's dH
+    constexpr int F = 16 * V, PART4 = part4_of(F), LONG4 = PART4;
+    typedef fv<V> vt;
+    __shared__ __attribute__((aligned(16))) float red[WAVES / 2][PART4];  // the waves' sums side by side (two rounds: 37 KB at F = 64)
+    __shared__ __attribute__((aligned(16))) float w2s[3 * F * C8];        // W2T [idx][col]: 24 rows of F, read by every row's dH
     for (int e = 4 * threadIdx.x; e < 3 * F * C8; e += 4 * 64 * WAVES) st4(w2s + e, ld4(d.W2T + e));
     __syncthreads();
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15, c = lane & 7, wv = threadIdx.x >> 6;
@@ -691,11 +743,11 @@ __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1
     const AcmDropCtx dh = acm_drop_ctx(take(d.drop_hidden));
     const float inv_keep = dh.on ? dh.inv_keep : 1.f;
     const bool act = g < K;
-    const f4 av = act ? ld4(d.t[0][ACM_SR_V_LOW + g].p + 4 * m) : zero4();
-    f4 gam = zero4();
-    if (d.layernorm && act) gam = ld4(d.t[0][ACM_SR_LNW_LOW + g].p + 4 * m);
-    f4 bet = zero4();
-    if (d.layernorm && act) bet = ld4(d.t[0][ACM_SR_LNB_LOW + g].p + 4 * m);
+    const vt av = act ? ldv<V>(d.t[0][ACM_SR_V_LOW + g].p + V * m) : zerov<V>();
+    vt gam = zerov<V>();
+    if (d.layernorm && act) gam = ldv<V>(d.t[0][ACM_SR_LNW_LOW + g].p + V * m);
+    vt bet = zerov<V>();
+    if (d.layernorm && act) bet = ldv<V>(d.t[0][ACM_SR_LNB_LOW + g].p + V * m);
     float mix[K][K];
 #pragma unroll
     for (int a = 0; a < K; ++a)
@@ -704,15 +756,15 @@ __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1
     const AdamFactors af(take(d.hp));
     const SmallTensor ts2 = take(d.t[1][ACM_SR_STRUC]);
     const bool s2_lane = FOUR && lane < 8 && c < C;
-    f4 a_w2[6];
+    vt a_w2[6];
 #pragma unroll
-    for (int t = 0; t < 6; ++t) a_w2[t] = zero4();
-    f4 a_dv = zero4(), a_dg = zero4(), a_db = zero4();
+    for (int t = 0; t < 6; ++t) a_w2[t] = zerov<V>();
+    vt a_dv = zerov<V>(), a_dg = zerov<V>(), a_db = zerov<V>();
     float a_dm = 0.f;                                 // d(mix): lane L < 16 holds element (L >> 2, L & 3)
     narrow_items<NQ>(
         take(d.graph), d.slots, d.counters, wave, n_waves,
         [&](int row) {                                   // everything the row's epilogue reads that is not a gathered sum
-            Pre4 pf;
+            Pre4<V> pf;
             pf.rs = d.row_scale[row];
             const float* dzp = d.DZ2 + (long)row * 24;
             pf.gH = dzp[8 + c], pf.dzI = dzp[16 + c];
@@ -723,8 +775,8 @@ __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1
                 const long i = (long)row * C + c;
                 pf.sp = ts2.p[i], pf.sm = ts2.m[i], pf.sv = ts2.v[i];
             }
-            pf.o = ld4(d.OUT1 + (long)row * F + 4 * m);
-            pf.h = act ? ld4(d.H1 + (long)row * (4 * F) + g * F + 4 * m) : zero4();
+            pf.o = ldv<V>(d.OUT1 + (long)row * F + V * m);
+            pf.h = act ? ldv<V>(d.H1 + (long)row * (4 * F) + g * F + V * m) : zerov<V>();
             const float* st = d.ST1 + (long)row * 16;
             pf.mean = st[g], pf.rstd = st[4 + g];
 #pragma unroll
@@ -732,7 +784,7 @@ __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1
             return pf;
         },
         [&](const AcmItem& item) { return narrow_gather<NQ>(d.graph.indices, item.begin, item.end, d.G2, 24, item.row, false); },
-        [&](int row, f4 acc, const Pre4& pf, int li) {
+        [&](int row, f4 acc, const Pre4<V>& pf, int li) {
             const float aL = narrow_pick(acc, 0), aH = narrow_pick(acc, 1), aS = FOUR ? narrow_pick(acc, 2) : 0.f;
             float dzL = aL, dzH = pf.gH - aH;
             const float dzI = pf.dzI;
@@ -759,13 +811,13 @@ __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1
                 dz[8 + cc] = acm_lane_f(dzH, cc);
                 dz[16 + cc] = acm_lane_f(dzI, cc);
             }
-            const f4 o = pf.o;
-            // dH = dZ2 Wcat2^T (columns 4m .. 4m+3) and dWcat2 += H^T dZ2 (group g: idx = g, g + 4, ...)
+            const vt o = pf.o;
+            // dH = dZ2 Wcat2^T (columns V m .. V m + V - 1) and dWcat2 += H^T dZ2 (group g: idx = g, g + 4, ...)
             // (W2T from LDS, staged once per workgroup: as global loads its 24 rows were three dependent round trips per row)
-            f4 dH0 = zero4(), dH1 = zero4();
+            vt dH0 = zerov<V>(), dH1 = zerov<V>();
 #pragma unroll
-            for (int q = 0; q < 24; q += 2) dH0 += dz[q] * ld4(w2s + q * F + 4 * m), dH1 += dz[q + 1] * ld4(w2s + (q + 1) * F + 4 * m);
-            const f4 dH = dH0 + dH1;
+            for (int q = 0; q < 24; q += 2) dH0 += dz[q] * ldv<V>(w2s + q * F + V * m), dH1 += dz[q + 1] * ldv<V>(w2s + (q + 1) * F + V * m);
+            const vt dH = dH0 + dH1;
             if (li < 0) {
 #pragma unroll
                 for (int t = 0; t < 6; ++t) {
@@ -778,22 +830,21 @@ __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1
                 for (int t = 0; t < 6; ++t) {
                     const int idx = g + 4 * t, ch = idx >> 3, cc = idx & 7;
                     const float zz = g == 0 ? dz[4 * t] : (g == 1 ? dz[4 * t + 1] : (g == 2 ? dz[4 * t + 2] : dz[4 * t + 3]));
-                    float* rp = rec + ch * (F * C8) + (4 * m) * C8 + cc;
-                    rp[0] = zz * o.x, rp[C8] = zz * o.y, rp[2 * C8] = zz * o.z, rp[3 * C8] = zz * o.w;
+                    float* rp = rec + ch * (F * C8) + (V * m) * C8 + cc;
+#pragma unroll
+                    for (int r = 0; r < V; ++r) rp[r * C8] = zz * o[r];
                 }
             }
             // through dropout(relu(.)): the forward's output is non-zero exactly where both let the element pass
-            f4 dmix;
-            dmix.x = o.x > 0.f ? dH.x * inv_keep : 0.f, dmix.y = o.y > 0.f ? dH.y * inv_keep : 0.f;
-            dmix.z = o.z > 0.f ? dH.z * inv_keep : 0.f, dmix.w = o.w > 0.f ? dH.w * inv_keep : 0.f;
+            const vt dmix = wherev(o, dH * inv_keep);
             // row-local backward of layer 1, channel g in group g
             const float rs = pf.rs;
-            const f4 h = pf.h;
+            const vt h = pf.h;
             float sig[K], al[K];
 #pragma unroll
             for (int ch = 0; ch < K; ++ch) sig[ch] = pf.sa[ch], al[ch] = pf.sa[4 + ch];
             const float mean = pf.mean, rstd = pf.rstd;
-            const float dal_mine = d.scale * acm_group_sum<16>(hsum4(dmix * h));
+            const float dal_mine = d.scale * acm_group_sum<16>(hsumv(dmix * h));
             float dal[K], dot = 0.f;
 #pragma unroll
             for (int ch = 0; ch < K; ++ch) dal[ch] = acm_lane_f(dal_mine, 16 * ch), dot += al[ch] * dal[ch];
@@ -817,37 +868,34 @@ __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1
             }
             const float my_dl = g == 0 ? dlg[0] : (g == 1 ? dlg[1] : (g == 2 ? dlg[2] : (K == 4 ? dlg[K - 1] : 0.f)));
             const float my_al = g == 0 ? al[0] : (g == 1 ? al[1] : (g == 2 ? al[2] : (K == 4 ? al[K - 1] : 0.f)));
-            f4 xh = zero4(), hn = h;
+            vt xh = zerov<V>(), hn = h;
             if (d.layernorm) xh = (h - mean) * rstd, hn = xh * gam + bet;
-            const f4 r_dv = my_dl * hn;
-            const f4 dhn = my_dl * av;
-            f4 dln = dhn, r_dg = zero4(), r_db = zero4();
+            const vt r_dv = my_dl * hn;
+            const vt dhn = my_dl * av;
+            vt dln = dhn, r_dg = zerov<V>(), r_db = zerov<V>();
             if (d.layernorm) {
                 r_dg = dhn * xh;
                 r_db = dhn;
-                const f4 u = dhn * gam;
-                const float s1 = acm_group_sum<16>(hsum4(u)) * (1.0f / F), s2 = acm_group_sum<16>(hsum4(u * xh)) * (1.0f / F);
+                const vt u = dhn * gam;
+                const float s1 = acm_group_sum<16>(hsumv(u)) * (1.0f / F), s2 = acm_group_sum<16>(hsumv(u * xh)) * (1.0f / F);
                 dln = rstd * (u - s1 - xh * s2);
             }
-            f4 dhc = (d.scale * my_al) * dmix + dln;
+            vt dhc = (d.scale * my_al) * dmix + dln;
             const bool relu_here = !(variant && g < 2);
-            if (relu_here) {
-                dhc.x = h.x > 0.f ? dhc.x : 0.f, dhc.y = h.y > 0.f ? dhc.y : 0.f;
-                dhc.z = h.z > 0.f ? dhc.z : 0.f, dhc.w = h.w > 0.f ? dhc.w : 0.f;
-            }
-            float* g1 = d.G1 + (long)row * (3 * F) + 4 * m;
-            float* dz1 = d.DZ1 + (long)row * (3 * F) + 4 * m;
-            if (g == 0) st4(g1, rs * dhc);
-            if (g == 1) st4(g1 + F, rs * dhc), st4(dz1 + F, dhc);
-            if (g == 2) st4(dz1 + 2 * F, dhc);
-            if (FOUR && g == 3) st4(g1 + 2 * F, dhc);
+            if (relu_here) dhc = wherev(h, dhc);
+            float* g1 = d.G1 + (long)row * (3 * F) + V * m;
+            float* dz1 = d.DZ1 + (long)row * (3 * F) + V * m;
+            if (g == 0) stv<V>(g1, rs * dhc);
+            if (g == 1) stv<V>(g1 + F, rs * dhc), stv<V>(dz1 + F, dhc);
+            if (g == 2) stv<V>(dz1 + 2 * F, dhc);
+            if (FOUR && g == 3) stv<V>(g1 + 2 * F, dhc);
             if (li < 0) {
                 a_dv += r_dv, a_dg += r_dg, a_db += r_db, a_dm += r_dm;
             } else {                                      // the finisher of a long row: its terms go to the row's own record
                 float* rec = d.long4 + (long)li * LONG4 + 3 * F * C8;
-                const f4 zv = zero4();
-                st4(rec + g * F + 4 * m, act ? r_dv : zv), st4(rec + 4 * F + g * F + 4 * m, act ? r_dg : zv);
-                st4(rec + 8 * F + g * F + 4 * m, act ? r_db : zv);
+                const vt zv = zerov<V>();
+                stv<V>(rec + g * F + V * m, act ? r_dv : zv), stv<V>(rec + 4 * F + g * F + V * m, act ? r_dg : zv);
+                stv<V>(rec + 8 * F + g * F + V * m, act ? r_db : zv);
                 if (lane < 16) rec[12 * F + lane] = r_dm;
             }
         });
@@ -860,15 +908,18 @@ __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1
 #pragma unroll
             for (int t = 0; t < 6; ++t) {
                 const int idx = g + 4 * t, ch = idx >> 3, cc = idx & 7;
-                float* rp = mine + ch * (F * C8) + (4 * m) * C8 + cc;
-                if (round == 0) rp[0] = a_w2[t].x, rp[C8] = a_w2[t].y, rp[2 * C8] = a_w2[t].z, rp[3 * C8] = a_w2[t].w;
-                else rp[0] += a_w2[t].x, rp[C8] += a_w2[t].y, rp[2 * C8] += a_w2[t].z, rp[3 * C8] += a_w2[t].w;
+                float* rp = mine + ch * (F * C8) + (V * m) * C8 + cc;
+#pragma unroll
+                for (int r = 0; r < V; ++r) {
+                    if (round == 0) rp[r * C8] = a_w2[t][r];
+                    else rp[r * C8] += a_w2[t][r];
+                }
             }
-            float* r1 = mine + 3 * F * C8 + g * F + 4 * m;
-            const f4 zv = zero4();
-            const f4 v0 = act ? a_dv : zv, v1 = act ? a_dg : zv, v2 = act ? a_db : zv;
-            if (round == 0) st4(r1, v0), st4(r1 + 4 * F, v1), st4(r1 + 8 * F, v2);
-            else st4(r1, ld4(r1) + v0), st4(r1 + 4 * F, ld4(r1 + 4 * F) + v1), st4(r1 + 8 * F, ld4(r1 + 8 * F) + v2);
+            float* r1 = mine + 3 * F * C8 + g * F + V * m;
+            const vt zv = zerov<V>();
+            const vt v0 = act ? a_dv : zv, v1 = act ? a_dg : zv, v2 = act ? a_db : zv;
+            if (round == 0) stv<V>(r1, v0), stv<V>(r1 + 4 * F, v1), stv<V>(r1 + 8 * F, v2);
+            else stv<V>(r1, ldv<V>(r1) + v0), stv<V>(r1 + 4 * F, ldv<V>(r1 + 4 * F) + v1), stv<V>(r1 + 8 * F, ldv<V>(r1 + 8 * F) + v2);
             if (lane < 16) {
                 float* rm = mine + 3 * F * C8 + 12 * F + lane;
                 if (round == 0) rm[0] = a_dm;
@@ -882,11 +933,14 @@ __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1
 }
 
 // ------------------------------------------------------------------------------------------------ launch 5: layer 1 backward gather
+template <int V>
 struct Pre5 {
-    f4 a, b, pp, mm, vv;
+    fv<V> a, b, pp, mm, vv;
 };
-template <bool FOUR, bool VARIANT, class D>
+template <int V, bool FOUR, bool VARIANT, class D>
 __device__ __forceinline__ void small_conv1_bwd_body(const D& d, const float* z1) {
+    constexpr int F = 16 * V;
+    typedef fv<V> vt;
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
     const int wave = (int)blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = (int)gridDim.x * WAVES;
     constexpr int NCH = FOUR ? 3 : 2;
@@ -894,54 +948,44 @@ __device__ __forceinline__ void small_conv1_bwd_body(const D& d, const float* z1
     const int ld[3] = {3 * F, 3 * F, 3 * F};
     const AdamFactors af(take(d.hp));
     const SmallTensor ts = take(d.t[0][ACM_SR_STRUC]);
-    wide_items<NCH>(
+    wide_items<V, NCH>(
         take(d.graph), d.slots, d.counters, wave, n_waves,
         [&](int row) {
             // group 0: the ReLU mask of Z_L (ACMII); group 1: its direct term dZ_H and the mask of Z_H; group 3: G_S of the row
             // and the parameter row with its moments
-            Pre5 pf;
-            pf.a = pf.b = pf.pp = pf.mm = pf.vv = zero4();
-            const float* zr = z1 + (long)row * (3 * F) + 4 * m;
-            if (g == 0 && VARIANT) pf.b = ld4(zr);
+            Pre5<V> pf;
+            pf.a = pf.b = pf.pp = pf.mm = pf.vv = zerov<V>();
+            const float* zr = z1 + (long)row * (3 * F) + V * m;
+            if (g == 0 && VARIANT) pf.b = ldv<V>(zr);
             if (g == 1) {
-                pf.a = ld4(d.DZ1 + (long)row * (3 * F) + F + 4 * m);
-                if (VARIANT) pf.b = ld4(zr + F);
+                pf.a = ldv<V>(d.DZ1 + (long)row * (3 * F) + F + V * m);
+                if (VARIANT) pf.b = ldv<V>(zr + F);
             }
             if (FOUR && g == 3) {
-                pf.a = ld4(d.G1 + (long)row * (3 * F) + 2 * F + 4 * m);
+                pf.a = ldv<V>(d.G1 + (long)row * (3 * F) + 2 * F + V * m);
                 if (d.update) {
-                    const long i = (long)row * F + 4 * m;
-                    pf.pp = ld4(ts.p + i), pf.mm = ld4(ts.m + i), pf.vv = ld4(ts.v + i);
+                    const long i = (long)row * F + V * m;
+                    pf.pp = ldv<V>(ts.p + i), pf.mm = ldv<V>(ts.m + i), pf.vv = ldv<V>(ts.v + i);
                 }
             }
             return pf;
         },
-        [&](const AcmItem& item, f4(&acc)[3]) {
-            wide_gather<NCH, 0>(d.graph.indices, item.begin, item.end, tab, ld, item.row, [](int) { return 1.f; }, acc);
+        [&](const AcmItem& item, vt(&acc)[3]) {
+            wide_gather<V, NCH, 0>(d.graph.indices, item.begin, item.end, tab, ld, item.row, [](int) { return 1.f; }, acc);
         },
-        [&](int row, f4(&acc)[3], const Pre5& pf) {
-            float* dz1 = d.DZ1 + (long)row * (3 * F) + 4 * m;
+        [&](int row, vt(&acc)[3], const Pre5<V>& pf) {
+            float* dz1 = d.DZ1 + (long)row * (3 * F) + V * m;
             if (g == 0 || g == 1) {
-                f4 dz = g == 0 ? acc[0] : pf.a - acc[1];
-                if (VARIANT) {
-                    const f4 z = pf.b;
-                    dz.x = z.x > 0.f ? dz.x : 0.f, dz.y = z.y > 0.f ? dz.y : 0.f, dz.z = z.z > 0.f ? dz.z : 0.f, dz.w = z.w > 0.f ? dz.w : 0.f;
-                }
-                st4(dz1 + g * F, dz);
+                vt dz = g == 0 ? acc[0] : pf.a - acc[1];
+                if (VARIANT) dz = wherev(pf.b, dz);
+                stv<V>(dz1 + g * F, dz);
             } else if (FOUR && g == 3) {                   // dS = P G_S - G_S: final, the parameter row is updated in place
-                const f4 ds = acc[2] - pf.a;
-                const long i = (long)row * F + 4 * m;
-                if (ts.g) st4(ts.g + i, ds);
+                const vt ds = acc[2] - pf.a;
+                const long i = (long)row * F + V * m;
+                if (ts.g) stv<V>(ts.g + i, ds);
                 if (d.update) {
                     const float* fc = d.FACT + 2 * ACM_SR_STRUC;
-                    float pp[4] = {pf.pp.x, pf.pp.y, pf.pp.z, pf.pp.w}, mm[4] = {pf.mm.x, pf.mm.y, pf.mm.z, pf.mm.w};
-                    float vv[4] = {pf.vv.x, pf.vv.y, pf.vv.z, pf.vv.w};
-                    const float gg[4] = {ds.x, ds.y, ds.z, ds.w};
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        adam_one(pp[r], gg[r], mm[r], vv[r], af.decay_eff, af.wd, af.decoupled, af.w1, af.b2, af.w2, fc[0], fc[1], af.eps);
-                    st4(ts.p + i, f4{pp[0], pp[1], pp[2], pp[3]}), st4(ts.m + i, f4{mm[0], mm[1], mm[2], mm[3]});
-                    st4(ts.v + i, f4{vv[0], vv[1], vv[2], vv[3]});
+                    ACM_SMALL_ADAM_LANE(ts, i, pf, ds, af, fc)
                 }
             }
         });
@@ -951,8 +995,10 @@ __device__ __forceinline__ void small_conv1_bwd_body(const D& d, const float* z1
 // blocks [0, item_blocks): dW1 = drop(X)^T dZ1 by feature row (the transposed feature handle's items) + its update;
 // blocks behind: RED_EL elements of the two partial-sum vectors per block (sum over the producer workgroups and the long
 // rows' records, then the update).  The first block advances the step counters.
-template <class D>
+template <int V, class D>
 __device__ __forceinline__ void small_finish_body(const D& d, int item_blocks, int red_blocks) {
+    constexpr int F = 16 * V, PART4 = part4_of(F), LONG4 = PART4;
+    typedef fv<V> vt;
     __shared__ float red8[256 / RED_EL][RED_EL];
     const float* __restrict__ fact = d.FACT;              // step factors of every tensor (launch 1 wrote them)
     const AdamFactors af(take(d.hp));
@@ -976,42 +1022,35 @@ __device__ __forceinline__ void small_finish_body(const D& d, int item_blocks, i
         const float* __restrict__ xv = d.x_vals;
         const float* __restrict__ xtv = d.xt_vals;
         const int32_t* __restrict__ sp = d.xt_src_pos;
-        wide_items<3>(
+        wide_items<V, 3>(
             take(d.xt), d.slots, d.counters, wave, n_waves,
             [&](int frow) {                                // the weight rows this wave will update, with their moments
-                Pre5 pf;
-                pf.a = pf.b = pf.pp = pf.mm = pf.vv = zero4();
+                Pre5<V> pf;
+                pf.a = pf.b = pf.pp = pf.mm = pf.vv = zerov<V>();
                 if (g < 3 && d.update) {
                     const SmallTensor t = take(d.t[0][ACM_SR_W_LOW + g]);
-                    const long i = (long)frow * F + 4 * m;
-                    pf.pp = ld4(t.p + i), pf.mm = ld4(t.m + i), pf.vv = ld4(t.v + i);
+                    const long i = (long)frow * F + V * m;
+                    pf.pp = ldv<V>(t.p + i), pf.mm = ldv<V>(t.m + i), pf.vv = ldv<V>(t.v + i);
                 }
                 return pf;
             },
-            [&](const AcmItem& item, f4(&acc)[3]) {
+            [&](const AcmItem& item, vt(&acc)[3]) {
                 if (xtv)
-                    wide_gather<3, 0>(d.xt.indices, item.begin, item.end, tab, ld, 0,
-                                      [&](int pos) { return xtv[pos] * acm_drop1(dc, sp[pos], 0); }, acc);
+                    wide_gather<V, 3, 0>(d.xt.indices, item.begin, item.end, tab, ld, 0,
+                                         [&](int pos) { return xtv[pos] * acm_drop1(dc, sp[pos], 0); }, acc);
                 else
-                    wide_gather<3, 0>(d.xt.indices, item.begin, item.end, tab, ld, 0,
-                                      [&](int pos) { const int s = sp[pos]; return xv[s] * acm_drop1(dc, s, 0); }, acc);
+                    wide_gather<V, 3, 0>(d.xt.indices, item.begin, item.end, tab, ld, 0,
+                                         [&](int pos) { const int s = sp[pos]; return xv[s] * acm_drop1(dc, s, 0); }, acc);
             },
-            [&](int frow, f4(&acc)[3], const Pre5& pf) {
+            [&](int frow, vt(&acc)[3], const Pre5<V>& pf) {
                 if (g < 3) {
-                    const f4 gw = sel4(g, acc[0], acc[1], acc[2], acc[2]);
+                    const vt gw = selv(g, acc[0], acc[1], acc[2], acc[2]);
                     const SmallTensor t = take(d.t[0][ACM_SR_W_LOW + g]);
-                    const long i = (long)frow * F + 4 * m;
-                    if (t.g) st4(t.g + i, gw);
+                    const long i = (long)frow * F + V * m;
+                    if (t.g) stv<V>(t.g + i, gw);
                     if (d.update) {
                         const float* fc = fact + 2 * (ACM_SR_W_LOW + g);
-                        float pp[4] = {pf.pp.x, pf.pp.y, pf.pp.z, pf.pp.w}, mm[4] = {pf.mm.x, pf.mm.y, pf.mm.z, pf.mm.w};
-                        float vv[4] = {pf.vv.x, pf.vv.y, pf.vv.z, pf.vv.w};
-                        const float gg[4] = {gw.x, gw.y, gw.z, gw.w};
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            adam_one(pp[r], gg[r], mm[r], vv[r], af.decay_eff, af.wd, af.decoupled, af.w1, af.b2, af.w2, fc[0], fc[1], af.eps);
-                        st4(t.p + i, f4{pp[0], pp[1], pp[2], pp[3]}), st4(t.m + i, f4{mm[0], mm[1], mm[2], mm[3]});
-                        st4(t.v + i, f4{vv[0], vv[1], vv[2], vv[3]});
+                        ACM_SMALL_ADAM_LANE(t, i, pf, gw, af, fc)
                     }
                 }
             });
@@ -1106,77 +1145,88 @@ __device__ __forceinline__ void small_finish_body(const D& d, int item_blocks, i
 // / latch: the same instructions in the same order, the same bits.
 struct SmallBatchEntry {
     int32_t active;                  // 0: an empty slot -- every launch returns before it touches anything else
-    int32_t key[6];                  // per launch: gridDim.x * 8 + form (four | variant << 1 | train << 2) the entry was bound
-    int32_t item_blocks;             // for: a grid row of any other launch shape does nothing (part3 / part4 are sized by it)
+    int32_t key[6];                  // per launch: gridDim.x * 16 + form (four | variant << 1 | train << 2 | (F == 32) << 3) the
+    int32_t item_blocks;             // entry was bound for: a grid row of any other launch shape -- or of the other hidden width,
+                                     // whose kernels read every table at another pitch -- does nothing
     SmallDev first;                  // launch 1: reads the live dropout counter and latches it
     SmallDev rest;                   // launches 2-6: draw their masks with the latched copy
 };
-template <int LAUNCH>
+constexpr int FORM_NARROW = 8;       // the form's width bit: set for F = 32
+// V: the width the calling kernel was compiled for (it, not the host's word, decides the form's width bit); 0: a kernel
+// that is the same for every width (launch 3), which takes the bit as it is given
+template <int LAUNCH, int V>
 __device__ __forceinline__ const ACM_CONST_AS SmallBatchEntry* batch_entry(const SmallBatchEntry* table, int form) {
     const ACM_CONST_AS SmallBatchEntry* e = (const ACM_CONST_AS SmallBatchEntry*)table + blockIdx.y;
-    if (e->active == 0 || e->key[LAUNCH] != (int)gridDim.x * 8 + form) return nullptr;
+    if (V != 0) form = (form & (FORM_NARROW - 1)) | (V == 2 ? FORM_NARROW : 0);
+    if (e->active == 0 || e->key[LAUNCH] != (int)gridDim.x * 16 + form) return nullptr;
     return e;
 }
-__host__ __device__ constexpr int form_of(bool four, bool variant, bool train) { return (four ? 1 : 0) | (variant ? 2 : 0) | (train ? 4 : 0); }
-
-__global__ __launch_bounds__(256) void small_proj1_kernel(SmallDev d) { small_proj1_body(d); }
-__global__ __launch_bounds__(256) void small_proj1_batch_kernel(const SmallBatchEntry* table, int form) {
-    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<0>(table, form);
-    if (!e) return;
-    const ACM_CONST_AS SmallDev& d = e->first;
-    small_proj1_body(d);
+__host__ __device__ constexpr int form_of(bool four, bool variant, bool train, int hidden) {
+    return (four ? 1 : 0) | (variant ? 2 : 0) | (train ? 4 : 0) | (hidden == 32 ? FORM_NARROW : 0);
 }
 
-template <bool FOUR, bool VARIANT>
-__global__ __launch_bounds__(64 * WAVES) void small_conv1_fwd_kernel(SmallDev d, const float* z1) { small_conv1_fwd_body<FOUR, VARIANT>(d, z1); }
-template <bool FOUR, bool VARIANT>
+template <int V>
+__global__ __launch_bounds__(256) void small_proj1_kernel(SmallDev d) { small_proj1_body<V>(d); }
+template <int V>
+__global__ __launch_bounds__(256) void small_proj1_batch_kernel(const SmallBatchEntry* table, int form) {
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<0, V>(table, form);
+    if (!e) return;
+    const ACM_CONST_AS SmallDev& d = e->first;
+    small_proj1_body<V>(d);
+}
+
+template <int V, bool FOUR, bool VARIANT>
+__global__ __launch_bounds__(64 * WAVES) void small_conv1_fwd_kernel(SmallDev d, const float* z1) { small_conv1_fwd_body<V, FOUR, VARIANT>(d, z1); }
+template <int V, bool FOUR, bool VARIANT>
 __global__ __launch_bounds__(64 * WAVES) void small_conv1_fwd_batch_kernel(const SmallBatchEntry* table, int form) {
-    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<1>(table, form);
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<1, V>(table, form);
     if (!e) return;
     const ACM_CONST_AS SmallDev& d = e->rest;
-    small_conv1_fwd_body<FOUR, VARIANT>(d, d.Z1);
+    small_conv1_fwd_body<V, FOUR, VARIANT>(d, d.Z1);
 }
 
 template <bool FOUR>
 __global__ __launch_bounds__(64 * WAVES) void small_conv2_fwd_kernel(SmallDev d) { small_conv2_fwd_body<FOUR>(d); }
 template <bool FOUR>
 __global__ __launch_bounds__(64 * WAVES) void small_conv2_fwd_batch_kernel(const SmallBatchEntry* table, int form) {
-    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<2>(table, form);
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<2, 0>(table, form);
     if (!e) return;
     const ACM_CONST_AS SmallDev& d = e->rest;
     small_conv2_fwd_body<FOUR>(d);
 }
 
-template <bool FOUR>
-__global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_kernel(SmallDev d, const float* z1) { small_conv2_bwd_body<FOUR>(d, z1); }
-template <bool FOUR>
+template <int V, bool FOUR>
+__global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_kernel(SmallDev d, const float* z1) { small_conv2_bwd_body<V, FOUR>(d, z1); }
+template <int V, bool FOUR>
 __global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_batch_kernel(const SmallBatchEntry* table, int form) {
-    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<3>(table, form);
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<3, V>(table, form);
     if (!e) return;
     const ACM_CONST_AS SmallDev& d = e->rest;
-    small_conv2_bwd_body<FOUR>(d, d.Z1);
+    small_conv2_bwd_body<V, FOUR>(d, d.Z1);
 }
 
-template <bool FOUR, bool VARIANT>
-__global__ __launch_bounds__(64 * WAVES) void small_conv1_bwd_kernel(SmallDev d, const float* z1) { small_conv1_bwd_body<FOUR, VARIANT>(d, z1); }
-template <bool FOUR, bool VARIANT>
+template <int V, bool FOUR, bool VARIANT>
+__global__ __launch_bounds__(64 * WAVES) void small_conv1_bwd_kernel(SmallDev d, const float* z1) { small_conv1_bwd_body<V, FOUR, VARIANT>(d, z1); }
+template <int V, bool FOUR, bool VARIANT>
 __global__ __launch_bounds__(64 * WAVES) void small_conv1_bwd_batch_kernel(const SmallBatchEntry* table, int form) {
-    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<4>(table, form);
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<4, V>(table, form);
     if (!e) return;
     const ACM_CONST_AS SmallDev& d = e->rest;
-    small_conv1_bwd_body<FOUR, VARIANT>(d, d.Z1);
+    small_conv1_bwd_body<V, FOUR, VARIANT>(d, d.Z1);
 }
 
-__global__ __launch_bounds__(256) void small_finish_kernel(SmallDev d, int item_blocks, int red_blocks) { small_finish_body(d, item_blocks, red_blocks); }
+template <int V>
+__global__ __launch_bounds__(256) void small_finish_kernel(SmallDev d, int item_blocks, int red_blocks) { small_finish_body<V>(d, item_blocks, red_blocks); }
 // (three waves per SIMD like the single form: without the hint the table pointer costs four registers and an occupancy step)
 // Three waves per SIMD like the single form.  Left alone the compiler takes 172 registers here (the single form: 168, the
 // limit for three waves) and drops to two; held to three it parks two loop-invariant addresses in scratch (20 bytes per lane:
 // stored once per wave, read back once per work item).  EXPERIMENTS.md has the table.
+template <int V>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void small_finish_batch_kernel(const SmallBatchEntry* table, int form, int item_blocks, int red_blocks) {
-    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<5>(table, form);
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<5, V>(table, form);
     if (!e || e->item_blocks != item_blocks) return;
     const ACM_CONST_AS SmallDev& d = e->rest;
-    small_finish_body(d, item_blocks, red_blocks);
+    small_finish_body<V>(d, item_blocks, red_blocks);
 }
 
 ItemView view_of(const acm_csr* a) {
@@ -1193,7 +1243,11 @@ struct Layout {
     size_t Z1, H1, ST1, OUT1, T2, Z2I, G2, DZ2, G1, DZ1, slots, part3, part4, W2T, FACT, latch, long3, long4, counters, total;
 };
 
+// The carve-up is the widest width's at every width (acm_small_step_workspace_bytes takes no shape): a narrower step uses
+// the front of each block at its own pitch.  One function for the single and the batched form: they carve identically.
 Layout layout_of(const acm_csr* a, const acm_csr* x, const acm_csr* xt) {
+    constexpr int F = F_MAX, PART4 = part4_of(F_MAX), LONG4 = PART4;
+    static_assert(SLOT_PITCH == 192 && 3 * F == 192 && 4 * F == 256, "the block sizes below are written out for F_MAX = 64");
     const size_t n = (size_t)a->n_rows;
     // the slot buffer and the arrival counters serve one launch at a time: sized for the handle with the most pieces
     size_t n_slots = (size_t)a->n_slots, n_long = (size_t)a->n_long;
@@ -1229,11 +1283,12 @@ extern "C" int acm_small_step_workspace_bytes(const acm_csr_t* a_low, const acm_
 
 namespace {
 
-// The grids of the six launches: functions of the handles alone, so the same for every slot of a batch.
+// The grids of the six launches: functions of the handles and the hidden width alone, so the same for every slot of a batch.
 struct Grids {
     int proj, wide, graph, item_blocks, red_blocks;
 };
-Grids grids_of(const acm_csr* a, const acm_csr* x, const acm_csr* xt, bool train) {
+Grids grids_of(const acm_csr* a, const acm_csr* x, const acm_csr* xt, bool train, int hidden) {
+    const int PART4 = part4_of(hidden);
     Grids g;
     g.proj = std::max((int)std::min<int64_t>(2 * MAX_WG, (x->n_items + 3) / 4), 1);
     g.graph = (int)std::min<int64_t>(MAX_WG, (a->n_items + WAVES - 1) / WAVES);
@@ -1247,6 +1302,7 @@ Grids grids_of(const acm_csr* a, const acm_csr* x, const acm_csr* xt, bool train
 // d for launches 2-6 (the latched one).  Shared by acm_small_step and acm_small_batch_bind: one envelope, one set of refusals.
 int small_prepare(const acm_csr* a, const acm_csr* x, const acm_csr* xt, const acm_small_step_t* p, SmallDev& d1, SmallDev& d) {
     ACM_REQUIRE(a && p, ACM_EINVAL, "acm_small_step: NULL argument");
+    ACM_REQUIRE(acm_small_hidden_ok(p->hidden), ACM_EUNSUPPORTED, "acm_small_step: hidden width %d (32 or 64; 0 means 64)", (int)p->hidden);
     ACM_REQUIRE(a->vals == nullptr && a->n_rows == a->n_cols, ACM_EUNSUPPORTED,
                 "acm_small_step: pattern-only square operators only (acm_csr_create with vals = NULL)");
     ACM_REQUIRE(a->n_rows >= 1 && a->n_rows <= 16384, ACM_EUNSUPPORTED, "acm_small_step: 1 .. 16384 rows (got %lld)", (long long)a->n_rows);
@@ -1307,7 +1363,7 @@ int small_prepare(const acm_csr* a, const acm_csr* x, const acm_csr* xt, const a
     d1 = d;                                        // launch 1 reads the live dropout counter and latches it for the others
     if (d.drop_in.p > 0.f) d.drop_in.step = d.latch;
     if (d.drop_hidden.p > 0.f) d.drop_hidden.step = d.latch;
-    d.nwg3 = d.nwg4 = grids_of(a, x, xt, p->train != 0).graph;
+    d.nwg3 = d.nwg4 = grids_of(a, x, xt, p->train != 0, acm_small_hidden_of(p)).graph;
     return ACM_OK;
 }
 
@@ -1317,6 +1373,7 @@ int batch_shape_check(const acm_csr* a, const acm_csr* x, const acm_csr* xt, int
     ACM_REQUIRE(n_slots <= ACM_SMALL_BATCH_MAX, ACM_EUNSUPPORTED, "acm_small_batch: n_slots %d > %d slots of one table", (int)n_slots,
                 ACM_SMALL_BATCH_MAX);
     ACM_REQUIRE(a && x && shape, ACM_EINVAL, "acm_small_batch: NULL argument");
+    ACM_REQUIRE(acm_small_hidden_ok(shape->hidden), ACM_EUNSUPPORTED, "acm_small_batch: hidden width %d (32 or 64; 0 means 64)", (int)shape->hidden);
     ACM_REQUIRE(shape->n_channels == 3 || shape->n_channels == 4, ACM_EINVAL, "acm_small_batch: n_channels must be 3 or 4");
     ACM_REQUIRE(a->n_rows >= 1 && a->n_rows <= 16384 && a->vals == nullptr && a->n_rows == a->n_cols, ACM_EUNSUPPORTED,
                 "acm_small_batch: pattern-only square operators of 1 .. 16384 rows");
@@ -1336,28 +1393,32 @@ extern "C" int acm_small_step(const acm_csr_t* a, const acm_csr_t* x, const acm_
     if (st != ACM_OK) return st;
     const float* z1 = d.Z1;
     hipStream_t s = (hipStream_t)stream;
-    const Grids gr = grids_of(a, x, xt, p->train != 0);
+    const int hidden = acm_small_hidden_of(p);
+    const Grids gr = grids_of(a, x, xt, p->train != 0, hidden);
     const int graph_wg = gr.graph, wide_wg = gr.wide;
-    acm_pick([&](auto four, auto variant) {
+    const int picked = acm_pick([&](auto v, auto four, auto variant) {
         // launch 1
-        hipLaunchKernelGGL(small_proj1_kernel, dim3(gr.proj), dim3(256), 0, s, d1);
+        hipLaunchKernelGGL(small_proj1_kernel<v()>, dim3(gr.proj), dim3(256), 0, s, d1);
         // launch 2
-        hipLaunchKernelGGL((small_conv1_fwd_kernel<four(), variant()>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
+        hipLaunchKernelGGL((small_conv1_fwd_kernel<v(), four(), variant()>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
         // launch 3
         hipLaunchKernelGGL(small_conv2_fwd_kernel<four()>, dim3(graph_wg), dim3(64 * WAVES), 0, s, d);
         if (p->train) {
             // launch 4
-            hipLaunchKernelGGL(small_conv2_bwd_kernel<four()>, dim3(graph_wg), dim3(64 * WAVES), 0, s, d, z1);
+            hipLaunchKernelGGL((small_conv2_bwd_kernel<v(), four()>), dim3(graph_wg), dim3(64 * WAVES), 0, s, d, z1);
             // launch 5
-            hipLaunchKernelGGL((small_conv1_bwd_kernel<four(), variant()>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
+            hipLaunchKernelGGL((small_conv1_bwd_kernel<v(), four(), variant()>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
             // launch 6
-            hipLaunchKernelGGL(small_finish_kernel, dim3(gr.item_blocks + gr.red_blocks), dim3(256), 0, s, d, gr.item_blocks, gr.red_blocks);
+            hipLaunchKernelGGL(small_finish_kernel<v()>, dim3(gr.item_blocks + gr.red_blocks), dim3(256), 0, s, d, gr.item_blocks, gr.red_blocks);
         }
         return ACM_OK;
-    }, acm_flag(p->n_channels == 4), acm_flag(p->relu_before != 0));
+    }, acm_one_of<2, 4>(hidden / 16), acm_flag(p->n_channels == 4), acm_flag(p->relu_before != 0));
+    ACM_REQUIRE(picked != ACM_NO_INSTANTIATION, ACM_EUNSUPPORTED, "acm_small_step: no kernels for hidden width %d", hidden);
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }
+
+extern "C" int acm_small_step_has_hidden(int32_t hidden) { return acm_small_hidden_ok(hidden) ? 1 : 0; }
 
 extern "C" int acm_small_batch_table_bytes(int32_t n_slots, size_t* bytes) {
     ACM_REQUIRE(bytes, ACM_EINVAL, "acm_small_batch_table_bytes: NULL argument");
@@ -1385,10 +1446,11 @@ extern "C" int acm_small_batch_bind(const acm_csr_t* a, const acm_csr_t* x, cons
         if (!p) continue;
         const int st = small_prepare(a, x, xt, p, e.first, e.rest);
         if (st != ACM_OK) return st;
-        const Grids gr = grids_of(a, x, xt, p->train != 0);
-        const int form = form_of(p->n_channels == 4, p->relu_before != 0, p->train != 0);
+        const int hidden = acm_small_hidden_of(p);
+        const Grids gr = grids_of(a, x, xt, p->train != 0, hidden);
+        const int form = form_of(p->n_channels == 4, p->relu_before != 0, p->train != 0, hidden);
         const int gx[6] = {gr.proj, gr.wide, gr.graph, gr.graph, gr.wide, gr.item_blocks + gr.red_blocks};
-        for (int l = 0; l < 6; ++l) e.key[l] = gx[l] * 8 + form;
+        for (int l = 0; l < 6; ++l) e.key[l] = gx[l] * 16 + form;
         e.item_blocks = gr.item_blocks;
         e.active = 1;
     }
@@ -1406,28 +1468,30 @@ extern "C" int acm_small_batch_step(const acm_csr_t* a, const acm_csr_t* x, cons
     const SmallBatchEntry* tb = (const SmallBatchEntry*)table;
     hipStream_t s = (hipStream_t)stream;
     const bool train = shape->train != 0, four = shape->n_channels == 4, variant = shape->relu_before != 0;
-    const Grids gr = grids_of(a, x, xt, train);
-    const int form = form_of(four, variant, train);
+    const int hidden = acm_small_hidden_of(shape);
+    const Grids gr = grids_of(a, x, xt, train, hidden);
+    const int form = form_of(four, variant, train, hidden);
     const unsigned B = (unsigned)n_slots;
     const dim3 wide(gr.wide, B), graph(gr.graph, B), blk(64 * WAVES);
-    acm_pick([&](auto four_c, auto variant_c) {
+    const int picked = acm_pick([&](auto v, auto four_c, auto variant_c) {
         // launch 1
-        hipLaunchKernelGGL(small_proj1_batch_kernel, dim3(gr.proj, B), dim3(256), 0, s, tb, form);
+        hipLaunchKernelGGL(small_proj1_batch_kernel<v()>, dim3(gr.proj, B), dim3(256), 0, s, tb, form);
         // launch 2
-        hipLaunchKernelGGL((small_conv1_fwd_batch_kernel<four_c(), variant_c()>), wide, blk, 0, s, tb, form);
+        hipLaunchKernelGGL((small_conv1_fwd_batch_kernel<v(), four_c(), variant_c()>), wide, blk, 0, s, tb, form);
         // launch 3
         hipLaunchKernelGGL(small_conv2_fwd_batch_kernel<four_c()>, graph, blk, 0, s, tb, form);
         if (train) {
             // launch 4
-            hipLaunchKernelGGL(small_conv2_bwd_batch_kernel<four_c()>, graph, blk, 0, s, tb, form);
+            hipLaunchKernelGGL((small_conv2_bwd_batch_kernel<v(), four_c()>), graph, blk, 0, s, tb, form);
             // launch 5
-            hipLaunchKernelGGL((small_conv1_bwd_batch_kernel<four_c(), variant_c()>), wide, blk, 0, s, tb, form);
+            hipLaunchKernelGGL((small_conv1_bwd_batch_kernel<v(), four_c(), variant_c()>), wide, blk, 0, s, tb, form);
             // launch 6
-            hipLaunchKernelGGL(small_finish_batch_kernel, dim3(gr.item_blocks + gr.red_blocks, B), dim3(256), 0, s, tb, form, gr.item_blocks,
-                               gr.red_blocks);
+            hipLaunchKernelGGL(small_finish_batch_kernel<v()>, dim3(gr.item_blocks + gr.red_blocks, B), dim3(256), 0, s, tb, form,
+                               gr.item_blocks, gr.red_blocks);
         }
         return ACM_OK;
-    }, acm_flag(four), acm_flag(variant));
+    }, acm_one_of<2, 4>(hidden / 16), acm_flag(four), acm_flag(variant));
+    ACM_REQUIRE(picked != ACM_NO_INSTANTIATION, ACM_EUNSUPPORTED, "acm_small_batch_step: no kernels for hidden width %d", hidden);
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }

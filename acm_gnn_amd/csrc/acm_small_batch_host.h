@@ -11,6 +11,11 @@
 
 #include "acm_hip.h"
 
+// The hidden width a block asks for: acm_small_step_t::hidden, where 0 (a caller from before the field had a meaning) is 64.
+inline int acm_small_hidden_of(const acm_small_step_t* p) { return p->hidden == 0 ? 64 : (int)p->hidden; }
+// the widths the kernels are instantiated for
+inline bool acm_small_hidden_ok(int32_t hidden) { return hidden == 0 || hidden == 32 || hidden == 64; }
+
 // [a, a + alen) and [b, b + blen) share a byte (no sum of an address and a length is formed: a range may end at the top of
 // the address space)
 inline bool acm_ranges_overlap(uintptr_t a, size_t alen, uintptr_t b, size_t blen) {
@@ -55,6 +60,7 @@ inline int acm_small_batch_check_slots(int n_slots, const acm_small_step_t* cons
         else if (p->train != s->train) what = "train";
         else if (p->update != s->update) what = "update";
         else if (p->f_in != s->f_in) what = "f_in";
+        else if (acm_small_hidden_of(p) != acm_small_hidden_of(s)) what = "hidden";
         else if (p->x_vals != s->x_vals) what = "x_vals";
         else if (p->xt_vals != s->xt_vals) what = "xt_vals";
         else if (p->xt_src_pos != s->xt_src_pos) what = "xt_src_pos";

@@ -8,7 +8,7 @@ autograd graph, no per-kernel Python dispatch, parameters updated in place by th
 (the optimizer's own ``state`` tensors are used, so ``state_dict`` / checkpoints / a later switch to the general path see
 exactly what ``optimizer.step()`` would have left).
 
-Envelope: ``GCN`` of model_type acmgcn | acmgcnp, two layers, hidden width 64, <= 8 classes, <= 16384 nodes, pattern-only
+Envelope: ``GCN`` of model_type acmgcn | acmgcnp, two layers, hidden width 32 or 64, <= 8 classes, <= 16384 nodes, pattern-only
 operators on one device, CSR features (``graph.SparseFeatures``, or dense features the model's ``auto_csr`` turns into one),
 counter-based dropout (or none), this package's FusedAdam / FusedAdamW with one parameter group.  Anything else stays on
 the general path (``why_not`` says why).
@@ -23,8 +23,18 @@ from .graph import FilterOperators, SparseFeatures, _device_ctx, _stream
 _F32 = torch.float32
 _ON_DEVICE = lambda t: t.is_cuda          # noqa: E731  (the CPU test double of the library lifts this guard)
 MAX_ROWS = 16384
-HIDDEN = 64
+HIDDEN = (32, 64)                         # the widths acm_small.hip instantiates
 MAX_CLASSES = 8
+
+
+def hidden_widths(lib=None):
+    """The hidden widths the loaded library's small step runs.  The real library always has ``acm_small_step_has_hidden``
+    (``_lib`` requires every declared symbol); the object without it is the CPU test double (tests/fake_lib.py), whose small
+    step has 64 written in and ignores the struct's ``hidden`` field, so only 64 is offered to it."""
+    probe = getattr(lib if lib is not None else _lib.load(), "acm_small_step_has_hidden", None)
+    if probe is None:
+        return (64,)
+    return tuple(w for w in HIDDEN if probe(w))
 
 _ROLE_NAMES = {
     _lib.SR_W_LOW: "weight_low", _lib.SR_W_HIGH: "weight_high", _lib.SR_W_MLP: "weight_mlp",
@@ -93,8 +103,9 @@ class SmallPlan:
         if gcns is None or len(gcns) != 2:
             return "not a two-layer model"
         l0, l1 = gcns
-        if l0.out_features != HIDDEN or l1.in_features != HIDDEN:
-            return f"hidden width {l0.out_features} (64)"
+        widths = hidden_widths()
+        if l0.out_features not in widths or l1.in_features != l0.out_features:
+            return f"hidden width {l0.out_features} ({' | '.join(map(str, widths))})"
         if not 1 <= l1.out_features <= MAX_CLASSES:
             return f"{l1.out_features} classes (<= {MAX_CLASSES})"
         c0, c1 = l0._config(), l1._config()
@@ -147,8 +158,8 @@ class SmallPlan:
         cfg = l0._config()
         self.cfg = cfg
         n, dev = ops.low.n_rows, x.values.device
-        self.n, self.C = n, l1.out_features
-        self.train = labels is not None                  # labels + row weights: a training plan; neither: evaluation
+        self.n, self.C, self.hidden = n, l1.out_features, l0.out_features
+        self.train = labels is not None                 # labels + row weights: a training plan; neither: evaluation
         self._xt = x.csr_t if self.train else None
         self.low = self._operator(ops)
         nbytes = C.c_size_t()
@@ -165,6 +176,9 @@ class SmallPlan:
         self._keep = []
         p = self.p = _lib.SmallStep()
         p.n_classes, p.n_channels, p.relu_before, p.layernorm = self.C, cfg.n_channels, int(cfg.relu_before), int(cfg.layernorm)
+        # every width-dependent buffer of a plan is either the model's own (parameters, `grads` as zeros_like of them, the
+        # optimizer's state) or sized for the widest width by the library (the workspace): the width is this one field
+        p.hidden = self.hidden
         self.update = bool(update) and self.train and optimizer is not None
         self.grads = {}
         if self.train and (keep_grads or not self.update):
@@ -310,6 +324,8 @@ class SmallBatch:
             if (p.cfg.n_channels, p.cfg.relu_before, p.cfg.layernorm, p.cfg.scale) != \
                     (first.cfg.n_channels, first.cfg.relu_before, first.cfg.layernorm, first.cfg.scale):
                 return "the models are configured differently"
+            if p.hidden != first.hidden:
+                return f"hidden widths {p.hidden} and {first.hidden}: the models are configured differently"
             if p.C != first.C:
                 return f"{p.C} and {first.C} classes"
             if p.x is not first.x:

@@ -951,8 +951,8 @@ def fit_batched(runs, x, adj, labels, epochs, rule="min_val_loss", early_stoppin
     ``batch``: slots (1 .. 32).  Default 8: the smallest measured size within 3 % of the best size on the Squirrel-shaped
     workload (scripts/bench_batched_fit.py, profiles/batched_fit.jsonl).
 
-    Where ``SmallPlan.why_not`` or ``SmallBatch.why_not`` objects (a model outside the small-graph envelope, runs that differ in
-    configuration) the call is ``fit_concurrent(..., sync_every=sync_every)`` and the reason is left in
+    Where ``SmallPlan.why_not`` or ``SmallBatch.why_not`` objects (a model outside the small-graph envelope -- hidden width 32
+    or 64, <= 8 classes, ... --, runs that differ in configuration, a 32-wide and a 64-wide run among them) the call is ``fit_concurrent(..., sync_every=sync_every)`` and the reason is left in
     ``fit_batched.last_refusal`` (None otherwise).  ``keep_best=True``, ``criterion="bce"`` and ``metric="rocauc"`` are not
     implemented here: use ``fit_concurrent``."""
     from .small import SmallBatch
@@ -988,10 +988,12 @@ def fit_batched(runs, x, adj, labels, epochs, rule="min_val_loss", early_stoppin
         why = SmallPlan.why_not(model, xs, ops, opt, need_dropout_state=False)
         if why is None:
             cfg = model.gcns[0]._config()
-            shape = (cfg.n_channels, cfg.relu_before, cfg.layernorm, cfg.scale, model.gcns[1].out_features)
+            shape = (cfg.n_channels, cfg.relu_before, cfg.layernorm, cfg.scale, model.gcns[1].out_features, model.gcns[0].out_features)
             shape0 = shape if shape0 is None else shape0
             if shape != shape0:
                 why = "the models are configured differently"
+                if shape[-1] != shape0[-1]:
+                    why = f"hidden width {shape[-1]} (run 0: {shape0[-1]}): {why}"
         if why is not None:
             return fallback(f"run {k}: {why}")
     n_slots = min(batch, len(runs))

@@ -1052,14 +1052,15 @@ int acm_adam_step(int32_t n_tensors, const acm_adam_tensor_t* tensors, const acm
  *
  * Rows are never split over launches: a row longer than the handle's chunk is cut into pieces whose partial sums meet
  * in a slot buffer, and the piece that arrives last finishes the row (fixed order of additions: deterministic, no float
- * atomics).  Hidden width 64, at most 8 classes, pattern-only operator (acm_csr_create with vals = NULL) + row scale.
+ * atomics).  Hidden width F = 32 or 64 (`hidden`), at most 8 classes, pattern-only operator (acm_csr_create with vals =
+ * NULL) + row scale.
  * With `update` the Adam / AdamW update of every parameter is applied where its gradient becomes final (same formulas
  * as acm_adam_step); without it the gradients are written to t[..].grad and nothing is updated.
  * `train = 0`: launches 1-3 only, forward (evaluation pass: logits, att).  Dense features: convert once (CSR copy).
  */
 #define ACM_SMALL_ROLES 17
 enum {
-    ACM_SR_W_LOW = 0, ACM_SR_W_HIGH, ACM_SR_W_MLP,                         /* [f_in, F] row-major                  */
+    ACM_SR_W_LOW = 0, ACM_SR_W_HIGH, ACM_SR_W_MLP,                         /* [f_in, F] row-major (layer 2: [F, C]) */
     ACM_SR_V_LOW, ACM_SR_V_HIGH, ACM_SR_V_MLP, ACM_SR_V_STRUC,              /* att_vec_*: F floats                  */
     ACM_SR_LNW_LOW, ACM_SR_LNW_HIGH, ACM_SR_LNW_MLP, ACM_SR_LNW_STRUC,      /* LayerNorm gamma                      */
     ACM_SR_LNB_LOW, ACM_SR_LNB_HIGH, ACM_SR_LNB_MLP, ACM_SR_LNB_STRUC,      /* LayerNorm beta                       */
@@ -1068,14 +1069,15 @@ enum {
 };
 
 typedef struct {
-    int32_t n_classes;          /* C <= 8: width of layer 2 (layer 1 is f_in -> 64)                                  */
+    int32_t n_classes;          /* C <= 8: width of layer 2 (layer 1 is f_in -> F, F = `hidden`)                     */
     int32_t n_channels;         /* k = 3, or 4 with the structure channel                                            */
     int32_t relu_before;        /* 1: ACMII (`variant`): ReLU between projection and filter; 0: ACM, ReLU after      */
     int32_t layernorm;          /* 1: LayerNorm feeds the attention logits (ACM-Geometric dialect)                   */
     float   scale;              /* 3, or 1 with the structure channel                                                */
     int32_t train;              /* 1: the step; 0: forward only (launches 1-3)                                       */
     int32_t update;             /* 1: apply Adam / AdamW in place; 0: write gradients to t[..].grad                   */
-    int32_t reserved0;
+    int32_t hidden;             /* F, the hidden width: 32 or 64; 0 means 64 (the field was reserved0 and zero while 64
+                                   was the only width).  Anything else: ACM_EUNSUPPORTED, before any launch              */
     /* t[layer][role]: param NULL = the role is absent / takes no gradient.  exp_avg / exp_avg_sq / step as in
      * acm_adam_tensor_t (needed with `update`); grad: optional output (required without `update`).  numel is ignored. */
     acm_adam_tensor_t t[2][ACM_SMALL_ROLES];
@@ -1101,11 +1103,19 @@ typedef struct {
     size_t  workspace_bytes;
 } acm_small_step_t;
 
+/* The workspace of one run.  No shape argument: the size is the one hidden width 64 needs, an upper bound for width 32
+ * (a 32-wide step uses the front of each block of the same carve-up). */
 int acm_small_step_workspace_bytes(const acm_csr_t* a_low, const acm_csr_t* x, const acm_csr_t* x_t, size_t* bytes);
 /* x / x_t: CSR handles of the features and of their transpose (pattern; values come from p->x_vals; x_t may be NULL with
- * train = 0).  Errors: ACM_EUNSUPPORTED outside the envelope (explicit values, > 8 classes, > 16384 rows, ...). */
+ * train = 0).  Errors: ACM_EUNSUPPORTED outside the envelope (explicit values, > 8 classes, > 16384 rows, a hidden width
+ * other than 32 or 64, ...). */
 int acm_small_step(const acm_csr_t* a_low, const acm_csr_t* x, const acm_csr_t* x_t, const acm_small_step_t* p,
                    acm_stream_t stream);
+/* 1 if the library has small-step kernels for the width (0, 32, 64), else 0 (added under ABI 29).  The Python host asks
+ * this before it offers a width (small.hidden_widths).  Builds of this library without the symbol are NOT a supported case
+ * (the Python loader requires every declared symbol): the one "library" without it is the CPU test double
+ * (tests/fake_lib.py), which restates the step with 64 written in and which the host therefore offers 64 only. */
+int acm_small_step_has_hidden(int32_t hidden);
 
 /* ------------------------------------- a BATCH of small-graph runs in the same six launches (added under ABI 29) --
  * The workload on these graphs is never one run: ACM-Pytorch/train.py:49-139 trains ten splits of up to 5 000 epochs each
@@ -1123,7 +1133,7 @@ int acm_small_step(const acm_csr_t* a_low, const acm_csr_t* x, const acm_csr_t* 
  *
  * acm_small_batch_bind   validates every active slot exactly as acm_small_step does, requires the fields that choose the
  *                        kernels and the grids to agree across slots (n_classes, n_channels, relu_before, layernorm, train,
- *                        update, f_in, x_vals / xt_vals / xt_src_pos / row_scale), refuses two active slots whose workspace,
+ *                        update, f_in, hidden, x_vals / xt_vals / xt_src_pos / row_scale), refuses two active slots whose workspace,
  *                        logits or loss ranges overlap, and writes the table (a copy ordered on `stream`, complete on return:
  *                        NOT capturable).  `slots`: HOST array of n_slots pointers.  The table also records the grids and
  *                        the kernel form it was bound for: a grid row whose launch does not match them does nothing.
