@@ -38,7 +38,11 @@ EXPORTED_SYMBOLS = (
     "acm_small_batch_table_bytes", "acm_small_batch_bind", "acm_small_batch_step", "acm_eval_metrics_batch", "acm_select_step_batch",
     "acm_bnorm_stats_workspace_bytes", "acm_bnorm_stats", "acm_bnorm_fold", "acm_bnorm_param_bwd", "acm_bnorm_bwd_workspace_bytes", "acm_bnorm_bwd",
     "acm_proj_blocks_fwd", "acm_proj_blocks_bwd_workspace_bytes", "acm_proj_blocks_bwd",
+    "acm_csr_build_loss_rows", "acm_csr_loss_rows_info", "acm_conv_fwd_tail_rows",
 )
+# the loss-row entry points (new symbols under ABI 29): callers look them up with getattr(lib, name, None) and keep the full
+# path where a library -- or a test double -- does not have them
+LOSS_ROWS_SYMBOLS = ("acm_csr_build_loss_rows", "acm_csr_loss_rows_info", "acm_conv_fwd_tail_rows")
 
 
 class Dropout(C.Structure):
@@ -377,6 +381,9 @@ def _declare(lib):
     lib.acm_reduce_flush.argtypes = [vp, vp]
     lib.acm_conv_fwd_tail_workspace_bytes.argtypes = [i64, i32, i32, C.POINTER(sz)]
     lib.acm_conv_fwd_tail.argtypes = [vp, C.POINTER(ConvFwd), C.POINTER(Loss), C.POINTER(ConvBwdLocal), vp, sz, vp, sz, vp]
+    lib.acm_csr_build_loss_rows.argtypes = [vp, vp]
+    lib.acm_csr_loss_rows_info.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.acm_conv_fwd_tail_rows.argtypes = lib.acm_conv_fwd_tail.argtypes
     lib.acm_small_step_workspace_bytes.argtypes = [vp, vp, vp, C.POINTER(sz)]
     lib.acm_small_step.argtypes = [vp, vp, vp, C.POINTER(SmallStep), vp]
     lib.acm_small_step_has_hidden.argtypes = [i32]

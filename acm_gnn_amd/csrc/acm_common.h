@@ -8,10 +8,10 @@
 
 #include "acm_dispatch.h"
 #include "acm_hip.h"
+#include "acm_items.h"      // ACM_WINDOW, AcmItem, AcmLongRow: the work list, shared with host-only code
 
 #define ACM_WAVE 64
 #define ACM_NXCD 8
-#define ACM_WINDOW 16         // work items per window of the piece region (see build_items)
 #define ACM_MIN_CHUNK 128
 #define ACM_MAX_CHUNK 1024
 #define ACM_GROUPS_IN_FLIGHT 8192  // 256 CUs x 8 waves x four 16-lane groups
@@ -46,18 +46,6 @@ const acm_tuning_t& acm_tuning();
             return (code);              \
         }                               \
     } while (0)
-
-// A work item: neighbours [begin,end) of `row`; slot < 0 => the item is the whole
-// row and its owner runs the epilogue, otherwise it is one piece of a long row and
-// its partial sums go to partial slot `slot` (combined in order by the fix-up pass, or
-// through LDS by a kernel that takes whole windows, see build_items in acm_csr.cpp).
-struct AcmItem {
-    int32_t row, begin, end, slot;
-};
-// A long row and its partial slots [slot_begin, slot_end).
-struct AcmLongRow {
-    int32_t row, slot_begin, slot_end, windows;   // windows > 1: the row's pieces fill that many whole windows (acm_csr.cpp)
-};
 
 // Per-wave id streams of a pattern-only operator (acm_csr_build_streams, acm_csr.cpp): the column ids laid out in the
 // order a wave of the streamed aggregate-first kernel consumes them.  A SLICE = four work items (rows, or pieces of at
@@ -96,6 +84,19 @@ struct AcmItemStreams {
     int32_t n_waves;
 };
 
+// The loss-row attachment of a square operator (acm_csr_build_loss_rows, acm_csr.cpp) for the output layer of a training
+// step whose masked loss gives weight 0 to the rows outside `keep`:
+// a work list over the kept rows alone (their items are those of the handle's own list: same pieces, same order of summation),
+// with its own long-row records, slot numbers and window count -- the forward gather walks it -- and a device copy of `keep`.
+struct AcmLossRows {
+    AcmItem* items;         // device
+    AcmLongRow* long_rows;  // device
+    int32_t* long_index;    // device, n_rows (NULL without long rows)
+    int64_t n_items, n_long, n_slots, n_windows, n_multi;
+    uint8_t* keep;          // device, n_rows
+    int64_t kept_rows, kept_edges;
+};
+
 struct acm_csr {
     int64_t n_rows, n_cols, nnz;
     int32_t chunk, max_degree;
@@ -113,6 +114,7 @@ struct acm_csr {
     int64_t n_multi;        // long rows that take several windows (their window sums are added by a second launch)
     AcmStreams* streams;    // NULL until acm_csr_build_streams
     AcmItemStreams* item_streams;   // NULL until acm_csr_build_item_streams
+    AcmLossRows* loss_rows;         // NULL until acm_csr_build_loss_rows
     int device;
 };
 
@@ -139,6 +141,12 @@ struct CsrView {
     int n_multi;
     const int32_t* indices;
     const float* vals;
+};
+
+// What launch_gather walks instead of the handle's own work list (acm_gather_device.h): a view and its slot count.
+struct GatherOverride {
+    CsrView view;
+    int64_t n_slots;
 };
 
 // Second phase of a partial-sum reduction: launch `segs` now (defer == NULL) or append them to the caller's list.

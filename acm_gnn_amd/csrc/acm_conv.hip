@@ -252,10 +252,15 @@ extern "C" int acm_conv_fwd(const acm_csr_t* a, const acm_conv_fwd_t* p, void* w
 // One thread per row, three steps that hand their results to each other through the row's own few bytes of global
 // memory (written and read back by the same thread): the head of the narrow forward, the masked NLL of its logits, the
 // row-local backward with that gradient.  Block-level reductions: loss partial, K3 parameter partials.
-template <int FP, int NG>
+// ROWS (acm_conv_fwd_tail_rows): `keep` marks the rows that carry weight in the loss.  A thread whose row is not kept loads
+// nothing and computes nothing: it stores zeros to every per-row output (logits, pre, att, dlogits, G_L, G_H, G_I -- G_H is
+// the self term of the transposed gather and G_I feeds the hidden layer's projection backward, so neither may be stale) and
+// enters both block reductions with zero accumulators.  Thread <-> row and block <-> 256 rows stay what they are, so the
+// partials of a block are the sums they were with the dropped rows' zero terms left out.
+template <int FP, int NG, bool ROWS = false>
 __global__ __launch_bounds__(256) void conv_tail_rows_kernel(acm_conv_fwd_t pf, acm_loss_t pl, acm_conv_bwd_local_t pb,
                                                              int n_rows, float* __restrict__ loss_partial,
-                                                             float* __restrict__ k3_partial) {
+                                                             float* __restrict__ k3_partial, const uint8_t* __restrict__ keep) {
     extern __shared__ float lds[];
     __shared__ float red[256];
     constexpr int K = NG + 1;
@@ -267,7 +272,17 @@ __global__ __launch_bounds__(256) void conv_tail_rows_kernel(acm_conv_fwd_t pf, 
     ParamAcc<LaySerial<FP>> pa;
     pa.zero();
     float term = 0.f;
-    if (active) {
+    if (ROWS && active && !keep[row]) {
+        for (int f = 0; f < F; ++f) {
+            pf.out[(long)row * pf.ld_out + f] = 0.f;
+            pl.dlogits[(long)row * pl.ld_dlogits + f] = 0.f;
+            pb.g_low[(long)row * pb.ld_g_low + f] = 0.f;
+            pb.g_high[(long)row * pb.ld_g_high + f] = 0.f;
+            pb.g_mlp[(long)row * pb.ld_g_mlp + f] = 0.f;
+            for (int c = 0; c < NG; ++c) pf.pre[(long)row * pf.ld_pre + c * F + f] = 0.f;
+        }
+        *reinterpret_cast<float4*>(pf.att + (long)row * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else if (active) {
         float acc[NG][FP];
         const float* pr = pf.pre + (long)row * pf.ld_pre;
 #pragma unroll
@@ -357,11 +372,17 @@ extern "C" int acm_conv_fwd_tail_workspace_bytes(int64_t n_rows, int f_out, int 
     return ACM_OK;
 }
 
-extern "C" int acm_conv_fwd_tail(const acm_csr_t* a, const acm_conv_fwd_t* p, const acm_loss_t* l,
-                                 const acm_conv_bwd_local_t* b, void* workspace, size_t workspace_bytes,
-                                 void* tail_workspace, size_t tail_workspace_bytes, acm_stream_t stream) {
+// rows: over the operator's loss-row attachment (acm_conv_fwd_tail_rows)
+static int conv_fwd_tail(const acm_csr_t* a, const acm_conv_fwd_t* p, const acm_loss_t* l,
+                         const acm_conv_bwd_local_t* b, void* workspace, size_t workspace_bytes,
+                         void* tail_workspace, size_t tail_workspace_bytes, acm_stream_t stream, bool rows) {
     ACM_REQUIRE(a && p && l && b, ACM_EINVAL, "acm_conv_fwd_tail: NULL argument");
     const int F = p->f_out, k = p->n_channels;
+    const AcmLossRows* lr = rows ? a->loss_rows : nullptr;
+    if (rows) {
+        ACM_REQUIRE(lr, ACM_EUNSUPPORTED, "acm_conv_fwd_tail_rows: the operator has no loss-row list (acm_csr_build_loss_rows)");
+        ACM_REQUIRE(F <= 4, ACM_EUNSUPPORTED, "acm_conv_fwd_tail_rows: f_out %d (the thread-per-row tail: f_out <= 4)", F);
+    }
     size_t need = 0;
     int st = acm_conv_fwd_tail_workspace_bytes(a->n_rows, F, k, &need);
     if (st != ACM_OK) return st;
@@ -370,7 +391,7 @@ extern "C" int acm_conv_fwd_tail(const acm_csr_t* a, const acm_conv_fwd_t* p, co
     ACM_REQUIRE(!p->post_relu && !p->post_scale && p->post_drop.p == 0.f && !b->post_relu && !b->post_scale &&
                     b->post_drop.p == 0.f && !p->gather_bf16, ACM_EUNSUPPORTED,
                 "acm_conv_fwd_tail: post-ops / bf16 operands are not part of the fused tail");
-    ACM_REQUIRE(a->n_long == 0 || narrow_finishes_long_rows(a), ACM_EUNSUPPORTED,
+    ACM_REQUIRE((rows ? lr->n_long : a->n_long) == 0 || narrow_finishes_long_rows(a), ACM_EUNSUPPORTED,
                 "acm_conv_fwd_tail: this graph's narrow gather leaves partial sums of long rows");
     ACM_REQUIRE(p->g_low && p->g_high && p->s_high && p->s_mlp && p->out && p->pre && p->att && p->att_mix &&
                     l->labels && l->row_weight && l->loss && l->dlogits && b->att_mix && b->g_low && b->g_high &&
@@ -390,7 +411,20 @@ extern "C" int acm_conv_fwd_tail(const acm_csr_t* a, const acm_conv_fwd_t* p, co
     if (a->n_rows == 0) return ACM_OK;
     hipStream_t s = (hipStream_t)stream;
     GatherSrc g = {{p->g_low, p->g_high, nullptr}, {p->ld_g_low, p->ld_g_high, 0}};
-    st = launch_gather<2, EpiRaw>(a, g, F, *p, workspace, workspace_bytes, s, "acm_conv_fwd_tail", nullptr, false, true);
+    if (rows) {
+        // the attachment's list in place of the handle's: same column ids, same values, its own items and slot count
+        GatherOverride over = {acm_view(a), lr->n_slots};
+        over.view.items = lr->items;
+        over.view.n_items = (int)lr->n_items;
+        over.view.long_rows = lr->long_rows;
+        over.view.long_index = lr->long_index;
+        over.view.n_long = (int)lr->n_long;
+        over.view.n_windows = (int)lr->n_windows;
+        over.view.n_multi = (int)lr->n_multi;
+        st = launch_gather<2, EpiRaw>(a, g, F, *p, workspace, workspace_bytes, s, "acm_conv_fwd_tail_rows", nullptr, false, true, &over);
+    } else {
+        st = launch_gather<2, EpiRaw>(a, g, F, *p, workspace, workspace_bytes, s, "acm_conv_fwd_tail", nullptr, false, true);
+    }
     if (st != ACM_OK) return st;
     const bool packed = F > 4;             // eight lanes per row (conv_tail_packed8_kernel)
     const int n = (int)a->n_rows, nblk = packed ? (n + 31) / 32 : (n + 255) / 256;
@@ -401,8 +435,12 @@ extern "C" int acm_conv_fwd_tail(const acm_csr_t* a, const acm_conv_fwd_t* p, co
     acm_pick([&](auto fp) {
         if constexpr (fp() == 8)
             hipLaunchKernelGGL((conv_tail_packed8_kernel<2>), dim3(nblk), dim3(256), lds, s, *p, *l, *b, n, loss_partial, k3_partial);
+        else if (rows)
+            hipLaunchKernelGGL((conv_tail_rows_kernel<fp(), 2, true>), dim3(nblk), dim3(256), lds, s, *p, *l, *b, n, loss_partial, k3_partial,
+                               (const uint8_t*)lr->keep);
         else
-            hipLaunchKernelGGL((conv_tail_rows_kernel<fp(), 2>), dim3(nblk), dim3(256), lds, s, *p, *l, *b, n, loss_partial, k3_partial);
+            hipLaunchKernelGGL((conv_tail_rows_kernel<fp(), 2>), dim3(nblk), dim3(256), lds, s, *p, *l, *b, n, loss_partial, k3_partial,
+                               (const uint8_t*)nullptr);
         return ACM_OK;
     }, acm_fp_of(F));
     ACM_CHECK_HIP(hipGetLastError());
@@ -410,4 +448,16 @@ extern "C" int acm_conv_fwd_tail(const acm_csr_t* a, const acm_conv_fwd_t* p, co
     st = acm_reduce_emit(b->defer, &seg, 1, s);
     if (st != ACM_OK) return st;
     return acm_bwd_local_reduce(b, k3_partial, nblk, s);
+}
+
+extern "C" int acm_conv_fwd_tail(const acm_csr_t* a, const acm_conv_fwd_t* p, const acm_loss_t* l,
+                                 const acm_conv_bwd_local_t* b, void* workspace, size_t workspace_bytes,
+                                 void* tail_workspace, size_t tail_workspace_bytes, acm_stream_t stream) {
+    return conv_fwd_tail(a, p, l, b, workspace, workspace_bytes, tail_workspace, tail_workspace_bytes, stream, false);
+}
+
+extern "C" int acm_conv_fwd_tail_rows(const acm_csr_t* a, const acm_conv_fwd_t* p, const acm_loss_t* l,
+                                      const acm_conv_bwd_local_t* b, void* workspace, size_t workspace_bytes,
+                                      void* tail_workspace, size_t tail_workspace_bytes, acm_stream_t stream) {
+    return conv_fwd_tail(a, p, l, b, workspace, workspace_bytes, tail_workspace, tail_workspace_bytes, stream, true);
 }

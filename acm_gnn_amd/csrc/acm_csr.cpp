@@ -36,7 +36,7 @@ const TuningField kTuningFields[] = {{"chunk", &acm_tuning_t::chunk},           
                                      {"bwd_split", &acm_tuning_t::bwd_split},   {"rows16", &acm_tuning_t::rows16},
                                      {"agg_fused", &acm_tuning_t::agg_fused},   {"gemm_forms", &acm_tuning_t::gemm_forms}};
 // host-side keys of the same variable (acm_gnn_amd/tuning.py reads them; listed here so that they are not "unknown")
-const char* const kHostKeys[] = {"rewrites", "implicit", "relabel", "pipeline", "csr_features", "small_step", "mlp_stack"};
+const char* const kHostKeys[] = {"rewrites", "implicit", "relabel", "pipeline", "csr_features", "small_step", "mlp_stack", "loss_rows"};
 
 const char* tuning_invalid(const acm_tuning_t& t) {
     if (t.chunk != 0 && (t.chunk < 8 || t.chunk > 4096 || (t.chunk & (t.chunk - 1)))) return "chunk";
@@ -120,8 +120,16 @@ void free_item_streams(AcmItemStreams* t) {
     delete t;
 }
 
+void free_loss_rows(AcmLossRows* t) {
+    if (!t) return;
+    for (void* q : {(void*)t->items, (void*)t->long_rows, (void*)t->long_index, (void*)t->keep})
+        if (q) (void)hipFree(q);
+    delete t;
+}
+
 void free_handle(acm_csr* a) {
     if (!a) return;
+    free_loss_rows(a->loss_rows);
     if (a->indptr) (void)hipFree(a->indptr);
     if (a->indices) (void)hipFree(a->indices);
     if (a->vals) (void)hipFree(a->vals);
@@ -134,72 +142,7 @@ void free_handle(acm_csr* a) {
     delete a;
 }
 
-// Split rows into work items of at most `chunk` neighbours -- host side, from a host copy of indptr.
-// A long row (more than `chunk` neighbours) becomes P = min(16, ceil(deg / chunk)) near-equal pieces with consecutive
-// partial slots.  All pieces come FIRST in the list, packed into windows of ACM_WINDOW = 16 items so that the pieces of
-// one row never straddle a window (a window that cannot take the next row is filled up with empty pieces of the row
-// before, and so is the last one): a kernel whose workgroup takes one window per round (16 groups of 16 lanes) can
-// combine the pieces of a row through LDS and finish the row itself instead of leaving partial sums to a second
-// launch; every other kernel writes the pieces to their partial slots as before.  The whole rows follow in row order.
-// Returns in n_multi the rows that take several windows.
-void build_items(const std::vector<int32_t>& indptr, int chunk, std::vector<AcmItem>& items,
-                 std::vector<AcmLongRow>& longs, int64_t& n_slots, int32_t& max_deg, int64_t& n_windows, int64_t& n_multi) {
-    const int64_t n = (int64_t)indptr.size() - 1;
-    items.clear();
-    longs.clear();
-    items.reserve(n + n / 8);
-    n_slots = 0;
-    max_deg = 0;
-    n_multi = 0;
-    for (int64_t r = 0; r < n; ++r) {
-        const int32_t b = indptr[r], e = indptr[r + 1];
-        const int32_t deg = e - b;
-        max_deg = std::max(max_deg, deg);
-        if (deg <= chunk) continue;
-        int32_t pieces = (deg + chunk - 1) / chunk;
-        // A row that sixteen pieces of up to 4 x chunk neighbours do not cover takes SEVERAL whole windows (at most sixteen)
-        // of pieces of about 2 x chunk: sixteen pieces in one window all run on the CU that window's workgroup lands on,
-        // and a row of 21 k neighbours then keeps one texture path busy for ~20 us whatever the rest of the chip does (the
-        // floor of a rank's gathers in an 8-rank plan: DESIGN.md section 7).  With the chunk sized to the operator
-        // (nnz / 32768 < chunk <= nnz / 16384) the bar of 64 x chunk neighbours is 0.5 .. 1 x the mean CU's share of the
-        // whole operator: no row of the twitch- or arXiv-year-shaped graphs reaches it on one GPU, the top rows of a rank
-        // of an 8-rank plan do.  (A lower bar -- every row above 32 x chunk that is also above nnz / 128 -- left the rows of
-        // 8-13 k neighbours in one window each and was slower per rank: 27-29 us against 22-27 us for the output-layer
-        // backward gather.)  A window of such a row leaves its sum in its first piece's slot and a small second launch adds
-        // the windows (AcmLongRow.windows > 1).
-        int32_t windows = 0;
-        if (pieces > ACM_WINDOW && (deg + ACM_WINDOW - 1) / ACM_WINDOW > 4 * chunk) {
-            windows = (deg + 2 * ACM_WINDOW * chunk - 1) / (2 * ACM_WINDOW * chunk);
-            if (windows > ACM_WINDOW) windows = ACM_WINDOW;
-            pieces = windows * ACM_WINDOW;
-        } else if (pieces > ACM_WINDOW) {
-            pieces = ACM_WINDOW;
-        }
-        const int32_t room = ACM_WINDOW - (int32_t)(items.size() % ACM_WINDOW);
-        if ((room < pieces || windows) && room < ACM_WINDOW) {    // does not fit: pad with empty pieces of the row before
-            AcmLongRow& prev = longs.back();
-            for (int32_t q = 0; q < room; ++q) items.push_back({prev.row, indptr[prev.row + 1], indptr[prev.row + 1], (int32_t)n_slots++});
-            prev.slot_end = (int32_t)n_slots;
-        }
-        const int32_t per = (deg + pieces - 1) / pieces;
-        AcmLongRow lr = {(int32_t)r, (int32_t)n_slots, 0, windows};
-        for (int32_t q = 0; q < pieces; ++q) {
-            const int32_t s = std::min(e, b + q * per);
-            items.push_back({(int32_t)r, s, std::min(e, s + per), (int32_t)n_slots++});
-        }
-        lr.slot_end = (int32_t)n_slots;
-        n_multi += windows > 1;
-        longs.push_back(lr);
-    }
-    if (!longs.empty() && items.size() % ACM_WINDOW) {
-        AcmLongRow& prev = longs.back();
-        while (items.size() % ACM_WINDOW) items.push_back({prev.row, indptr[prev.row + 1], indptr[prev.row + 1], (int32_t)n_slots++});
-        prev.slot_end = (int32_t)n_slots;
-    }
-    n_windows = (int64_t)items.size() / ACM_WINDOW;
-    for (int64_t r = 0; r < n; ++r)
-        if (indptr[r + 1] - indptr[r] <= chunk) items.push_back({(int32_t)r, indptr[r], indptr[r + 1], -1});
-}
+// (the cut of the rows into work items: build_items, acm_items.h)
 
 // Finish a handle whose indptr/indices/vals device arrays are already in place.
 int finish_handle(acm_csr* a, const std::vector<int32_t>& h_indptr, int chunk) {
@@ -685,6 +628,52 @@ extern "C" int acm_csr_build_item_streams(acm_csr_t* a, int n_waves) {
         return st;
     }
     a->item_streams = t;
+    return ACM_OK;
+}
+
+// ------------------------------------------------------------------ loss-row attachment
+extern "C" int acm_csr_build_loss_rows(acm_csr_t* a, const uint8_t* keep_dev) {
+    ACM_REQUIRE(a && keep_dev, ACM_EINVAL, "acm_csr_build_loss_rows: NULL argument");
+    ACM_REQUIRE(a->n_rows == a->n_cols, ACM_EUNSUPPORTED, "acm_csr_build_loss_rows: a square operator (%lld x %lld)",
+                (long long)a->n_rows, (long long)a->n_cols);
+    ACM_CHECK_HIP(hipDeviceSynchronize());
+    const int64_t n = a->n_rows;
+    std::vector<int32_t> ip((size_t)n + 1);
+    std::vector<uint8_t> keep((size_t)std::max<int64_t>(n, 1), 0);
+    ACM_CHECK_HIP(hipMemcpy(ip.data(), a->indptr, ip.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (n) ACM_CHECK_HIP(hipMemcpy(keep.data(), keep_dev, (size_t)n, hipMemcpyDeviceToHost));
+    AcmLossRowsHost h;
+    acm_loss_rows_host(ip, keep.data(), a->chunk, h);      // (the handle's own chunk: the kept rows' items are the full list's)
+    AcmLossRows* t = new (std::nothrow) AcmLossRows();
+    ACM_REQUIRE(t, ACM_ENOMEM, "acm_csr_build_loss_rows: host allocation failed");
+    memset(t, 0, sizeof(*t));
+    t->n_items = (int64_t)h.items.size();
+    t->n_long = (int64_t)h.longs.size();
+    t->n_slots = h.n_slots;
+    t->n_windows = h.n_windows;
+    t->n_multi = h.n_multi;
+    t->kept_rows = h.kept_rows;
+    t->kept_edges = h.kept_edges;
+    int st = upload(&t->keep, keep);
+    if (st == ACM_OK) st = upload(&t->items, h.items);
+    if (st == ACM_OK && !h.longs.empty()) st = upload(&t->long_rows, h.longs);
+    if (st == ACM_OK && !h.longs.empty()) st = upload(&t->long_index, h.long_index);
+    if (st != ACM_OK) {
+        free_loss_rows(t);
+        return st;
+    }
+    free_loss_rows(a->loss_rows);          // (the device is idle: synchronised above, nothing launched since)
+    a->loss_rows = t;
+    return ACM_OK;
+}
+
+extern "C" int acm_csr_loss_rows_info(const acm_csr_t* a, int64_t* out) {
+    ACM_REQUIRE(a && out, ACM_EINVAL, "acm_csr_loss_rows_info: NULL argument");
+    const AcmLossRows* t = a->loss_rows;
+    out[0] = t ? t->kept_rows : 0;
+    out[1] = t ? t->n_items : 0;
+    out[2] = t ? t->n_slots : 0;
+    out[3] = t ? t->kept_edges : 0;
     return ACM_OK;
 }
 

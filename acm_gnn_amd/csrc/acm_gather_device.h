@@ -877,8 +877,8 @@ void launch_pair3(int grid, hipStream_t st, const CsrView& v, const float* table
 // after a narrow gather with sixteen lanes per item: the rows of several windows (none on most operators)
 template <int NG, class Epi>
 int finish_window_rows(const acm_csr* a, const CsrView& v, int F, const typename Epi::Args& ea, const float* partial, hipStream_t st) {
-    if (a->n_multi == 0) return ACM_OK;
-    const int grid = (int)((a->n_long + 15) / 16);
+    if (v.n_multi == 0) return ACM_OK;            // (the view's own counts: the handle's, or an override's)
+    const int grid = (int)((v.n_long + 15) / 16);
     acm_pick([&](auto fp) {
         hipLaunchKernelGGL((spmm_fixup_windows_kernel<fp(), NG, Epi>), dim3(grid), dim3(256), 0, st, v, F, ea, partial);
         return ACM_OK;
@@ -887,17 +887,23 @@ int finish_window_rows(const acm_csr* a, const CsrView& v, int F, const typename
     return ACM_OK;
 }
 
+// `over` (NULL: the handle's own): the work list the gather walks in place of the handle's -- a loss-row attachment's.  The FORM
+// is still chosen from the handle's own sizes (narrow_lanes of its n_rows and nnz), so a sub-list runs the very kernel the full
+// list runs.
 template <int NG, class Epi>
 int launch_gather(const acm_csr* a, const GatherSrc& g, int F, const typename Epi::Args& ea,
                   void* workspace, size_t ws_bytes, hipStream_t st, const char* who,
-                  const float* vals_override = nullptr, bool bf16 = false, bool defer_fixup = false) {
-    const size_t need = (size_t)a->n_slots * (size_t)(NG * F) * sizeof(float);
+                  const float* vals_override = nullptr, bool bf16 = false, bool defer_fixup = false,
+                  const GatherOverride* over = nullptr) {
+    const int64_t n_slots = over ? over->n_slots : a->n_slots;
+    const size_t need = (size_t)n_slots * (size_t)(NG * F) * sizeof(float);
     ACM_REQUIRE(ws_bytes >= need && (need == 0 || workspace), ACM_ENOMEM,
                 "%s: workspace %zu B < required %zu B", who, ws_bytes, need);
     float* partial = (float*)workspace;
-    CsrView v = acm_view(a);
+    CsrView v = over ? over->view : acm_view(a);
     if (vals_override) v.vals = vals_override;
-    if (a->n_items == 0) return ACM_OK;
+    const int64_t n_items = v.n_items, n_long = v.n_long;
+    if (n_items == 0) return ACM_OK;
     ACM_REQUIRE(!bf16 || (F > 8 && F <= 64 && F % 2 == 0), ACM_EUNSUPPORTED,
                 "%s: bf16 gathered operands are implemented for even 8 < F <= 64", who);
     if (bf16) {
@@ -909,14 +915,14 @@ int launch_gather(const acm_csr* a, const GatherSrc& g, int F, const typename Ep
     const GatherForm form = choose_gather_form(a->n_rows, a->n_cols, a->nnz, a->n_long, a->long_index, g, NG, F, bf16,
                                                acm_tuning().wide_form, Epi::kFusedHead);
     // the forms for F > 8: a wave per work item, the same arguments
-    auto wide = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((int)((a->n_items + 3) / 4)), dim3(256), 0, st, v, g, F, ea, partial); };
+    auto wide = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((int)((n_items + 3) / 4)), dim3(256), 0, st, v, g, F, ea, partial); };
     if constexpr (epi_wide_only<Epi>::value)
         ACM_REQUIRE(F > 8, ACM_EUNSUPPORTED, "%s: this epilogue exists for more than 8 columns (got %d)", who, F);
     int rc = ACM_OK;
     switch (form.kind) {
     case GatherForm::PAIR3: {
       if constexpr (!epi_wide_only<Epi>::value) {
-        int grid = (int)((a->n_items + 15) / 16);
+        int grid = (int)((n_items + 15) / 16);
         if (grid > NARROW_MAX_BLOCKS) grid = NARROW_MAX_BLOCKS;
         launch_pair3<NG, Epi>(grid, st, v, g.p[0], ea, partial);
         ACM_CHECK_HIP(hipGetLastError());
@@ -928,7 +934,7 @@ int launch_gather(const acm_csr* a, const GatherSrc& g, int F, const typename Ep
       if constexpr (!epi_wide_only<Epi>::value)
         rc = acm_pick([&](auto fp, auto gs) {
             constexpr int FP = decltype(fp)::value, GS = decltype(gs)::value, gpb = 256 / GS;
-            int grid = (int)((a->n_items + gpb - 1) / gpb);
+            int grid = (int)((n_items + gpb - 1) / gpb);
             if (grid > NARROW_MAX_BLOCKS) grid = NARROW_MAX_BLOCKS;
             if (form.merged)
                 hipLaunchKernelGGL((spmm_narrow_kernel<FP, NG, GS, (NG >= 2), Epi>), dim3(grid), dim3(256), 0, st, v, g, F,
@@ -950,17 +956,17 @@ int launch_gather(const acm_csr* a, const GatherSrc& g, int F, const typename Ep
     // sixteen lanes per item: the narrow gather has finished the long rows itself, except the rows of several windows
     if constexpr (!epi_wide_only<Epi>::value)
         if (F <= 8 && narrow_finishes_long_rows(a)) return finish_window_rows<NG, Epi>(a, v, F, ea, partial, st);
-    if (defer_fixup || !a->n_long) return ACM_OK;      // (deferred: the caller's next kernel adds the partial slots of the long rows)
+    if (defer_fixup || !n_long) return ACM_OK;      // (deferred: the caller's next kernel adds the partial slots of the long rows)
     if (F <= 8) {
       if constexpr (!epi_wide_only<Epi>::value)
         acm_pick([&](auto fp) {
-            hipLaunchKernelGGL((spmm_fixup_narrow_kernel<fp(), NG, Epi>), dim3((int)((a->n_long + 15) / 16)), dim3(256), 0, st, v, F, ea,
+            hipLaunchKernelGGL((spmm_fixup_narrow_kernel<fp(), NG, Epi>), dim3((int)((n_long + 15) / 16)), dim3(256), 0, st, v, F, ea,
                                partial);
             return ACM_OK;
         }, acm_fp_of(F));
     } else {
         acm_pick([&](auto nreg) {
-            hipLaunchKernelGGL((spmm_fixup_kernel<nreg(), NG, Epi>), dim3((int)((a->n_long + 3) / 4)), dim3(256), 0, st, v, F, ea, partial);
+            hipLaunchKernelGGL((spmm_fixup_kernel<nreg(), NG, Epi>), dim3((int)((n_long + 3) / 4)), dim3(256), 0, st, v, F, ea, partial);
             return ACM_OK;
         }, acm_nreg_of(F));
     }

@@ -339,10 +339,17 @@ class fused_loss_tail:
     masked NLL of its logits and its own row-local backward (K3) as ONE kernel (acm_conv_fwd_tail).  Afterwards
     ``tail.matches(out)`` says whether ``out`` is that layer's output; if so ``tail.loss`` / ``tail.dz`` are what
     nll_loss_and_grad(out, labels, row_weight) returns, and ``out.backward(tail.dz)`` skips K3.  Any other gradient
-    handed to that layer's backward makes it run K3 as usual, so a request that is not honoured costs nothing but time."""
+    handed to that layer's backward makes it run K3 as usual, so a request that is not honoured costs nothing but time.
 
-    def __init__(self, labels, row_weight):
-        self.labels, self.row_weight = labels, row_weight
+    ``loss_rows`` (a graph.LossRows of the operators the model is called with, built for THIS ``row_weight``; default None:
+    the full path): the layer may then take acm_conv_fwd_tail_rows.  The loss,
+    ``dz`` and every gradient keep their bits; but the rows of ``out`` (and of the layer's ``att``) whose weight is 0 are
+    then ZEROS, not logits -- for a caller that reads the loss alone (train.TrainStep).  ``tail.used_loss_rows`` says
+    whether the layer took it."""
+
+    def __init__(self, labels, row_weight, loss_rows=None):
+        self.labels, self.row_weight, self.loss_rows = labels, row_weight, loss_rows
+        self.used_loss_rows = False
         self.loss = self.dz = self.out = None
 
     def __enter__(self):

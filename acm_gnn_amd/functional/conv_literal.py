@@ -11,7 +11,7 @@ from ._context import _current_tape, _take_pre_proj
 from ._conv_shared import _NO_GRADS, _chan_block, _conv_prologue, _flat_views, _gathered_input, _grads, _head_params, _hop_buffer, \
     _k3_setup, _low_product, _narrow_tables, _pack_head, _reduce_replicated, _set_head, _set_post, _struc_grad, _struc_rows, \
     _unpack_head, _z_pitch, PROJECTED
-from ._launch import _F32, _as_f32c, _capturing, _vp, _workspace, _workspace_bytes, launch
+from ._launch import _F32, EUNSUPPORTED, _as_f32c, _capturing, _vp, _workspace, _workspace_bytes, launch
 from .ops import _drop_now, _drop_spec, cast_bf16, gemm, gemm_drop_supported, gemm_split, proj3, proj_bwd, proj_bwd_supported, \
     proj_fwd, spmm, spmm_v
 
@@ -280,8 +280,22 @@ def _fwd_tail(ctx, ops, cfg, graph, p, ws, tail_req, w3, pre, zi, vecs, lnw, lnb
     if nbytes is None:
         return None
     wt = torch.empty(max(nbytes // 4, 1), dtype=_F32, device=dev)
-    st = launch("acm_conv_fwd_tail", f"conv_fwd_tail/F{f}k{k}", dev, graph.handle, C.byref(p), C.byref(lo), C.byref(q), _vp(ws), ws.numel() * 4,
-                _vp(wt), nbytes, unsupported_ok=True)
+    # over the operators' loss-row attachment where the request carries one (rows of weight 0 are then neither gathered nor
+    # finished: acm_conv_fwd_tail_rows); ACM_EUNSUPPORTED, a library without the symbol or stale weights: the full call
+    ctx.loss_rows = None
+    st, lr = EUNSUPPORTED, getattr(tail_req, "loss_rows", None)
+    if (lr is not None and f <= 4 and graph is ops.low and not ops.sharded and lr.current_for(tail_req.row_weight)
+            and getattr(_lib.load(), "acm_conv_fwd_tail_rows", None) is not None):
+        need = lr.fwd["slots"] * (k - 1) * f
+        wsr = ws if ws.numel() >= need else torch.empty(need, dtype=_F32, device=dev)     # (the list numbers its own partial slots)
+        st = launch("acm_conv_fwd_tail_rows", f"conv_fwd_tail/F{f}k{k}", dev, graph.handle, C.byref(p), C.byref(lo), C.byref(q), _vp(wsr),
+                    wsr.numel() * 4, _vp(wt), nbytes, unsupported_ok=True)
+        if st == 0:
+            ctx.loss_rows = lr
+            tail_req.used_loss_rows = True
+    if st == EUNSUPPORTED:
+        st = launch("acm_conv_fwd_tail", f"conv_fwd_tail/F{f}k{k}", dev, graph.handle, C.byref(p), C.byref(lo), C.byref(q), _vp(ws),
+                    ws.numel() * 4, _vp(wt), nbytes, unsupported_ok=True)
     if st == 0:
         st3["keep"] = (y, w_row, wt)
         ctx.tail = st3

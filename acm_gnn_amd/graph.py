@@ -175,6 +175,27 @@ class CsrGraph:
         self.item_stream_waves = info.item_stream_waves
         return self.item_stream_waves > 0
 
+    def build_loss_rows(self, keep):
+        """The loss-row attachment of a square operator (``acm_csr_build_loss_rows``): ``keep`` is a uint8 device tensor of
+        n_rows entries, non-zero = the row carries weight in the loss; the handle gets a work list over those rows alone.
+        One-off host-side preprocessing: it synchronises the device and must not run while a stream is capturing.  Calling
+        it again REPLACES the attachment -- a captured graph that walks the earlier one must not be replayed afterwards.
+        Returns the dict of ``acm_csr_loss_rows_info`` (kept_rows, items, slots, kept_edges), or None where the library has
+        no such entry point or the operator is not square."""
+        lib = _lib.load()
+        build, info = getattr(lib, "acm_csr_build_loss_rows", None), getattr(lib, "acm_csr_loss_rows_info", None)
+        if build is None or info is None or self.n_rows != self.n_cols:
+            return None
+        if keep.dtype != torch.uint8 or keep.numel() != self.n_rows or not keep.is_contiguous():
+            raise ValueError("build_loss_rows: keep must be a contiguous uint8 tensor of n_rows entries")
+        _require_cuda(keep, "keep")
+        with _device_ctx(self.device):
+            _sync(self.device)
+            _lib.check(build(self._h, keep.data_ptr()), "acm_csr_build_loss_rows")
+            out = (C.c_int64 * 4)()
+            _lib.check(info(self._h, out), "acm_csr_loss_rows_info")
+        return dict(zip(("kept_rows", "items", "slots", "kept_edges"), (int(v) for v in out)))
+
     # ---- derived operators ----------------------------------------------
     def transpose(self):
         if self._transposed is None:
@@ -353,6 +374,22 @@ class SparseFeatures:
         return self.csr.transpose()
 
 
+class LossRows:
+    """What FilterOperators.loss_rows attached to the forward handle for one row-weight tensor: ``keep`` (uint8, 1 = the row
+    carries weight), the counts acm_csr_loss_rows_info reports (``fwd``: kept_rows, items, slots, kept_edges) and the key
+    (data_ptr, _version, numel) of the weights."""
+    __slots__ = ("key", "keep", "fwd", "__weakref__")
+
+    def __init__(self, key, keep, fwd):
+        self.key, self.keep, self.fwd = key, keep, fwd
+
+    def current_for(self, weights):
+        return self.key == (weights.data_ptr(), weights._version, weights.numel())
+
+    def __repr__(self):
+        return f"LossRows(kept_rows={self.fwd['kept_rows']}, items={self.fwd['items']}, kept_edges={self.fwd['kept_edges']})"
+
+
 class FilterOperators:
     """What one ACM layer needs from the graph, for the rows this process owns."""
 
@@ -387,6 +424,7 @@ class FilterOperators:
         self.un = None                                  # CsrGraph of adj_low_unnormalized
         self._eye = None
         self._zeros = {}
+        self._loss_rows = None                          # weak reference to the live LossRows of these operators (loss_rows())
 
     @property
     def implicit(self):
@@ -401,6 +439,31 @@ class FilterOperators:
         if self._low_t is None:
             self._low_t = self.low.transpose()
         return self._low_t
+
+    def loss_rows(self, weights, replaces=None):
+        """The loss-row attachment of these operators for the row weights ``weights`` (rows of weight 0 carry no loss): the
+        work list over the weighted rows, on ``low``.  Cached per weights tensor (``data_ptr`` and ``_version``); the caller keeps the returned
+        LossRows alive for as long as it launches over it.
+
+        A handle carries ONE attachment, and a captured graph keeps the addresses of the one it was captured over: while a
+        LossRows for other weights is alive, a second request is refused (None) unless the caller hands its own object over as
+        ``replaces`` (an eager step whose weights changed).  None also for sharded / general operators, non-square operators
+        and libraries without the entry points.  Synchronises the device; never call it while a stream is capturing."""
+        if self.sharded or self.general or weights.numel() != self.low.n_rows:
+            return None
+        key = (weights.data_ptr(), weights._version, weights.numel())
+        cur = self._loss_rows() if self._loss_rows is not None else None
+        if cur is not None and cur.key == key:
+            return cur
+        if cur is not None and cur is not replaces:
+            return None
+        keep = (weights.detach().reshape(-1) != 0).to(torch.uint8).contiguous()
+        fwd = self.low.build_loss_rows(keep)
+        if fwd is None:
+            return None
+        out = LossRows(key, keep, fwd)
+        self._loss_rows = weakref.ref(out)
+        return out
 
     @property
     def n_local(self):

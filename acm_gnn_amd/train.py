@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import functional as AF
+from . import tuning
 from .graph import FilterOperators, SparseFeatures, operators_for
 
 _TORCH_DROPOUT = F.dropout          # to notice a patched F.dropout (mask replay in tests): see TrainStep
@@ -115,6 +116,15 @@ class TrainStep:
         ``flush_in_optimizer``: with this package's FusedAdam / FusedAdamW the step's deferred gradient sums are flushed by
         the optimizer's own launch (acm_adam_config_t.pending) instead of a launch of their own.
 
+        ``loss_rows`` (attribute): with the masked NLL on unsharded FilterOperators, when at least one row in eight has weight 0,
+        the step attaches the set of weighted rows to the operators ONCE, here (graph.FilterOperators.loss_rows: host-side
+        preprocessing that synchronises the device, so never inside the capture), and the output layer's forward gather and its
+        row pass skip the other rows (acm_conv_fwd_tail_rows; tuning key ``loss_rows``).  Loss and
+        parameters keep their bits; the logits of zero-weight rows are no longer computed inside the step.  ``loss_rows`` is
+        the graph.LossRows in use, or None with the reason in ``loss_rows_refused``.  The NONZERO PATTERN of ``weights`` is
+        fixed for the life of a captured step (as the reference fixes the split before its epoch loop, ACM-Geometric/train.py);
+        an eager step re-checks ``weights._version`` and re-attaches after an in-place edit.
+
         ``steps_per_graph`` (with ``use_graph``): capture that many consecutive optimizer steps in ONE hipGraph, so that a
         call runs them all (``steps_per_call``; the loss returned is the last one, ``losses`` holds every one) -- the ~8 us
         between two graph launches is then paid once per call instead of once per step.  Every captured step is a complete
@@ -200,8 +210,41 @@ class TrainStep:
             if why is None:
                 self.small = SmallPlan(model, self.x, self.adj, self.labels, self.weights, optimizer)
                 self.pipe = None
+        self.loss_rows, self.loss_rows_refused = None, "not requested"
+        if self.small is None:
+            self._attach_loss_rows()
         if use_graph:
             self._capture()
+
+    # below one zero-weight row in eight the forward gather can lose at most an eighth of its items (measured at one half: 52 ->
+    # 41 us, EXPERIMENTS.md) while the row pass pays for its divergent zero stores whatever the share: not worth an attachment
+    LOSS_ROWS_MIN_DROPPED = 0.125
+
+    def _attach_loss_rows(self):
+        """Build (or rebuild, after an in-place edit of the weights) the operators' loss-row attachment; never under capture."""
+        from . import _lib
+        old, self.loss_rows = self.loss_rows, None
+        ops, w = self.adj, self.weights
+        why = None
+        if self.criterion != "nll":
+            why = 'criterion="bce"'
+        elif not tuning.HOST.loss_rows:
+            why = "tuning: loss_rows=0"
+        elif not isinstance(ops, FilterOperators) or ops.sharded or ops.general:
+            why = "needs unsharded FilterOperators of the (A_low, I - A_low) pair"
+        elif not isinstance(w, torch.Tensor) or w.dim() != 1 or w.numel() != ops.low.n_rows:
+            why = "row weights of another shape"
+        elif w.is_cuda and torch.cuda.is_current_stream_capturing():
+            why = "the stream is capturing"
+        elif int((w == 0).sum()) < self.LOSS_ROWS_MIN_DROPPED * w.numel():
+            why = "fewer than one row in eight has weight 0"
+        elif any(getattr(_lib.load(), name, None) is None for name in _lib.LOSS_ROWS_SYMBOLS):
+            why = "the library lacks the loss-row entry points"
+        else:
+            self.loss_rows = ops.loss_rows(w, replaces=old)
+            if self.loss_rows is None:
+                why = "the operators refused (not square, or attached to another live step's weights)"
+        self.loss_rows_refused = why
 
     def _one_step(self):
         """Forward + loss + backward + update (+ the dropout counter's advance): one step, eager or under capture."""
@@ -305,7 +348,15 @@ class TrainStep:
         (wide output, structure channel, a wrapper around the output) the loss is its own launch."""
         if self.criterion == "bce":
             return self._forward_bce(call)
-        tail = call.tail = AF.fused_loss_tail(self.labels, self.weights)
+        lr = self.loss_rows
+        if lr is not None and not lr.current_for(self.weights):
+            # the weights were edited in place: re-attach -- or, under a capture (no host-side preprocessing there), the full path
+            if self.weights.is_cuda and torch.cuda.is_current_stream_capturing():
+                lr = None
+            else:
+                self._attach_loss_rows()
+                lr = self.loss_rows
+        tail = call.tail = AF.fused_loss_tail(self.labels, self.weights, loss_rows=lr)
         kw = {"call": call} if self._takes_call else {}
         if self._permuted:
             kw["rows_permuted"] = True
@@ -426,6 +477,8 @@ class TrainStep:
             self.graph = None
             if self.pipe is not None:
                 self.pipe.primed = False
+            if self.loss_rows is not None and not self.loss_rows.current_for(self.weights):
+                self._attach_loss_rows()        # (the old graph is gone: nothing replays over the attachment it replaces)
             self._capture()
 
     def _opt_step(self):

@@ -31,6 +31,10 @@ Host-level keys:
                acm_small_step): 0 = never, n > 0 = for graphs of at most n rows (the kernels take <= 16384).  Default 16384
     mlp_stack  deep mlpX stacks (Linear-ReLU-BatchNorm, init_layers_X > 1) on the acm_bnorm_* kernels with the BatchNorm folded
                into the Linears (functional.residual_mlp): 1 = on (default), 0 = the torch modules
+    loss_rows  train.TrainStep with the masked NLL: the output layer's forward gather and its row pass skip the rows whose loss
+               weight is 0 -- acm_conv_fwd_tail_rows over a loss-row attachment of the operator, built once per step object;
+               same bits as the full path.  1 = where it
+               applies (default), 0 = never
 
 One policy for a malformed ACM_TUNING in both readers: the item is REPORTED on stderr and IGNORED -- by the
 library when it is loaded, by this module when it is imported (``parse(text)`` itself stays strict for programmatic use:
@@ -46,9 +50,9 @@ import threading
 
 KERNEL_KEYS = ("chunk", "wide_form", "bwd_split", "rows16", "agg_fused", "gemm_forms")
 HOST_DEFAULTS = {"rewrites": 15, "implicit": 1, "relabel": -1, "pipeline": 8192, "csr_features": 256, "small_step": 16384,
-                 "mlp_stack": 1}
+                 "mlp_stack": 1, "loss_rows": 1}
 HOST_RANGES = {"rewrites": (0, 15), "implicit": (0, 1), "relabel": (-1, 1), "pipeline": (0, 1 << 31), "csr_features": (0, 1 << 31),
-               "small_step": (0, 16384), "mlp_stack": (0, 1)}
+               "small_step": (0, 16384), "mlp_stack": (0, 1), "loss_rows": (0, 1)}
 
 REWRITE_AGG_FIRST = 1
 REWRITE_ACMII_RECOMPUTE = 2

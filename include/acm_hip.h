@@ -177,6 +177,20 @@ int acm_csr_build_streams(acm_csr_t* a, int n_waves, int lmax);
  * acm_csr_info_t.item_stream_waves says whether (and for how many waves) they exist.  No reference counterpart. */
 int acm_csr_build_item_streams(acm_csr_t* a, int n_waves);
 
+/* acm_csr_build_loss_rows (new entry points under ABI 29; no struct changes): the loss-row attachment of a SQUARE operator,
+ * for the output layer of a training step whose masked loss gives weight 0 to every row outside a fixed set (the
+ * reference trains on out[train_idx] alone: ACM-Geometric/train.py:123-135).  keep_dev: n_rows bytes on the device,
+ * non-zero = the row carries weight.  The handle gets a work list over the kept rows alone -- a kept row has exactly the
+ * items of the handle's own list (same pieces, same summation order), a dropped row none; the list has its own long-row
+ * records, partial-slot numbers and windows -- and a device copy of `keep`.
+ * One-off host-side preprocessing like acm_csr_build_streams (synchronises the device; must not be called while a stream
+ * is capturing, nor while a launch that walks an earlier attachment of this handle may still be recorded in a graph that
+ * will be replayed).  Calling it again replaces the attachment; acm_csr_destroy frees it.
+ * acm_csr_loss_rows_info: out[0] kept rows, out[1] items of the row list, out[2] its partial slots, out[3] edges of kept
+ * rows (all 0 without an attachment). */
+int acm_csr_build_loss_rows(acm_csr_t* a, const uint8_t* keep_dev);
+int acm_csr_loss_rows_info(const acm_csr_t* a, int64_t* out);
+
 /* Bytes of caller-provided workspace the SpMM-type entry points need for an
  * operator when `width` fp32 columns are accumulated per row. */
 int acm_spmm_workspace_bytes(const acm_csr_t* a, int width, size_t* bytes);
@@ -990,6 +1004,19 @@ int acm_conv_fwd_tail_workspace_bytes(int64_t n_rows, int f_out, int n_channels,
 int acm_conv_fwd_tail(const acm_csr_t* a_low, const acm_conv_fwd_t* fwd, const acm_loss_t* loss,
                       const acm_conv_bwd_local_t* bwd, void* workspace, size_t workspace_bytes,
                       void* tail_workspace, size_t tail_workspace_bytes, acm_stream_t stream);
+
+/* The same step for a training loop whose row weights are zero outside a fixed set of rows (the reference's loss on
+ * out[train_idx]: ACM-Geometric/train.py:123-135), over the loss-row attachment of the operator (acm_csr_build_loss_rows).
+ * Same arguments as acm_conv_fwd_tail, same workspaces (the gather workspace also covers the list's own slot count,
+ * acm_csr_loss_rows_info out[2]).  The gather walks the attachment's row list, so rows outside the set are not aggregated
+ * at all; the row kernel keeps its thread-per-row mapping and block reductions and, for a row outside the set, loads and
+ * computes nothing and stores zeros to every per-row output (logits, pre, att, dlogits, the three G tables).  Needs the row
+ * list and f_out <= 4 (5..8: ACM_EUNSUPPORTED, the caller takes acm_conv_fwd_tail).  loss->row_weight must be zero exactly
+ * outside the set.  Rows of the set, the loss and the parameter-gradient sums equal acm_conv_fwd_tail's bit for bit (the
+ * sign of a zero aside): every kept row keeps its items and its order of summation, and the dropped rows' terms were zeros. */
+int acm_conv_fwd_tail_rows(const acm_csr_t* a_low, const acm_conv_fwd_t* fwd, const acm_loss_t* loss,
+                           const acm_conv_bwd_local_t* bwd, void* workspace, size_t workspace_bytes,
+                           void* tail_workspace, size_t tail_workspace_bytes, acm_stream_t stream);
 
 /* ------------------------------------------------ fused optimizer update --
  * Adam / AdamW over a list of fp32 parameter tensors in one launch per 40 tensors: the update of
