@@ -37,7 +37,10 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(long n_rows, int n_cols,
         const long r = q / n_cols;
         const int c = (int)(q - r * n_cols);
         unsigned b = __float_as_uint(src[r * ld_src + c]);
-        b += 0x7FFFu + ((b >> 16) & 1u);                 // round to nearest even
+        if ((b & 0x7FFFFFFFu) > 0x7F800000u)
+            b |= 0x00400000u;                            // NaN stays NaN (quiet, same sign): the carry below would make inf or 0 of some
+        else
+            b += 0x7FFFu + ((b >> 16) & 1u);             // round to nearest even
         dst[r * ld_dst + c] = (unsigned short)(b >> 16);
     }
 }

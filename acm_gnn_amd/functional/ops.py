@@ -186,6 +186,8 @@ def cast_bf16(src):
     _check_device(src, "src")
     n, c = src.shape
     dst = torch.empty(n, c, dtype=torch.bfloat16, device=src.device)
+    if n == 0 or c == 0:                          # (an empty tensor has no address to hand to the library)
+        return dst
     launch("acm_cast_bf16", f"cast_bf16/{n}x{c}", src.device, n, c, _vp(src), src.stride(0), _vp(dst), dst.stride(0))
     return dst
 

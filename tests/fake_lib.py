@@ -719,7 +719,8 @@ class FakeLib:
 
     def acm_cast_bf16(self, n, c, src, lds, dst, ldd, stream):
         b = _view(src, n, c, lds).copy().view(np.uint32)
-        b = b + 0x7FFF + ((b >> 16) & 1)
+        nan = (b & 0x7FFFFFFF) > 0x7F800000                  # NaN stays NaN (quiet, same sign), everything else rounds to nearest even
+        b = np.where(nan, b | 0x00400000, b + 0x7FFF + ((b >> 16) & 1))
         _view(dst, n, c, ldd, np.uint16)[...] = (b >> 16).astype(np.uint16)
         return 0
 
@@ -740,6 +741,9 @@ class FakeLib:
               bf16=0):
         import scipy.sparse as sp
         a = self._get(h)
+        if bf16 and not (8 < width <= 64 and width % 2 == 0):
+            self._err = b"acm_spmm: bf16 gathered operands are implemented for even 8 < F <= 64"
+            return 4
         v = _vec(vals, len(a.vals)).astype(np.float64) if vals else a.vals.astype(np.float64)
         m = sp.csr_matrix((v, a.indices, a.indptr), shape=(a.n_rows, a.n_cols))
         if bf16:
