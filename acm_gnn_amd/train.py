@@ -95,6 +95,31 @@ def _capture_mode():
     return {}
 
 
+def _operators_and_features(model, x, adj, adj_high, adj_un):
+    """(operators, features) a step or pass over ``model`` works on: the reference's adjacency TENSORS become the operator set
+    (the structure channel's degrees only for ACM-GCN+ / ++ with ``structure_info``), wide one-hot / bag-of-words features
+    handed over dense become their CSR twin (tuning csr_features).  Anything else is handed back as it came."""
+    ops = adj
+    if not isinstance(adj, FilterOperators) and isinstance(adj, torch.Tensor) and hasattr(model, "structure_info"):
+        four = model.structure_info and getattr(model, "model_type", "") in ("acmgcnp", "acmgcnpp")
+        ops = operators_for(adj, adj_high, adj_un if four else None)
+    if hasattr(model, "auto_csr"):
+        x = model.auto_csr(x, ops if isinstance(ops, FilterOperators) else None)
+    return ops, x
+
+
+def _warm_up(fn, times):
+    """``times`` eager calls of ``fn`` on a side stream before a capture (lazy handles, allocator pools, optimizer state);
+    the device is idle on return."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(times):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+
+
 class TrainStep:
     def __init__(self, model, optimizer, x, adj, labels, weights, adj_high=None, adj_un=None, use_graph=False,
                  fused_dropout=None, pipeline_input=None, steps_per_graph=1, flush_in_optimizer=True, small_step=None, tape=True,
@@ -140,20 +165,13 @@ class TrainStep:
         # of the step -- features, labels, row weights -- are moved into the operator's numbering ONCE, and the step
         # never leaves it (the loss does not care about the order of the rows).
         self._permuted = False
-        ops = adj
-        if not isinstance(adj, FilterOperators) and isinstance(adj, torch.Tensor) and hasattr(model, "structure_info"):
-            four = model.structure_info and getattr(model, "model_type", "") in ("acmgcnp", "acmgcnpp")
-            ops = operators_for(adj, adj_high, adj_un if four else None)
-            # the step keeps the operator set it built (the model's forward would look the same set up again, per call, by
-            # the tensors' identity): a caller that hands over the reference's adjacency TENSORS -- the drop-in loop,
-            # ACM-Pytorch/train.py:95-139 -- then reaches every plan that asks for FilterOperators, the fused small-graph
-            # step first of all (round 5: such a caller silently stayed on the general path)
-            self.adj = ops
-        if hasattr(model, "auto_csr"):
-            # wide one-hot / bag-of-words features handed over dense: the CSR twin, made here once (tuning csr_features)
-            self.x = x = model.auto_csr(x, ops if isinstance(ops, FilterOperators) else None)
+        # the step keeps the operator set it built (the model's forward would look the same set up again, per call, by
+        # the tensors' identity): a caller that hands over the reference's adjacency TENSORS -- the drop-in loop,
+        # ACM-Pytorch/train.py:95-139 -- then reaches every plan that asks for FilterOperators, the fused small-graph
+        # step first of all (round 5: such a caller silently stayed on the general path)
+        ops, x = _operators_and_features(model, x, adj, adj_high, adj_un)
+        self.adj, self.x = ops, x
         if isinstance(ops, FilterOperators) and ops.perm is not None and hasattr(model, "_forward"):
-            self.adj = ops
             self.x = x.permute_rows(ops.perm) if isinstance(x, SparseFeatures) else x.index_select(0, ops.perm)
             self.labels, self.weights = labels.index_select(0, ops.perm), weights.index_select(0, ops.perm)
             self._permuted = True
@@ -439,13 +457,7 @@ class TrainStep:
         # the optimizer moments / step counts and the dropout counter are put back afterwards, so a captured
         # TrainStep starts from exactly the state an eager one starts from (fit(epochs=N) trains N steps, not N + 3).
         snap = self._snapshot()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):           # warm-up off the capture: lazy handles, allocator pools
-            for _ in range(3):
-                self._eager()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
+        _warm_up(self._eager, 3)
         self._restore(snap)
         if self.pipe is not None:
             self.pipe.prime()                   # for the restored counter, outside the capture
@@ -601,13 +613,8 @@ class EvalStep:
         # small graphs: the evaluation forward as one call (small.SmallPlan without an optimizer)
         self.small, self.small_refused = None, "not requested"
         if small_step is not False:
-            from .graph import FilterOperators, operators_for
             from .small import SmallPlan
-            ops = adj
-            if not isinstance(adj, FilterOperators) and isinstance(adj, torch.Tensor) and hasattr(model, "structure_info"):
-                four = model.structure_info and getattr(model, "model_type", "") in ("acmgcnp", "acmgcnpp")
-                ops = operators_for(adj, adj_high, adj_un if four else None)
-            xs = model.auto_csr(x, ops if isinstance(ops, FilterOperators) else None) if hasattr(model, "auto_csr") else x
+            ops, xs = _operators_and_features(model, x, adj, adj_high, adj_un)
             self.small_refused = SmallPlan.why_not(model, xs, ops, None, need_dropout_state=False)
             if self.small_refused is None:
                 self.small = SmallPlan(model, xs, ops)
@@ -652,9 +659,12 @@ class EvalStep:
             # instead of argmax / compare / log_softmax / gather / matmul / sum / cat (eight torch launches)
             return out, AF.eval_metrics(out, self.labels, self.w, self.loss_set, self._metrics_buffers(out))
         correct = (out.argmax(dim=1) == self.labels).to(torch.float32)
+        return out, torch.cat([self.w @ correct, self._weighted_nll(out).view(1)])
+
+    def _weighted_nll(self, out):
+        """The NLL of the logits averaged over ``loss_set`` (its row of the averaging weights), in torch operations."""
         nll = -F.log_softmax(out, 1).gather(1, self._labels_safe.view(-1, 1)).view(-1)
-        res = torch.cat([self.w @ correct, (self.w[self.loss_set] * nll).sum().view(1)])
-        return out, res
+        return (self.w[self.loss_set] * nll).sum()
 
     def _second_protocol(self, out):
         """[metric per index set ..., loss on ``loss_set``] in float64 for ``metric="rocauc"`` and / or ``criterion="bce"``:
@@ -668,8 +678,7 @@ class EvalStep:
         if self.criterion == "bce":
             loss = AF.bce_loss(out, self.labels, self.w[self.loss_set])
         else:
-            nll = -F.log_softmax(out, 1).gather(1, self._labels_safe.view(-1, 1)).view(-1)
-            loss = (self.w[self.loss_set] * nll).sum()
+            loss = self._weighted_nll(out)
         return torch.cat([per_set, loss.double().view(1)])
 
     def _metrics_ok(self, out):
@@ -685,13 +694,7 @@ class EvalStep:
         return self._metrics
 
     def _capture(self):
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):           # warm-up off the capture (lazy handles, allocator pools)
-            for _ in range(2):
-                self._run()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
+        _warm_up(self._run, 2)
         if self.selector is not None:
             self.selector.reset()               # the warm-up passes folded two epochs in
             torch.cuda.synchronize()
@@ -755,36 +758,20 @@ def fit(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, 
                            exceeds the mean of the last `early_stopping` epochs
                            (ACM-Pytorch/train.py:129-139)
     """
-    if _resident_loop(sync_every, keep_best):
-        return _fit_resident(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, rule, early_stopping,
-                             adj_high, adj_un, use_graph, fused_dropout, pipeline_input, criterion, metric, sync_every, keep_best)
-    w = row_weights(train_idx, x.shape[0], device=x.device)
-    _checked(metric, METRICS, "metric")
-    step = TrainStep(model, optimizer, x, adj, labels, w, adj_high, adj_un, use_graph=use_graph,
-                     fused_dropout=fused_dropout, pipeline_input=pipeline_input, criterion=criterion)
-    best_key, selected, history = None, 0.0, []
-    val_hist = []
-    # the evaluation pass of every epoch: its own captured graph when the training step is one
-    ev = EvalStep(model, x, adj, labels, (train_idx, val_idx, test_idx), adj_high, adj_un, loss_set=1,
-                  use_graph=use_graph, metric=metric, criterion=criterion) if use_graph else None
-    for epoch in range(epochs):
-        loss = step()
-        if ev is not None:
-            out, (acc_tr, acc_va, acc_te), val_loss = ev()
-        else:
-            out, (acc_tr, acc_va, acc_te) = evaluate(model, x, adj, labels, (train_idx, val_idx, test_idx),
-                                                     adj_high, adj_un, metric=metric)
-            val_loss = _eager_val_loss(out, labels, val_idx, criterion)
-        history.append((float(loss), acc_tr, acc_va, acc_te, val_loss))
-        key = _selection_key(rule, acc_va, val_loss)
-        if key is not None and (best_key is None or key > best_key):
-            best_key, selected = key, acc_te
-        if rule == "min_val_loss":
-            val_hist.append(val_loss)
-            if early_stopping > 0 and epoch > early_stopping:
-                if val_loss > sum(val_hist[epoch - early_stopping:epoch]) / early_stopping:
-                    break
-    return selected, history
+    resident = _resident_loop(sync_every, keep_best)
+    if resident and not use_graph:
+        raise ValueError("fit(sync_every > 1 or keep_best=True) needs use_graph=True: the selection launches ride the captured "
+                         "evaluation pass")
+    if resident and int(epochs) < 1:
+        return 0.0, []
+    args = (model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, rule, early_stopping, adj_high, adj_un,
+            fused_dropout, pipeline_input, criterion, metric)
+    run = _ResidentRun(*args, keep_best) if resident else _HostRun(*args, use_graph)
+    done = int(epochs) < 1                  # (the host-selected run has built, and with use_graph captured, its step by now)
+    while not done:
+        run.enqueue(sync_every)
+        done = run.finished()
+    return run.result()
 
 
 def _resident_loop(sync_every, keep_best):
@@ -835,59 +822,82 @@ class _ResidentRun:
         return selected, history
 
 
-def _fit_resident(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, rule, early_stopping, adj_high, adj_un,
-                  use_graph, fused_dropout, pipeline_input, criterion, metric, sync_every, keep_best):
-    if not use_graph:
-        raise ValueError("fit(sync_every > 1 or keep_best=True) needs use_graph=True: the selection launches ride the captured "
-                         "evaluation pass")
-    if int(epochs) < 1:
-        return 0.0, []
-    run = _ResidentRun(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, rule, early_stopping, adj_high,
-                       adj_un, fused_dropout, pipeline_input, criterion, metric, keep_best)
-    while True:
-        run.enqueue(sync_every)
-        if run.finished():
-            return run.result()
+class _HostRun:
+    """One run of ``fit`` with the selection on the host, behind the three methods of ``_ResidentRun``: the training step, the
+    captured evaluation pass (without ``use_graph`` an epoch is ``evaluate`` + ``_eager_val_loss``), the history and the
+    selection.  The host loop's selection and early-stopping rule is stated once, in ``_fold``."""
+
+    def __init__(self, model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, rule, early_stopping, adj_high,
+                 adj_un, fused_dropout, pipeline_input, criterion, metric, use_graph):
+        _checked(metric, METRICS, "metric")
+        self.epochs, self.rule, self.early_stopping = epochs, rule, early_stopping
+        self.best_key, self.selected, self.history, self.val_hist = None, 0.0, [], []
+        w = row_weights(train_idx, x.shape[0], device=labels.device)
+        self.step = TrainStep(model, optimizer, x, adj, labels, w, adj_high, adj_un, use_graph=use_graph,
+                              fused_dropout=fused_dropout, pipeline_input=pipeline_input, criterion=criterion)
+        self.labels, self.val_idx, self.metric, self.criterion = labels, val_idx, metric, criterion
+        self.eval_args = (model, x, adj, labels, (train_idx, val_idx, test_idx), adj_high, adj_un)   # EvalStep's and evaluate's
+        # the evaluation pass of every epoch: its own captured graph when the training step is one
+        self.ev = EvalStep(*self.eval_args, loss_set=1, use_graph=True, metric=metric, criterion=criterion) if use_graph else None
+
+    def enqueue(self, sync_every):
+        """One epoch (step + evaluation pass) on the current stream: this loop IS ``sync_every = 1``, whatever it is handed."""
+        self.loss = self.step()
+        if self.ev is not None:
+            self.ev.launch()
+
+    def finished(self):
+        """The epoch's synchronising read (the pass's numbers, then the loss), folded in; True once the run has stopped or used
+        its budget up."""
+        if self.ev is not None:
+            _, accs, val_loss = self.ev.read()
+        else:
+            out, accs = evaluate(*self.eval_args, metric=self.metric)
+            val_loss = _eager_val_loss(out, self.labels, self.val_idx, self.criterion)
+        return self._fold(float(self.loss), accs, val_loss)
+
+    def _fold(self, loss, accs, val_loss):
+        """Append the epoch's row; "best so far" by ``_selection_key`` (strict ``>``); under "min_val_loss" stop when the
+        validation loss exceeds the mean of the ``early_stopping`` epochs before it (``sum(...) / early_stopping``: see ``fit``)."""
+        epoch, (acc_tr, acc_va, acc_te) = len(self.history), accs
+        self.history.append((loss, acc_tr, acc_va, acc_te, val_loss))
+        key = _selection_key(self.rule, acc_va, val_loss)
+        if key is not None and (self.best_key is None or key > self.best_key):
+            self.best_key, self.selected = key, acc_te
+        stop, es = False, self.early_stopping
+        if self.rule == "min_val_loss":
+            self.val_hist.append(val_loss)
+            stop = es > 0 and epoch > es and val_loss > sum(self.val_hist[epoch - es:epoch]) / es
+        return stop or epoch + 1 >= self.epochs
+
+    def result(self):
+        return self.selected, self.history
 
 
-def _fit_concurrent_resident(runs, x, adj, labels, epochs, rule, early_stopping, adj_high, adj_un, streams, fused_dropout,
-                             criterion, metric, sync_every, keep_best):
-    """fit_concurrent with every run's selection state on the device."""
-    if int(epochs) < 1:
-        return [(0.0, []) for _ in runs]
-    results = [None] * len(runs)
-    on_gpu = labels.is_cuda and torch.cuda.is_available()
-    if not on_gpu or streams <= 1:
-        for k, (model, opt, tr, va, te) in enumerate(runs):
-            results[k] = fit(model, opt, x, adj, labels, tr, va, te, epochs, rule=rule, early_stopping=early_stopping,
-                             adj_high=adj_high, adj_un=adj_un, use_graph=True, fused_dropout=fused_dropout, criterion=criterion,
-                             metric=metric, sync_every=sync_every, keep_best=keep_best)
-        return results
-    pending = list(range(len(runs)))
-    slots = [None] * min(int(streams), len(runs))
+def _run_on_streams(start, n_runs, streams, sync_every):
+    """``start(k)`` builds run ``k`` (a ``_HostRun`` or a ``_ResidentRun``); at most ``streams`` of the ``n_runs`` are alive at a
+    time, each on a stream of its own, and a finished run's stream goes to the next pending one.  Results in the order of k."""
+    results, pending = [None] * n_runs, list(range(n_runs))
+    slots = [None] * min(int(streams), n_runs)
     pool = [torch.cuda.Stream() for _ in slots]
-
-    def start(k, stream):
-        model, opt, tr, va, te = runs[k]
-        with torch.cuda.stream(stream):
-            run = _ResidentRun(model, opt, x, adj, labels, tr, va, te, epochs, rule, early_stopping, adj_high, adj_un,
-                               fused_dropout, None, criterion, metric, keep_best)
-        stream.synchronize()
-        return k, run
-
     while pending or any(sl is not None for sl in slots):
         for i in range(len(slots)):
             if slots[i] is None and pending:
-                slots[i] = start(pending.pop(0), pool[i])
+                k = pending.pop(0)
+                with torch.cuda.stream(pool[i]):         # built and captured on the stream it will run on
+                    slots[i] = k, start(k)
+                pool[i].synchronize()
         live = [(i, sl) for i, sl in enumerate(slots) if sl is not None]
-        for i, (k, run) in live:                         # every live run's epochs are enqueued before any state is awaited
+        for i, (k, run) in live:                         # every live run's epochs are enqueued before any result is awaited
             with torch.cuda.stream(pool[i]):
                 run.enqueue(sync_every)
         for i, (k, run) in live:
             with torch.cuda.stream(pool[i]):
                 if run.finished():
                     results[k] = run.result()
-                    pool[i].synchronize()                # keep_best: the restore was enqueued HERE, the caller reads elsewhere
+                    # keep_best: the restore was enqueued HERE, the caller reads elsewhere.  (A host-selected run's stream is
+                    # already drained by its epoch's read: one call that waits for nothing.)
+                    pool[i].synchronize()
                     slots[i] = None
     return results
 
@@ -910,61 +920,22 @@ def fit_concurrent(runs, x, adj, labels, epochs, rule="min_val_loss", early_stop
     selected parameters on return, whatever stream the caller uses).  These need the captured graphs: the one-after-the-other
     path (``streams <= 1``) then calls ``fit(use_graph=True)``, so unlike the default path it does not run without a GPU
     (the CPU tests stub the capture)."""
-    if _resident_loop(sync_every, keep_best):
-        return _fit_concurrent_resident(runs, x, adj, labels, epochs, rule, early_stopping, adj_high, adj_un, streams,
-                                        fused_dropout, criterion, metric, sync_every, keep_best)
-    results = [None] * len(runs)
+    resident = _resident_loop(sync_every, keep_best)
+    if resident and int(epochs) < 1:
+        return [(0.0, []) for _ in runs]
     on_gpu = labels.is_cuda and torch.cuda.is_available()
     if not on_gpu or streams <= 1:
-        for k, (model, opt, tr, va, te) in enumerate(runs):
-            results[k] = fit(model, opt, x, adj, labels, tr, va, te, epochs, rule=rule, early_stopping=early_stopping,
-                             adj_high=adj_high, adj_un=adj_un, use_graph=on_gpu, fused_dropout=fused_dropout,
-                             criterion=criterion, metric=metric)
-        return results
-    pending = list(range(len(runs)))
-    slots = [None] * min(int(streams), len(runs))
-    pool = [torch.cuda.Stream() for _ in slots]
+        return [fit(model, opt, x, adj, labels, tr, va, te, epochs, rule=rule, early_stopping=early_stopping, adj_high=adj_high,
+                    adj_un=adj_un, use_graph=on_gpu or resident, fused_dropout=fused_dropout, criterion=criterion, metric=metric,
+                    sync_every=sync_every, keep_best=keep_best) for model, opt, tr, va, te in runs]
 
-    def start(k, stream):
+    def start(k):
         model, opt, tr, va, te = runs[k]
-        with torch.cuda.stream(stream):
-            w = row_weights(tr, x.shape[0], device=labels.device)
-            step = TrainStep(model, opt, x, adj, labels, w, adj_high, adj_un, use_graph=True, fused_dropout=fused_dropout,
-                             criterion=criterion)
-            ev = EvalStep(model, x, adj, labels, (tr, va, te), adj_high, adj_un, loss_set=1, use_graph=True, metric=metric,
-                          criterion=criterion)
-        stream.synchronize()
-        return dict(k=k, step=step, ev=ev, epoch=0, best=None, selected=0.0, history=[], vals=[])
+        args = (model, opt, x, adj, labels, tr, va, te, epochs, rule, early_stopping, adj_high, adj_un, fused_dropout, None,
+                criterion, metric)
+        return _ResidentRun(*args, keep_best) if resident else _HostRun(*args, True)
 
-    while pending or any(sl is not None for sl in slots):
-        for i in range(len(slots)):
-            if slots[i] is None and pending:
-                slots[i] = start(pending.pop(0), pool[i])
-        live = [(i, sl) for i, sl in enumerate(slots) if sl is not None]
-        for i, sl in live:                               # every live run's epoch is enqueued before any result is awaited
-            with torch.cuda.stream(pool[i]):
-                sl["loss"] = sl["step"]()
-                sl["ev"].launch()
-        for i, sl in live:
-            with torch.cuda.stream(pool[i]):
-                _, (acc_tr, acc_va, acc_te), val_loss = sl["ev"].read()
-                loss = float(sl["loss"])
-            sl["history"].append((loss, acc_tr, acc_va, acc_te, val_loss))
-            key = _selection_key(rule, acc_va, val_loss)
-            if key is not None and (sl["best"] is None or key > sl["best"]):
-                sl["best"], sl["selected"] = key, acc_te
-            epoch = sl["epoch"]
-            done = epoch + 1 >= epochs
-            if rule == "min_val_loss":
-                sl["vals"].append(val_loss)
-                if early_stopping > 0 and epoch > early_stopping and \
-                        val_loss > sum(sl["vals"][epoch - early_stopping:epoch]) / early_stopping:
-                    done = True
-            sl["epoch"] = epoch + 1
-            if done:
-                results[sl["k"]] = (sl["selected"], sl["history"])
-                slots[i] = None
-    return results
+    return _run_on_streams(start, len(runs), streams, sync_every)
 
 
 # The smallest measured batch size within 3 % of the best one on the Squirrel-shaped workload (scripts/bench_batched_fit.py on
@@ -1027,13 +998,9 @@ def fit_batched(runs, x, adj, labels, epochs, rule="min_val_loss", early_stoppin
 
     if _is_sharded(adj):
         return fallback("row-sharded operators")
-    # one operator set and one feature object for every run (TrainStep would build them per run: the plans must SHARE them)
-    ops = adj
-    if not isinstance(adj, FilterOperators) and isinstance(adj, torch.Tensor) and hasattr(runs[0][0], "structure_info"):
-        m0 = runs[0][0]
-        four = m0.structure_info and getattr(m0, "model_type", "") in ("acmgcnp", "acmgcnpp")
-        ops = operators_for(adj, None, adj if four else None)
-    xs = runs[0][0].auto_csr(x, ops if isinstance(ops, FilterOperators) else None) if hasattr(runs[0][0], "auto_csr") else x
+    # one operator set and one feature object for every run (TrainStep would build them per run: the plans must SHARE them).
+    # This loop takes no adj_high / adj_un: an adjacency TENSOR is handed on as its own un-normalised twin, as it always was.
+    ops, xs = _operators_and_features(runs[0][0], x, adj, None, adj)
     # every run against the envelope before anything is built: the fallback is decided here, not in the middle of the loop
     from .small import SmallPlan
     shape0 = None
@@ -1094,13 +1061,7 @@ def fit_batched(runs, x, adj, labels, epochs, rule="min_val_loss", early_stoppin
         # as TrainStep._capture: warm up on a snapshot of every run in a slot, put it back, then capture -- no run sees the
         # warm-up steps; the selection states are reset (the warm-up folded epochs in)
         snaps = [r.step._snapshot() for r in live]
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(3):
-                epoch()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
+        _warm_up(epoch, 3)
         for r, snap in zip(live, snaps):
             r.step._restore(snap)
         for i in range(n_slots):

@@ -186,6 +186,33 @@ def test_fit_concurrent_keep_best_on_streams_returns_the_selected_models(rule):
     assert not_last, "every run selected its last epoch: the restore is not exercised"
 
 
+@pytest.mark.parametrize("rule,es", [("max_val_acc", 0), ("min_val_loss", 3)])
+def test_host_selected_fit_concurrent_with_more_runs_than_streams_equals_fit(rule, es):
+    """The host-selected path of fit_concurrent (sync_every=1): a baseline GCN (the general path) and two acmgcn runs (the fused
+    small-graph plan) on two streams, so the third run takes over a freed slot -- each equals fit(use_graph=True) of it alone."""
+    from acm_gnn_amd import train as T
+    ops, xs, x, y, sets0, n, *_ = _problem("synthetic")
+    kinds = ("gcn", "acmgcn", "acmgcn")
+
+    def split(k):
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(k)).to(DEV)
+        return idx[: n // 2], idx[n // 2: 3 * n // 4], idx[3 * n // 4:]
+
+    def make(k):
+        model, opt, _ = _make("synthetic", kinds[k], seed=k)
+        return (model, opt) + split(k)
+
+    runs = [make(k) for k in range(3)]
+    got = T.fit_concurrent(runs, xs, ops, y, 10, rule=rule, early_stopping=es, streams=2)
+    for k in range(3):
+        alone = make(k)
+        want = T.fit(alone[0], alone[1], xs, ops, y, *alone[2:], 10, rule=rule, early_stopping=es, use_graph=True)
+        assert _same(got[k], want) and 1 <= len(want[1]) <= 10, k
+        assert all(torch.equal(p, q) for p, q in zip(runs[k][0].parameters(), alone[0].parameters())), k
+        step = T.TrainStep(*make(k)[:2], xs, ops, y, T.row_weights(alone[2], n, device=y.device))
+        assert (step.small is not None) == (kinds[k] == "acmgcn"), (k, step.small_refused)
+
+
 def test_resident_loop_needs_the_captured_graphs():
     from acm_gnn_amd import train as T
     ops, xs, x, y, sets, *_ = _problem("synthetic")

@@ -299,6 +299,131 @@ def test_a_dropped_rule_would_show(monkeypatch):
     assert differ, "both rules select the same test metric in every run: choose another problem"
 
 
+class _InertStream:
+    """Stands in for torch.cuda.Stream and, as ``_InertStream.use``, for torch.cuda.stream: nothing here touches a device."""
+    made = []
+
+    def __init__(self):
+        self.made.append(self)
+        self.entered = 0
+
+    def synchronize(self):
+        pass
+
+    def use(self):
+        import contextlib
+        self.entered += 1
+        return contextlib.nullcontext()
+
+
+class _FakeRun:
+    """A run that is finished after ``rounds`` calls of ``finished()``; every call goes to the shared log."""
+
+    def __init__(self, name, rounds, log):
+        self.name, self.rounds, self.log = name, rounds, log
+
+    def enqueue(self, sync_every):
+        self.log.append((self.name, "enqueue"))
+
+    def finished(self):
+        self.log.append((self.name, "finished"))
+        self.rounds -= 1
+        return self.rounds == 0
+
+    def result(self):
+        self.log.append((self.name, "result"))
+        return self.name
+
+
+def test_the_stream_scheduler_on_five_runs_and_two_slots(monkeypatch):
+    """train._run_on_streams, the one scheduler of fit_concurrent, with runs that finish after 3, 1, 4, 1 and 2 rounds."""
+    from acm_gnn_amd import train as T
+    monkeypatch.setattr(_InertStream, "made", [])
+    monkeypatch.setattr(torch.cuda, "Stream", _InertStream)
+    monkeypatch.setattr(torch.cuda, "stream", _InertStream.use)
+    log = []
+    runs = [_FakeRun(name, rounds, log) for name, rounds in zip("abcde", (3, 1, 4, 1, 2))]
+
+    def start(k):
+        log.append((runs[k].name, "start"))
+        return runs[k]
+
+    assert T._run_on_streams(start, 5, 2, 1) == list("abcde")               # the results, in the order of the runs
+    assert len(_InertStream.made) == 2 and all(s.entered for s in _InertStream.made)
+    # a round = the entries from one "start or enqueue" stretch up to the next: slot filling, every enqueue, then the reads
+    rounds, phase = [], None
+    for name, what in log:
+        if what in ("start", "enqueue") and phase not in ("start", "enqueue"):
+            rounds.append([])
+        rounds[-1].append((name, what))
+        phase = what
+    live_want = ["ab", "ac", "ac", "dc", "ec", "e"]       # b leaves after round 0 (-> c), a after 2 (-> d), d after 3 (-> e)
+    assert len(rounds) == len(live_want)
+    for entries, live in zip(rounds, live_want):
+        whats = [w for _, w in entries if w != "result"]
+        first_read = whats.index("finished")
+        assert "enqueue" not in whats[first_read:] and "start" not in whats[first_read:], entries
+        assert [n for n, w in entries if w == "enqueue"] == list(live) == [n for n, w in entries if w == "finished"], entries
+    assert [n for n, w in log if w == "start"] == list("abcde")             # freed slots go to the pending runs in order
+    assert [[n for n, w in r if w == "start"] for r in rounds] == [["a", "b"], ["c"], [], ["d"], ["e"], []]
+    for run in runs:
+        calls = [w for n, w in log if n == run.name]
+        assert calls.count("result") == 1 and calls[-2:] == ["finished", "result"] and run.rounds == 0, (run.name, calls)
+
+
+class _RowsStep:
+    """TrainStep's and EvalStep's double for the host loop: hands out the rows of a recorded sequence, one per epoch."""
+    rows, made = [], []
+
+    def __init__(self, *args, **kw):
+        self.made.append(self)
+        self.epoch, self.small_refused = -1, None
+
+    def __call__(self):                                 # TrainStep(): the loss -- a tensor, as the loop calls float() on it
+        self.epoch += 1
+        return torch.tensor(self.rows[self.epoch][0], dtype=torch.float64)
+
+    def launch(self):
+        self.epoch += 1
+
+    def read(self):
+        row = self.rows[self.epoch]
+        return None, list(row[1:4]), row[4]
+
+
+@pytest.mark.parametrize("name", sorted(SEQUENCES))
+@pytest.mark.parametrize("rule,es", [("max_val_acc", 0), ("max_val_acc", 3), ("min_val_loss", 0), ("min_val_loss", 3)])
+@pytest.mark.parametrize("use_graph", [True, False])
+def test_the_host_loop_states_the_rule_of_select_ref(monkeypatch, name, rule, es, use_graph):
+    """The ONE statement of the host rule (train._HostRun, reached through ``fit`` with its step and pass replaced by rows) against
+    the restated loop: both rules, windows 0 and 3, NaN validation metrics, an early stop strictly inside the budget."""
+    from acm_gnn_amd import train as T
+    rows = SEQUENCES[name]
+    monkeypatch.setattr(_RowsStep, "rows", rows)
+    monkeypatch.setattr(_RowsStep, "made", [])
+    monkeypatch.setattr(T, "TrainStep", _RowsStep)
+    monkeypatch.setattr(T, "EvalStep", _RowsStep)
+    seen = []
+
+    def evaluate(*args, metric="acc"):
+        seen.append(len(seen))
+        return len(seen) - 1, list(rows[len(seen) - 1][1:4])
+
+    monkeypatch.setattr(T, "evaluate", evaluate)
+    monkeypatch.setattr(T, "_eager_val_loss", lambda out, labels, val_idx, criterion: rows[out][4])
+    idx = torch.arange(2)
+    got = T.fit(None, None, torch.zeros(4, 1), None, torch.zeros(4, dtype=torch.long), idx, idx, idx, len(rows), rule=rule,
+                early_stopping=es, use_graph=use_graph)
+    want = select_ref(rows, rule, es)
+    assert same_floats(got[0], want[0]) and same_floats(got[1], want[1])
+    assert len(_RowsStep.made) == (2 if use_graph else 1) and (bool(seen) != use_graph)
+    assert all(s.epoch == len(want[1]) - 1 for s in _RowsStep.made)          # nothing was enqueued past the stop
+    if name == "stop" and rule == "min_val_loss" and es:
+        assert len(got[1]) == 7 < len(rows)
+    else:
+        assert len(got[1]) == len(rows)
+
+
 def test_refresh_is_refused_once_the_run_has_begun(monkeypatch):
     _install(monkeypatch)
     from acm_gnn_amd import functional as AF, train as T
