@@ -37,12 +37,16 @@ EXPORTED_SYMBOLS = (
     "acm_select_step", "acm_copy_if",
     "acm_small_batch_table_bytes", "acm_small_batch_bind", "acm_small_batch_step", "acm_eval_metrics_batch", "acm_select_step_batch",
     "acm_bnorm_stats_workspace_bytes", "acm_bnorm_stats", "acm_bnorm_fold", "acm_bnorm_param_bwd", "acm_bnorm_bwd_workspace_bytes", "acm_bnorm_bwd",
+    "acm_linear_fwd_shift", "acm_gemm_shift", "acm_bnorm_fold_centred", "acm_bnorm_param_bwd_centred",
     "acm_proj_blocks_fwd", "acm_proj_blocks_bwd_workspace_bytes", "acm_proj_blocks_bwd",
     "acm_csr_build_loss_rows", "acm_csr_loss_rows_info", "acm_conv_fwd_tail_rows",
 )
 # the loss-row entry points (new symbols under ABI 29): callers look them up with getattr(lib, name, None) and keep the full
 # path where a library -- or a test double -- does not have them
 LOSS_ROWS_SYMBOLS = ("acm_csr_build_loss_rows", "acm_csr_loss_rows_info", "acm_conv_fwd_tail_rows")
+# the centred form of a deep mlpX stack (new symbols under ABI 29, looked up the same way): all four together, or the first form of
+# the stack (acm_bnorm_fold + acm_linear_fwd, acm_gemm + acm_bnorm_param_bwd) where a library or a test double lacks one
+BNORM_CENTRED_SYMBOLS = ("acm_bnorm_fold_centred", "acm_linear_fwd_shift", "acm_gemm_shift", "acm_bnorm_param_bwd_centred")
 
 
 class Dropout(C.Structure):
@@ -376,6 +380,10 @@ def _declare(lib):
     lib.acm_bnorm_stats.argtypes = [i64, i32, vp, i64, vp, vp, C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, sz, vp]
     lib.acm_bnorm_fold.argtypes = [i32, i32, vp, i64, vp, vp, vp, i64, vp, vp]
     lib.acm_bnorm_param_bwd.argtypes = [i32, i32, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp]
+    lib.acm_bnorm_fold_centred.argtypes = [i32, i32, vp, i64, vp, vp, vp, vp, i64, vp, vp]
+    lib.acm_bnorm_param_bwd_centred.argtypes = [i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp]
+    lib.acm_linear_fwd_shift.argtypes = [i64, i64, i64, vp, i64, vp, vp, i64, vp, i32, vp, vp, i64, vp, sz, vp]
+    lib.acm_gemm_shift.argtypes = [i32, i32, i64, i64, i64, vp, i64, vp, i64, vp, vp, i64, vp, sz, vp]
     lib.acm_bnorm_bwd_workspace_bytes.argtypes = [i64, i32, C.POINTER(sz)]
     lib.acm_bnorm_bwd.argtypes = [i64, i32, vp, i64, vp, i64, vp, vp, vp, C.c_float, i32, vp, i64, vp, vp, sz, vp, vp]
     lib.acm_reduce_flush.argtypes = [vp, vp]

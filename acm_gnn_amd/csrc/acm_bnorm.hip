@@ -1,8 +1,14 @@
 // BatchNorm1d between the Linears of a deep mlpX stack (ACM-Pytorch/models/layers.py:245-285: lin -> relu -> bn -> dropout,
 // ACM-Pytorch/models/models.py:37-41,150-152), folded into the Linears on both sides of it:
 //   acm_bnorm_stats      column statistics of H = relu(...) [n, f] -> (mu, r, a, c) and the running buffers
-//   acm_bnorm_fold       W' = W diag(a), b' = b + W c: the next Linear reads H itself, Z = a * H + c is never written
-//   acm_bnorm_param_bwd  dW, d_beta, d_gamma of that pair from the f x f matrices M = G^T H and s = colsum(G)
+//   acm_bnorm_fold_centred       W' = W diag(a), b' = b + W beta: the next Linear reads H - 1 mu^T, subtracted where its product
+//                        stages H (acm_linear_fwd_shift); Z = a * (H - mu) + beta is never written
+//   acm_bnorm_param_bwd_centred  dW, d_beta, d_gamma of that pair from the f x f matrices M_c = G^T (H - 1 mu^T) (acm_gemm_shift)
+//                        and s = colsum(G)
+//   acm_bnorm_fold / acm_bnorm_param_bwd  the same pair for products on H itself (b' = b + W c, M = G^T H): the first form of the
+//                        stack, kept for callers of the C ABI
+// The package takes the CENTRED pair: on a column whose mean is far above its spread (a unit that is always on) a * H + c and
+// M a + s c cancel all but the digits the statistics kernel took care to keep.
 //   acm_bnorm_bwd        the one row-local pass of the backward: G_i = [H > 0] a (dZ - d_beta / n - xhat d_gamma / n) and
 //                        its column sums (or, without statistics, the stack's output epilogue read off Y as acm_bias_act_bwd does)
 // Row-major matrices of f <= 256 columns.  The 256 threads of a block are (row slice, column group): f / V threads share a
@@ -183,17 +189,18 @@ __global__ __launch_bounds__(256) void bn_stats_eval_kernel(int f, BnFinal p) {
     }
 }
 
-// Block o: row o of W' = W diag(a) and b'[o] = b[o] + sum_k W[o, k] c[k] (binary tree over the 256 threads)
+// Block o: row o of W' = W diag(a) and b'[o] = b[o] + sum_k W[o, k] beta[k] (binary tree over the 256 threads); beta NULL: the
+// uncentred form, c[k] = stats row 3 in beta's place
 __global__ __launch_bounds__(256) void bn_fold_kernel(int f_in, const float* __restrict__ w, long ldw, const float* __restrict__ bias,
-                                                      const float* __restrict__ stats, float* __restrict__ wf, long ldwf,
-                                                      float* __restrict__ bias_f) {
+                                                      const float* __restrict__ beta, const float* __restrict__ stats,
+                                                      float* __restrict__ wf, long ldwf, float* __restrict__ bias_f) {
     __shared__ float red[256];
     const int o = blockIdx.x, k = threadIdx.x;
     float t = 0.f;
     if (k < f_in) {
         const float wv = w[(long)o * ldw + k];
         wf[(long)o * ldwf + k] = wv * stats[2 * f_in + k];
-        t = wv * stats[3 * f_in + k];
+        t = wv * (beta ? beta[k] : stats[3 * f_in + k]);
     }
     red[k] = t;
     __syncthreads();
@@ -204,24 +211,26 @@ __global__ __launch_bounds__(256) void bn_fold_kernel(int f_in, const float* __r
     if (k == 0) bias_f[o] = (bias ? bias[o] : 0.f) + red[0];
 }
 
-// Thread = input column k of the Linear behind the BatchNorm, rows o in order:
-//   dW[o, k] = M[o, k] a[k] + s[o] c[k]     d_beta[k] = sum_o s[o] W[o, k]     d_gamma[k] = r[k] (sum_o W[o, k] M[o, k] - mu[k] d_beta[k])
+// Thread = input column k of the Linear behind the BatchNorm, rows o in order, M = M_c = G^T (H - 1 mu^T):
+//   dW[o, k] = M[o, k] a[k] + s[o] beta[k]     d_beta[k] = sum_o s[o] W[o, k]     d_gamma[k] = r[k] sum_o W[o, k] M[o, k]
+// beta NULL: the uncentred form, M = G^T H:  dW = M a + s c,  d_gamma[k] = r[k] (sum_o W[o, k] M[o, k] - mu[k] d_beta[k])
 __global__ __launch_bounds__(64) void bn_param_bwd_kernel(int f_out, int f_in, const float* __restrict__ m, long ldm,
                                                           const float* __restrict__ s, const float* __restrict__ w, long ldw,
-                                                          const float* __restrict__ stats, float* __restrict__ dw, long lddw,
-                                                          float* __restrict__ d_beta, float* __restrict__ d_gamma) {
+                                                          const float* __restrict__ beta, const float* __restrict__ stats,
+                                                          float* __restrict__ dw, long lddw, float* __restrict__ d_beta,
+                                                          float* __restrict__ d_gamma) {
     const int k = blockIdx.x * 64 + threadIdx.x;
     if (k >= f_in) return;
-    const float mu = stats[k], r = stats[f_in + k], a = stats[2 * f_in + k], c = stats[3 * f_in + k];
+    const float r = stats[f_in + k], a = stats[2 * f_in + k], bt = beta ? beta[k] : stats[3 * f_in + k];
     float db = 0.f, q = 0.f;
     for (int o = 0; o < f_out; ++o) {
         const float mv = m[(long)o * ldm + k], wv = w[(long)o * ldw + k], so = s[o];
-        dw[(long)o * lddw + k] = fmaf(mv, a, so * c);
+        dw[(long)o * lddw + k] = fmaf(mv, a, so * bt);
         db = fmaf(so, wv, db);
         q = fmaf(wv, mv, q);
     }
     d_beta[k] = db;
-    d_gamma[k] = r * (q - mu * db);
+    d_gamma[k] = beta ? r * q : r * (q - stats[k] * db);
 }
 
 struct BnBwd {
@@ -335,28 +344,51 @@ extern "C" int acm_bnorm_stats(int64_t n_rows, int f, const float* H, int64_t ld
     return ACM_OK;
 }
 
-extern "C" int acm_bnorm_fold(int f_out, int f_in, const float* W, int64_t ldw, const float* bias, const float* stats, float* W_folded,
-                              int64_t ldwf, float* bias_folded, acm_stream_t stream) {
+static int bn_fold(int f_out, int f_in, const float* W, int64_t ldw, const float* bias, const float* beta, const float* stats,
+                   float* W_folded, int64_t ldwf, float* bias_folded, acm_stream_t stream) {
     ACM_REQUIRE(W && stats && W_folded && bias_folded, ACM_EINVAL, "acm_bnorm_fold: NULL argument");
     ACM_REQUIRE(f_in >= 1 && f_in <= 256 && f_out >= 1 && f_out <= 256, ACM_EUNSUPPORTED, "acm_bnorm_fold: %d x %d outside 1..256", f_out,
                 f_in);
     ACM_REQUIRE(ldw >= f_in && ldwf >= f_in, ACM_ESHAPE, "acm_bnorm_fold: leading dimension too small");
-    hipLaunchKernelGGL(bn_fold_kernel, dim3(f_out), dim3(256), 0, (hipStream_t)stream, f_in, W, (long)ldw, bias, stats, W_folded,
-                       (long)ldwf, bias_folded);
+    hipLaunchKernelGGL(bn_fold_kernel, dim3(f_out), dim3(256), 0, (hipStream_t)stream, f_in, W, (long)ldw, bias, beta, stats,
+                       W_folded, (long)ldwf, bias_folded);
+    ACM_CHECK_HIP(hipGetLastError());
+    return ACM_OK;
+}
+
+extern "C" int acm_bnorm_fold(int f_out, int f_in, const float* W, int64_t ldw, const float* bias, const float* stats, float* W_folded,
+                              int64_t ldwf, float* bias_folded, acm_stream_t stream) {
+    return bn_fold(f_out, f_in, W, ldw, bias, nullptr, stats, W_folded, ldwf, bias_folded, stream);
+}
+
+extern "C" int acm_bnorm_fold_centred(int f_out, int f_in, const float* W, int64_t ldw, const float* bias, const float* beta,
+                                      const float* stats, float* W_folded, int64_t ldwf, float* bias_folded, acm_stream_t stream) {
+    ACM_REQUIRE(beta, ACM_EINVAL, "acm_bnorm_fold_centred: NULL argument");
+    return bn_fold(f_out, f_in, W, ldw, bias, beta, stats, W_folded, ldwf, bias_folded, stream);
+}
+
+static int bn_param_bwd(int f_out, int f_in, const float* M, int64_t ldm, const float* s, const float* W, int64_t ldw, const float* beta,
+                        const float* stats, float* dW, int64_t lddw, float* d_beta, float* d_gamma, acm_stream_t stream) {
+    ACM_REQUIRE(M && s && W && stats && dW && d_beta && d_gamma, ACM_EINVAL, "acm_bnorm_param_bwd: NULL argument");
+    ACM_REQUIRE(f_in >= 1 && f_in <= 256 && f_out >= 1 && f_out <= 256, ACM_EUNSUPPORTED, "acm_bnorm_param_bwd: %d x %d outside 1..256",
+                f_out, f_in);
+    ACM_REQUIRE(ldm >= f_in && ldw >= f_in && lddw >= f_in, ACM_ESHAPE, "acm_bnorm_param_bwd: leading dimension too small");
+    hipLaunchKernelGGL(bn_param_bwd_kernel, dim3((f_in + 63) / 64), dim3(64), 0, (hipStream_t)stream, f_out, f_in, M, (long)ldm, s, W,
+                       (long)ldw, beta, stats, dW, (long)lddw, d_beta, d_gamma);
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
 }
 
 extern "C" int acm_bnorm_param_bwd(int f_out, int f_in, const float* M, int64_t ldm, const float* s, const float* W, int64_t ldw,
                                    const float* stats, float* dW, int64_t lddw, float* d_beta, float* d_gamma, acm_stream_t stream) {
-    ACM_REQUIRE(M && s && W && stats && dW && d_beta && d_gamma, ACM_EINVAL, "acm_bnorm_param_bwd: NULL argument");
-    ACM_REQUIRE(f_in >= 1 && f_in <= 256 && f_out >= 1 && f_out <= 256, ACM_EUNSUPPORTED, "acm_bnorm_param_bwd: %d x %d outside 1..256",
-                f_out, f_in);
-    ACM_REQUIRE(ldm >= f_in && ldw >= f_in && lddw >= f_in, ACM_ESHAPE, "acm_bnorm_param_bwd: leading dimension too small");
-    hipLaunchKernelGGL(bn_param_bwd_kernel, dim3((f_in + 63) / 64), dim3(64), 0, (hipStream_t)stream, f_out, f_in, M, (long)ldm, s, W,
-                       (long)ldw, stats, dW, (long)lddw, d_beta, d_gamma);
-    ACM_CHECK_HIP(hipGetLastError());
-    return ACM_OK;
+    return bn_param_bwd(f_out, f_in, M, ldm, s, W, ldw, nullptr, stats, dW, lddw, d_beta, d_gamma, stream);
+}
+
+extern "C" int acm_bnorm_param_bwd_centred(int f_out, int f_in, const float* M, int64_t ldm, const float* s, const float* W, int64_t ldw,
+                                           const float* beta, const float* stats, float* dW, int64_t lddw, float* d_beta, float* d_gamma,
+                                           acm_stream_t stream) {
+    ACM_REQUIRE(beta, ACM_EINVAL, "acm_bnorm_param_bwd_centred: NULL argument");
+    return bn_param_bwd(f_out, f_in, M, ldm, s, W, ldw, beta, stats, dW, lddw, d_beta, d_gamma, stream);
 }
 
 extern "C" int acm_bnorm_bwd_workspace_bytes(int64_t n_rows, int f, size_t* bytes) {

@@ -184,7 +184,7 @@ int acm_gemm_bx3_nn(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda
 bool acm_gemm_bx3_tn_ok(int64_t n_rows, int64_t K, int64_t N);
 int acm_gemm_bx3_tn_blocks(int64_t n_rows, int64_t K);
 int acm_gemm_bx3_tn(int64_t n_rows, int64_t K, int64_t N, const float* X, int64_t ldx, const float* Dz, int64_t lddz,
-                    float* slabs, int blocks, const acm_dropout_t* drop, hipStream_t st);
+                    float* slabs, int blocks, const acm_dropout_t* drop, hipStream_t st, const float* z_shift = nullptr);
 int acm_linear_fwd_narrow(int64_t n_rows, int64_t f_in, int64_t f_out, const float* X, int64_t ldx, const float* W, int64_t ldw,
                           const float* bias, int relu, const acm_dropout_t* drop, float* Y, int64_t ldy, hipStream_t s,
                           const float* add, int64_t ld_add);   // acm_linear.hip

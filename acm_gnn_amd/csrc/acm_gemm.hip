@@ -29,20 +29,25 @@ struct TileLds {
     }
 };
 
-// Global -> register staging of one BMN x BK tile.  `gmn`/`gk` strides are in elements.
+// Global -> register staging of one BMN x BK tile.  `gmn`/`gk` strides are in elements.  SHIFT: the operand is the stored
+// matrix minus 1 shift^T, shift[c] per STORED column c (k where the memory is contiguous along k, m/n otherwise), subtracted
+// here; the tile's zero padding stays zero.
 template <bool KMAJOR, int BMN>
 struct TileLoad {
     static constexpr int PER_THREAD = BMN * BK / 256;
     float r[PER_THREAD];
+    template <bool SHIFT = false>
     __device__ __forceinline__ void load(const float* __restrict__ base, long s_mn, long s_k, int mn0,
-                                         int mn_lim, int k0, int k_lim) {
+                                         int mn_lim, int k0, int k_lim, const float* __restrict__ shift = nullptr) {
 #pragma unroll
         for (int i = 0; i < PER_THREAD; ++i) {
             const int idx = threadIdx.x + i * 256;
             const int mn = KMAJOR ? idx / BK : idx % BMN;
             const int kk = KMAJOR ? idx % BK : idx / BMN;
             const int gmn = mn0 + mn, gk = k0 + kk;
-            r[i] = (gmn < mn_lim && gk < k_lim) ? base[(long)gmn * s_mn + (long)gk * s_k] : 0.f;
+            const bool in = gmn < mn_lim && gk < k_lim;
+            r[i] = in ? base[(long)gmn * s_mn + (long)gk * s_k] : 0.f;
+            if (SHIFT) r[i] = in ? r[i] - shift[KMAJOR ? gk : gmn] : 0.f;
         }
     }
     __device__ __forceinline__ void store(float* __restrict__ lds) const {
@@ -56,14 +61,14 @@ struct TileLoad {
     }
 };
 
-// C tile = op(A) op(B) over k in [k_begin, k_end) of split blockIdx.z.
-template <int WM, int WN, int WAVES_M, int WAVES_N, bool TA, bool TB>
+// C tile = op(A) op(B) over k in [k_begin, k_end) of split blockIdx.z.  SH = 1 / 2: A / B is read as (stored matrix - 1 shift^T).
+template <int WM, int WN, int WAVES_M, int WAVES_N, bool TA, bool TB, int SH = 0>
 __global__ __launch_bounds__(256) void gemm_kernel(int M, int N, int K, const float* __restrict__ A, long lda,
                                                    const float* __restrict__ B, long ldb,
                                                    float* __restrict__ C, long ldc, int relu, int k_per_split,
                                                    float* __restrict__ slabs, int cb, long cbs, int split,
                                                    float* __restrict__ C2, long ldc2, const float* __restrict__ bias,
-                                                   acm_dropout_t drop) {
+                                                   acm_dropout_t drop, const float* __restrict__ shift) {
     constexpr int BM = 16 * WM * WAVES_M, BN = 16 * WN * WAVES_N;
     constexpr bool A_KMAJOR = !TA, B_KMAJOR = TB;
     using LA = TileLds<A_KMAJOR, BM>;
@@ -90,16 +95,16 @@ __global__ __launch_bounds__(256) void gemm_kernel(int M, int N, int K, const fl
     TileLoad<A_KMAJOR, BM> ta;
     TileLoad<B_KMAJOR, BN> tb;
     if (k_begin < k_end) {
-        ta.load(A, a_sm, a_sk, m0, M, k_begin, k_end);
-        tb.load(B, b_sn, b_sk, n0, N, k_begin, k_end);
+        ta.template load<SH == 1>(A, a_sm, a_sk, m0, M, k_begin, k_end, shift);
+        tb.template load<SH == 2>(B, b_sn, b_sk, n0, N, k_begin, k_end, shift);
     }
     for (int k0 = k_begin; k0 < k_end; k0 += BK) {
         ta.store(As);
         tb.store(Bs);
         __syncthreads();
         if (k0 + BK < k_end) {  // prefetch the next slab while this one feeds the MFMAs
-            ta.load(A, a_sm, a_sk, m0, M, k0 + BK, k_end);
-            tb.load(B, b_sn, b_sk, n0, N, k0 + BK, k_end);
+            ta.template load<SH == 1>(A, a_sm, a_sk, m0, M, k0 + BK, k_end, shift);
+            tb.template load<SH == 2>(B, b_sn, b_sk, n0, N, k0 + BK, k_end, shift);
         }
 #pragma unroll
         for (int ks = 0; ks < BK / 4; ++ks) {
@@ -231,10 +236,22 @@ GemmPlan plan_gemm(int64_t M, int64_t N, int64_t K) {
 template <int WM, int WN, int WVM, int WVN>
 void launch_shape(int ta, int tb, const GemmPlan& p, hipStream_t st, int M, int N, int K, const float* A,
                   long lda, const float* B, long ldb, float* C, long ldc, int relu, float* slabs, int cb, long cbs,
-                  int split, float* C2, long ldc2, const float* bias, const acm_dropout_t& drop) {
+                  int split, float* C2, long ldc2, const float* bias, const acm_dropout_t& drop, const float* a_shift,
+                  const float* b_shift) {
+    // the two shifted products of a deep mlpX stack (gemm_core admits no other): (X - 1 mu^T) W^T and G^T (H - 1 mu^T)
+    if (a_shift) {
+        hipLaunchKernelGGL((gemm_kernel<WM, WN, WVM, WVN, false, true, 1>), p.grid, dim3(256), 0, st, M, N, K, A, lda, B, ldb, C,
+                           ldc, relu, p.k_per_split, slabs, cb, cbs, split, C2, ldc2, bias, drop, a_shift);
+        return;
+    }
+    if (b_shift) {
+        hipLaunchKernelGGL((gemm_kernel<WM, WN, WVM, WVN, true, false, 2>), p.grid, dim3(256), 0, st, M, N, K, A, lda, B, ldb, C,
+                           ldc, relu, p.k_per_split, slabs, cb, cbs, split, C2, ldc2, bias, drop, b_shift);
+        return;
+    }
     acm_pick([&](auto TA, auto TB) {
         hipLaunchKernelGGL((gemm_kernel<WM, WN, WVM, WVN, TA(), TB()>), p.grid, dim3(256), 0, st, M, N, K, A, lda, B, ldb, C,
-                           ldc, relu, p.k_per_split, slabs, cb, cbs, split, C2, ldc2, bias, drop);
+                           ldc, relu, p.k_per_split, slabs, cb, cbs, split, C2, ldc2, bias, drop, (const float*)nullptr);
         return ACM_OK;
     }, acm_flag(ta != 0), acm_flag(tb != 0));
 }
@@ -281,7 +298,8 @@ extern "C" int acm_gemm(int transA, int transB, int64_t M, int64_t N, int64_t K,
 static int gemm_core(int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
                      int64_t ldb, float* C, int64_t ldc, int64_t c_col_block, int64_t c_block_stride, int64_t split_col,
                      float* C2, int64_t ldc2, int relu, void* workspace, size_t workspace_bytes, acm_stream_t stream,
-                     const float* bias = nullptr, const acm_dropout_t* drop = nullptr, const acm_dropout_t* a_drop = nullptr);
+                     const float* bias = nullptr, const acm_dropout_t* drop = nullptr, const acm_dropout_t* a_drop = nullptr,
+                     const float* a_shift = nullptr, const float* b_shift = nullptr);
 
 // op(A) with the counter-based dropout applied to the STORED matrix A while its tiles are staged (element [r][c] of A as it
 // lies in memory: the node-feature matrix X, whichever side of the product it is on):
@@ -309,6 +327,27 @@ extern "C" int acm_linear_fwd(int64_t n_rows, int64_t f_in, int64_t f_out, const
     }
     return gemm_core(0, 1, n_rows, f_out, f_in, X, ldx, W, ldw, Y, ldy, 0, 0, 0, nullptr, 0, relu, workspace, workspace_bytes,
                      stream, bias, drop);
+}
+
+// The same with X read as X - 1 x_shift^T (x_shift: f_in floats, subtracted where the tiles of X are staged): the Linear behind a
+// BatchNorm of a deep mlpX stack on the CENTRED activations (acm_bnorm_fold).  Always the tile kernel.
+extern "C" int acm_linear_fwd_shift(int64_t n_rows, int64_t f_in, int64_t f_out, const float* X, int64_t ldx, const float* x_shift,
+                                    const float* W, int64_t ldw, const float* bias, int relu, const acm_dropout_t* drop, float* Y,
+                                    int64_t ldy, void* workspace, size_t workspace_bytes, acm_stream_t stream) {
+    ACM_REQUIRE(X && W && Y && x_shift, ACM_EINVAL, "acm_linear_fwd_shift: NULL argument");
+    ACM_REQUIRE(f_in > 0, ACM_ESHAPE, "acm_linear_fwd_shift: f_in must be positive");
+    return gemm_core(0, 1, n_rows, f_out, f_in, X, ldx, W, ldw, Y, ldy, 0, 0, 0, nullptr, 0, relu, workspace, workspace_bytes,
+                     stream, bias, drop, nullptr, x_shift, nullptr);
+}
+
+// C = op(A) op(B - 1 b_shift^T), b_shift[c] per stored column c of B: M_c = G^T (H - 1 mu^T) of the same stack's backward
+// (transA = 1, transB = 0; ACM_EUNSUPPORTED otherwise).  Workspace: acm_gemm_workspace_bytes of the same product.
+extern "C" int acm_gemm_shift(int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
+                              int64_t ldb, const float* b_shift, float* C, int64_t ldc, void* workspace, size_t workspace_bytes,
+                              acm_stream_t stream) {
+    ACM_REQUIRE(b_shift, ACM_EINVAL, "acm_gemm_shift: NULL argument");
+    return gemm_core(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, 0, 0, 0, nullptr, 0, 0, workspace, workspace_bytes, stream,
+                     nullptr, nullptr, nullptr, nullptr, b_shift);
 }
 
 // Y = dropout(relu?(X W)), W stored [f_in, f_out]: the same epilogue on the untransposed product (the baselines' first layer on
@@ -353,7 +392,8 @@ extern "C" int acm_gemm_split(int transA, int transB, int64_t M, int64_t N, int6
 static int gemm_core(int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
                      int64_t ldb, float* C, int64_t ldc, int64_t c_col_block, int64_t c_block_stride, int64_t split_col,
                      float* C2, int64_t ldc2, int relu, void* workspace, size_t workspace_bytes, acm_stream_t stream,
-                     const float* bias, const acm_dropout_t* drop_in, const acm_dropout_t* a_drop) {
+                     const float* bias, const acm_dropout_t* drop_in, const acm_dropout_t* a_drop, const float* a_shift,
+                     const float* b_shift) {
     acm_dropout_t drop = {0.f, 0, 0, nullptr, 0};
     if (drop_in) drop = *drop_in;
     ACM_REQUIRE(drop.p == 0.f || (drop.p > 0.f && drop.p < 1.f && drop.step), ACM_EINVAL, "acm_gemm: bad dropout spec");
@@ -370,6 +410,10 @@ static int gemm_core(int transA, int transB, int64_t M, int64_t N, int64_t K, co
                 "acm_gemm: leading dimension too small (lda %lld ldb %lld ldc %lld)", (long long)lda,
                 (long long)ldb, (long long)ldc);
     hipStream_t st = (hipStream_t)stream;
+    // a shifted operand: only the two products a deep mlpX stack forms, and only in the forms that subtract while they stage
+    ACM_REQUIRE(!a_shift || (!transA && transB && !b_shift && !a_drop), ACM_EUNSUPPORTED, "acm_linear_fwd_shift: the shifted input exists for X W^T only");
+    ACM_REQUIRE(!b_shift || (transA && !transB && !a_drop && !cb && !split), ACM_EUNSUPPORTED,
+                "acm_gemm_shift: the shifted operand exists for A^T (B - 1 shift^T) only");
     ACM_REQUIRE(!a_drop || (a_drop->p > 0.f && a_drop->p < 1.f && a_drop->step), ACM_EINVAL, "acm_gemm_drop: bad dropout spec");
     // row-panel forms (acm_gemm_rows.hip): A = the tall node-feature matrix, read exactly once
     const bool plain_out = !split && !bias && drop.p == 0.f;
@@ -384,11 +428,12 @@ static int gemm_core(int transA, int transB, int64_t M, int64_t N, int64_t K, co
         return acm_gemm_rows_nn(M, N, K, A, lda, B, ldb, C, ldc, relu, a_drop, st);
     const TnPanel tp = (transA && !transB && plain_out) ? tn_panel(M, N, K) : TnPanel{0, 0};
     const bool bx3_tn = tp.bx3_blocks > 0;
-    if (bx3_tn || (tp.rows_blocks > 0 && (a_drop || K >= 100000 || (acm_tuning().gemm_forms & ACM_GEMM_ROWS_ALWAYS)))) {
+    // (the fp32 row-panel form has no shifted load: a shifted product it would take goes to the tile kernel below)
+    if (bx3_tn || (!b_shift && tp.rows_blocks > 0 && (a_drop || K >= 100000 || (acm_tuning().gemm_forms & ACM_GEMM_ROWS_ALWAYS)))) {
         const int blocks = bx3_tn ? tp.bx3_blocks : tp.rows_blocks;
         const size_t need = (size_t)blocks * (size_t)M * (size_t)N * sizeof(float);
         ACM_REQUIRE(workspace && workspace_bytes >= need, ACM_ENOMEM, "acm_gemm: workspace %zu B < required %zu B", workspace_bytes, need);
-        int rc = bx3_tn ? acm_gemm_bx3_tn(K, M, N, A, lda, B, ldb, (float*)workspace, blocks, a_drop, st)
+        int rc = bx3_tn ? acm_gemm_bx3_tn(K, M, N, A, lda, B, ldb, (float*)workspace, blocks, a_drop, st, b_shift)
                         : acm_gemm_rows_tn(K, M, N, A, lda, B, ldb, (float*)workspace, blocks, a_drop, st);
         if (rc != ACM_OK) return rc;
         const long total = (long)M * N;
@@ -423,11 +468,11 @@ static int gemm_core(int transA, int transB, int64_t M, int64_t N, int64_t K, co
         return ACM_OK;
     }
     if (p.shape == 0)
-        launch_shape<2, 2, 2, 2>(transA, transB, p, st, (int)M, (int)N, (int)K, A, lda, B, ldb, C, ldc, relu, slabs, cb, cbs, split, C2, (long)ldc2, bias, drop);
+        launch_shape<2, 2, 2, 2>(transA, transB, p, st, (int)M, (int)N, (int)K, A, lda, B, ldb, C, ldc, relu, slabs, cb, cbs, split, C2, (long)ldc2, bias, drop, a_shift, b_shift);
     else if (p.shape == 1)
-        launch_shape<1, 4, 1, 4>(transA, transB, p, st, (int)M, (int)N, (int)K, A, lda, B, ldb, C, ldc, relu, slabs, cb, cbs, split, C2, (long)ldc2, bias, drop);
+        launch_shape<1, 4, 1, 4>(transA, transB, p, st, (int)M, (int)N, (int)K, A, lda, B, ldb, C, ldc, relu, slabs, cb, cbs, split, C2, (long)ldc2, bias, drop, a_shift, b_shift);
     else
-        launch_shape<4, 1, 4, 1>(transA, transB, p, st, (int)M, (int)N, (int)K, A, lda, B, ldb, C, ldc, relu, slabs, cb, cbs, split, C2, (long)ldc2, bias, drop);
+        launch_shape<4, 1, 4, 1>(transA, transB, p, st, (int)M, (int)N, (int)K, A, lda, B, ldb, C, ldc, relu, slabs, cb, cbs, split, C2, (long)ldc2, bias, drop, a_shift, b_shift);
     ACM_CHECK_HIP(hipGetLastError());
     if (slabs) {
         const long total = (long)M * N;

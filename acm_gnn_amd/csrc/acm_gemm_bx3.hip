@@ -225,10 +225,12 @@ constexpr int TS = 20;                     // dwords per column in LDS
 // Workgroup barrier that orders LDS traffic only: __syncthreads() also drains the global loads in flight (s_waitcnt vmcnt(0)),
 // i.e. the next slab's rows requested a phase ahead -- every phase would last a full memory latency.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-template <int NT>
+// SHIFT: dZ is read as dZ - 1 z_shift^T (z_shift[c] per column c < N), subtracted in fp32 before the split: the centred
+// activations of a deep mlpX stack (acm_gemm_shift).  Rows past the end of X are zero in X, so what they hold in dZ is immaterial.
+template <int NT, bool SHIFT>
 __global__ __launch_bounds__(512, 2) void gemm_bx3_tn_kernel(int n_rows, int Ktot, int N, const float* __restrict__ Xall, long ldx,
                                                              const float* __restrict__ Dz, long lddz, float* __restrict__ slabs,
-                                                             int rows_per_block, acm_dropout_t drop) {
+                                                             int rows_per_block, acm_dropout_t drop, const float* __restrict__ z_shift) {
     extern __shared__ __attribute__((aligned(16))) unsigned Tl[];    // [group 2][part 3][128 + 16 NT columns][TS]
     constexpr int COLS = 128 + 16 * NT, BUF = 3 * COLS * TS, ZT = (64 * NT + 255) / 256;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, m = lane & 15, g = lane >> 4;
@@ -257,6 +259,12 @@ __global__ __launch_bounds__(512, 2) void gemm_bx3_tn_kernel(int n_rows, int Kto
         const int t = tid + 256 * u, zc = t % (16 * NT), zrg = t / (16 * NT);
         zok[u] = zrg < 4 && zc < N;
         zoff[u] = (unsigned)(8 * (zok[u] ? zrg : 0)) * (unsigned)lddz + (unsigned)(zok[u] ? zc : 0);
+    }
+    float zsh[ZT];
+#pragma unroll
+    for (int u = 0; u < ZT; ++u) {
+        const int zc = (tid + 256 * u) % (16 * NT);
+        zsh[u] = (SHIFT && zok[u]) ? z_shift[zc] : 0.f;
     }
     auto fetch = [&](int r0) {
         if (r0 + 32 <= r_end) {                    // whole slab: no row guards, uniform row bases + the lane's 32-bit offset
@@ -326,7 +334,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bx3_tn_kernel(int n_rows, int Kto
         for (int u = 0; u < ZT; ++u) {
             const int t = tid + 256 * u, zc = t % (16 * NT), zrg = t / (16 * NT);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) zv[u][e] = zok[u] ? zv[u][e] : 0.f;
+            for (int e = 0; e < 8; ++e) zv[u][e] = zok[u] ? (SHIFT ? zv[u][e] - zsh[u] : zv[u][e]) : 0.f;
             split3(zv[u], hi, md, lo);
             if (zrg < 4) {
                 *reinterpret_cast<u32x4*>(T + (0 * COLS + 128 + zc) * TS + 4 * zrg) = hi;
@@ -463,7 +471,7 @@ int acm_gemm_bx3_tn_blocks(int64_t n_rows, int64_t K) {
 
 // slabs: blocks x K x N floats; the caller reduces them (splitk_reduce_kernel of acm_gemm.hip)
 int acm_gemm_bx3_tn(int64_t n_rows, int64_t K, int64_t N, const float* X, int64_t ldx, const float* Dz, int64_t lddz,
-                    float* slabs, int blocks, const acm_dropout_t* drop_in, hipStream_t st) {
+                    float* slabs, int blocks, const acm_dropout_t* drop_in, hipStream_t st, const float* z_shift) {
     acm_dropout_t drop = {0.f, 0, 0, nullptr, 0, 0};
     if (drop_in) drop = *drop_in;
     const int nt = (int)((N + 15) / 16);
@@ -471,12 +479,12 @@ int acm_gemm_bx3_tn(int64_t n_rows, int64_t K, int64_t N, const float* X, int64_
     int64_t rpb = (n_rows + blocks - 1) / blocks;
     rpb = (rpb + 31) / 32 * 32;
     const size_t lds = (size_t)2 * 3 * (128 + 16 * ntr) * 20 * sizeof(unsigned);
-    const int rc = acm_pick([&](auto NT) {
-        ACM_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bx3_tn_kernel<NT()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((gemm_bx3_tn_kernel<NT()>), dim3(blocks, (unsigned)((K + 127) / 128)), dim3(512), lds, st, (int)n_rows, (int)K, (int)N, X,
-                           (long)ldx, Dz, (long)lddz, slabs, (int)rpb, drop);
+    const int rc = acm_pick([&](auto NT, auto SH) {
+        ACM_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bx3_tn_kernel<NT(), SH()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((gemm_bx3_tn_kernel<NT(), SH()>), dim3(blocks, (unsigned)((K + 127) / 128)), dim3(512), lds, st, (int)n_rows, (int)K,
+                           (int)N, X, (long)ldx, Dz, (long)lddz, slabs, (int)rpb, drop, z_shift);
         return ACM_OK;
-    }, acm_one_of<2, 4, 8, 12>(ntr));
+    }, acm_one_of<2, 4, 8, 12>(ntr), acm_flag(z_shift != nullptr));
     ACM_REQUIRE(rc != ACM_NO_INSTANTIATION, ACM_EUNSUPPORTED, "acm_gemm_bx3_tn: no kernel for %d column tiles", nt);
     if (rc != ACM_OK) return rc;
     ACM_CHECK_HIP(hipGetLastError());

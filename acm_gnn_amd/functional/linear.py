@@ -2,7 +2,7 @@
 kernels, alone or added to the hidden activations in the same launch."""
 import torch
 
-from .. import tuning
+from .. import _lib, tuning
 from ..graph import SparseFeatures
 from ._context import _call_or_ambient, _run, _sum_over_ranks
 from ._launch import _F32, _as_f32_rows, _as_f32c, _ref, _vp, _workspace_sized, launch
@@ -171,14 +171,19 @@ class _StackMeta:
         self.n_lins, self.relu, self.drop, self.call, self.buffers = n_lins, relu, drop, call, buffers
 
 
-def _linear_into(x, w, b, relu, spec):
-    """dropout(relu?(x W^T + b)) of a dense x (leading w.shape[1] columns) or SparseFeatures: the forward of _ResidualLinear."""
+def _linear_into(x, w, b, relu, spec, shift=None):
+    """dropout(relu?(x W^T + b)) of a dense x (leading w.shape[1] columns) or SparseFeatures: the forward of _ResidualLinear.
+    ``shift`` (dense x): x is read as x - 1 shift^T (acm_linear_fwd_shift)."""
     f_out, f_in = w.shape
     n, dev = x.shape[0], w.device
     y = torch.empty(n, f_out, dtype=_F32, device=dev)
     if isinstance(x, SparseFeatures):
         spmm_v(x.csr, x.values, w.t().contiguous(), out=y)
         launch("acm_bias_act", f"bias_act/{n}x{f_out}", dev, n, f_out, _vp(y), y.stride(0), _vp(b), int(relu), _ref(spec))
+    elif shift is not None:
+        ws, nbytes = _gemm_workspace(dev, 0, 1, n, f_out, f_in)
+        launch("acm_linear_fwd_shift", f"linear_fwd/{n}x{f_out}x{f_in}", dev, n, f_in, f_out, _vp(x), x.stride(0), _vp(shift), _vp(w),
+               w.stride(0), _vp(b), int(relu), _ref(spec), _vp(y), y.stride(0), _vp(ws), nbytes)
     else:
         ws, nbytes = _gemm_workspace(dev, 0, 1, n, f_out, f_in)
         launch("acm_linear_fwd", f"linear_fwd/{n}x{f_out}x{f_in}", dev, n, f_in, f_out, _vp(x), x.stride(0), _vp(w), w.stride(0), _vp(b),
@@ -186,9 +191,17 @@ def _linear_into(x, w, b, relu, spec):
     return y
 
 
-def _bnorm_fold(h, gamma, beta, buf, train, w_next, b_next):
-    """(stats [4, f] = mu | r | a | c of BatchNorm(h), W' = W_next diag(a), b' = b_next + W_next c): acm_bnorm_stats (which also
-    updates the running buffers when ``train``) + acm_bnorm_fold."""
+def _stack_centred():
+    """Whether the library has the centred form of the stack (_lib.BNORM_CENTRED_SYMBOLS: the real one does).  A library or a
+    test double without them gets the stack's first form: both products on H itself, c = beta - mu a folded into the bias."""
+    lib = _lib.load()
+    return all(getattr(lib, name, None) is not None for name in _lib.BNORM_CENTRED_SYMBOLS)
+
+
+def _bnorm_fold(h, gamma, beta, buf, train, w_next, b_next, centred):
+    """(stats [4, f] = mu | r | a | c of BatchNorm(h), W' = W_next diag(a), b'): acm_bnorm_stats (which also updates the running
+    buffers when ``train``) + the fold.  ``centred``: b' = b_next + W_next beta (acm_bnorm_fold_centred), for a Linear that reads
+    h - 1 mu^T; otherwise b' = b_next + W_next c (acm_bnorm_fold), for one that reads h."""
     n, f = h.shape
     dev = h.device
     rm, rv, nbt, eps, momentum = buf
@@ -199,14 +212,19 @@ def _bnorm_fold(h, gamma, beta, buf, train, w_next, b_next):
     f_out = w_next.shape[0]
     wf = torch.empty(f_out, f, dtype=_F32, device=dev)
     bf = torch.empty(f_out, dtype=_F32, device=dev)
-    launch("acm_bnorm_fold", f"bnorm_fold/{f_out}x{f}", dev, f_out, f, _vp(w_next), w_next.stride(0), _vp(b_next), _vp(stats), _vp(wf),
-           wf.stride(0), _vp(bf))
+    if centred:
+        launch("acm_bnorm_fold_centred", f"bnorm_fold/{f_out}x{f}", dev, f_out, f, _vp(w_next), w_next.stride(0), _vp(b_next), _vp(beta),
+               _vp(stats), _vp(wf), wf.stride(0), _vp(bf))
+    else:
+        launch("acm_bnorm_fold", f"bnorm_fold/{f_out}x{f}", dev, f_out, f, _vp(w_next), w_next.stride(0), _vp(b_next), _vp(stats), _vp(wf),
+               wf.stride(0), _vp(bf))
     return stats, wf, bf
 
 
-def _stack_forward(x, lin_params, bn_params, buffers, train, relu, spec):
+def _stack_forward(x, lin_params, bn_params, buffers, train, relu, spec, centred):
     """The stack's forward: H_0 = relu(x W_0^T + b_0), then per BatchNorm its statistics folded into the next Linear, which reads
-    H_i itself.  Returns (y, [H_0 .. H_{L-2}], [stats_0 .. stats_{L-2}])."""
+    H_i - 1 mu_i^T (the mean subtracted where its product stages H_i; ``centred`` False: H_i itself).  Returns
+    (y, [H_0 .. H_{L-2}], [stats_0 .. stats_{L-2}])."""
     n_lins = len(lin_params)
     w0, b0 = lin_params[0]
     h = _linear_into(x, w0, b0, True, None)
@@ -214,11 +232,11 @@ def _stack_forward(x, lin_params, bn_params, buffers, train, relu, spec):
     for i in range(n_lins - 1):
         gamma, beta = bn_params[i]
         w, b = lin_params[i + 1]
-        st, wf, bf = _bnorm_fold(h, gamma, beta, buffers[i], train, w, b)
+        st, wf, bf = _bnorm_fold(h, gamma, beta, buffers[i], train, w, b, centred)
         hs.append(h)
         stats.append(st)
         last = i + 1 == n_lins - 1
-        h = _linear_into(h, wf, bf, relu if last else True, spec if last else None)
+        h = _linear_into(h, wf, bf, relu if last else True, spec if last else None, shift=st[0] if centred else None)
     return h, hs, stats
 
 
@@ -226,9 +244,9 @@ class _MlpStack(torch.autograd.Function):
     """y = dropout(relu?(mlp(x))) for mlp = L >= 2 Linears with ReLU -> BatchNorm1d between them, in TRAINING mode
     (ACM-Pytorch/models/layers.py:279-284, models.py:150-152).  Arguments: x, a _StackMeta, then W_0, b_0, ..., W_{L-1}, b_{L-1},
     gamma_0, beta_0, ..., gamma_{L-2}, beta_{L-2}.  The normalised activations are never written: forward =
-    per layer acm_bnorm_stats + acm_bnorm_fold + acm_linear_fwd on the ReLU output; backward = per layer one acm_gemm(transA) for
-    M = G^T H, acm_bnorm_param_bwd (dW, d_beta, d_gamma from f x f matrices), one acm_gemm for dZ = G W and the row-local
-    acm_bnorm_bwd.  Only the first Linear's bias gradient honours the call's deferral list: every other column sum is read
+    per layer acm_bnorm_stats + acm_bnorm_fold_centred + acm_linear_fwd_shift on the centred ReLU output; backward = per layer one
+    acm_gemm_shift(transA) for M_c = G^T (H - 1 mu^T), acm_bnorm_param_bwd_centred (dW, d_beta, d_gamma from f x f matrices), one
+    acm_gemm for dZ = G W and the row-local acm_bnorm_bwd (``_stack_centred`` False: the uncentred entry points on H itself).  Only the first Linear's bias gradient honours the call's deferral list: every other column sum is read
     by the next acm_bnorm_param_bwd at once."""
 
     @staticmethod
@@ -248,11 +266,12 @@ class _MlpStack(torch.autograd.Function):
             raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
         drop = meta.drop
         spec = _drop_spec(drop[:3], drop[3]) if drop is not None else None
-        y, hs, stats = _stack_forward(x, lin_params, bn_params, meta.buffers, True, meta.relu, spec)
+        ctx.centred = _stack_centred()
+        y, hs, stats = _stack_forward(x, lin_params, bn_params, meta.buffers, True, meta.relu, spec, ctx.centred)
         ctx.n_lins, ctx.relu = n_lins, bool(meta.relu)
         ctx.keep_scale = 1.0 / (1.0 - drop[0]) if (drop is not None and drop[0] > 0) else 1.0
         ctx.sparse_x = x if sparse_x else None
-        ctx.save_for_backward(*([] if sparse_x else [x]), y, *hs, *stats, *[w for w, _ in lin_params])
+        ctx.save_for_backward(*([] if sparse_x else [x]), y, *hs, *stats, *[w for w, _ in lin_params], *[bt for _, bt in bn_params])
         return y
 
     @staticmethod
@@ -261,7 +280,8 @@ class _MlpStack(torch.autograd.Function):
         saved = list(ctx.saved_tensors)
         x = saved.pop(0) if ctx.sparse_x is None else None
         y = saved.pop(0)
-        hs, stats, ws_ = saved[:n_lins - 1], saved[n_lins - 1:2 * (n_lins - 1)], saved[2 * (n_lins - 1):]
+        hs, stats, ws_ = saved[:n_lins - 1], saved[n_lins - 1:2 * (n_lins - 1)], saved[2 * (n_lins - 1):3 * n_lins - 2]
+        betas = saved[3 * n_lins - 2:]
         dy = _as_f32_rows(dy, "grad")
         n, dev = y.shape[0], y.device
         d_w, d_b, d_gamma, d_beta = [None] * n_lins, [None] * n_lins, [None] * (n_lins - 1), [None] * (n_lins - 1)
@@ -283,11 +303,11 @@ class _MlpStack(torch.autograd.Function):
         for i in range(n_lins - 2, -1, -1):
             h, st, w = hs[i], stats[i], ws_[i + 1]
             f = h.shape[1]
-            m = gemm(g, h, trans_a=True)                                     # [f_{i+1}, f_i]
+            m = gemm(g, h, trans_a=True, b_shift=st[0] if ctx.centred else None)     # M_c = G^T (H - 1 mu^T): [f_{i+1}, f_i]
             d_w[i + 1] = torch.empty_like(w)
             d_beta[i], d_gamma[i] = torch.empty(f, dtype=_F32, device=dev), torch.empty(f, dtype=_F32, device=dev)
-            launch("acm_bnorm_param_bwd", f"bnorm_param_bwd/{w.shape[0]}x{f}", dev, w.shape[0], f, _vp(m), m.stride(0), _vp(d_b[i + 1]), _vp(w),
-                   w.stride(0), _vp(st), _vp(d_w[i + 1]), d_w[i + 1].stride(0), _vp(d_beta[i]), _vp(d_gamma[i]))
+            launch("acm_bnorm_param_bwd_centred" if ctx.centred else "acm_bnorm_param_bwd", f"bnorm_param_bwd/{w.shape[0]}x{f}", dev, w.shape[0],
+                   f, _vp(m), m.stride(0), _vp(d_b[i + 1]), _vp(w), w.stride(0), *([_vp(betas[i])] if ctx.centred else []), _vp(st), _vp(d_w[i + 1]), d_w[i + 1].stride(0), _vp(d_beta[i]), _vp(d_gamma[i]))
             dz = gemm(g, w)                                                  # [n, f_i]; becomes G_i in place
             if i == 0:
                 f_in = ws_[0].shape[1]
@@ -382,7 +402,7 @@ def residual_mlp(x, mlp, relu=True, drop=None, call=None):
             spec = _drop_spec(drop[:3], drop[3]) if drop is not None else None
             lp = [(_as_f32c(lin.weight, "weight"), _as_f32c(lin.bias, "bias")) for lin in lins]
             bp = [(_as_f32c(bn.weight, "weight"), _as_f32c(bn.bias, "bias")) for bn in bns]
-            return _stack_forward(x, lp, bp, buffers, False, bool(relu), spec)[0]
+            return _stack_forward(x, lp, bp, buffers, False, bool(relu), spec, _stack_centred())[0]
     params = [t for lin in lins for t in (lin.weight, lin.bias)] + [t for bn in bns for t in (bn.weight, bn.bias)]
     meta = _StackMeta(len(lins), bool(relu), drop, _call_or_ambient(call), buffers)
     return _run(_MlpStack, x, meta, *params)

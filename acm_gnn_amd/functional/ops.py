@@ -18,10 +18,11 @@ def gemm_drop_supported(n_rows, f_in, n_out):
             and (tuning.gemm_forms() & (tuning.GEMM_ROWS | tuning.GEMM_ROWS_ALWAYS)) != 0)
 
 
-def gemm(a, b, trans_a=False, trans_b=False, relu=False, out=None, col_blocks=0, a_drop=None):
+def gemm(a, b, trans_a=False, trans_b=False, relu=False, out=None, col_blocks=0, a_drop=None, b_shift=None):
     """out = op(a) @ op(b) on the fp32 MFMA pipe (acm_gemm).  ``col_blocks=j`` returns the product as a
     contiguous [j, m, n / j] tensor of column blocks (acm_gemm_blocks).  ``a_drop``: an acm_dropout_t applied to the stored
-    matrix ``a`` while its tiles are staged (acm_gemm_drop; see gemm_drop_supported)."""
+    matrix ``a`` while its tiles are staged (acm_gemm_drop; see gemm_drop_supported).  ``b_shift``: one float per column of the
+    stored ``b``, subtracted while ITS tiles are staged (acm_gemm_shift: a^T (b - 1 shift^T) only)."""
     a, b = _as_f32_rows(a, "a"), _as_f32_rows(b, "b")          # column slices of wider matrices: (pointer, ld), no copy
     m, k = (a.shape[1], a.shape[0]) if trans_a else (a.shape[0], a.shape[1])
     k2, n = (b.shape[1], b.shape[0]) if trans_b else (b.shape[0], b.shape[1])
@@ -41,7 +42,14 @@ def gemm(a, b, trans_a=False, trans_b=False, relu=False, out=None, col_blocks=0,
     ws, nbytes = _gemm_workspace(a.device, trans_a, trans_b, m, n, k)
     label = f"gemm_{'T' if trans_a else 'N'}{'T' if trans_b else 'N'}/{m}x{n}x{k}"
     head = (int(trans_a), int(trans_b), m, n, k, _vp(a), a.stride(0), _vp(b), b.stride(0), _vp(out))
-    if a_drop is not None:
+    if b_shift is not None:
+        if a_drop is not None or col_blocks or relu:
+            raise ValueError("gemm: b_shift goes with a plain product only")
+        b_shift = _as_f32c(b_shift, "b_shift")
+        if b_shift.numel() != b.shape[1]:
+            raise ValueError(f"gemm: b_shift has {b_shift.numel()} entries for {b.shape[1]} columns")
+        launch("acm_gemm_shift", label, a.device, *head[:9], _vp(b_shift), _vp(out), ld[0], _vp(ws), nbytes)
+    elif a_drop is not None:
         launch("acm_gemm_drop", label, a.device, *head, *ld, int(relu), C.byref(a_drop), _vp(ws), nbytes)
     elif col_blocks:
         launch("acm_gemm_blocks", label, a.device, *head, *ld, int(relu), _vp(ws), nbytes)

@@ -1446,11 +1446,17 @@ typedef struct {
 
 int acm_copy_if(int32_t n_tensors, const acm_copy_tensor_t* tensors, const int32_t* flag, acm_stream_t stream);
 
-/* ------------------------------------------------ BatchNorm1d inside a deep mlpX stack (ABI 29) --
+/* ------------------------------------------------ BatchNorm1d inside a deep mlpX stack (ABI 29; the centred pair: new symbols, same number) --
  * ACM-GCN++ with --link_init_layers_X k > 1 (ACM-Pytorch/models/models.py:37-41,150-152): mlpX is k Linears with
  *     x = lin(x); x = F.relu(x); x = self.bns[i](x); x = F.dropout(x, p=0)        (ACM-Pytorch/models/layers.py:279-284)
- * between them.  With H = relu(lin(x)) [n_rows, f] the BatchNorm is Z = a * H + c per column, a = gamma r, c = beta - mu a,
- * r = 1 / sqrt(var + eps); Z is never written: the NEXT Linear takes H with W' = W diag(a), b' = b + W c.  f <= 256 throughout.
+ * between them.  With H = relu(lin(x)) [n_rows, f] the BatchNorm is Z = a * (H - mu) + beta per column, a = gamma r,
+ * r = 1 / sqrt(var + eps); Z is never written: the NEXT Linear takes H - 1 mu^T (subtracted where its product stages H:
+ * acm_linear_fwd_shift) with W' = W diag(a), b' = b + W beta.  f <= 256 throughout.  Both products of the pair read the CENTRED
+ * activations.  The first form of the stack, kept under its names (acm_bnorm_fold, acm_bnorm_param_bwd), reads H itself with
+ * c = beta - mu a folded into the bias and into dW: on a column whose mean is far above its spread -- a unit whose bias has
+ * grown until it is always on -- a * H + c, M a + s c and q - mu d_beta cancel the leading digits of their terms, 2^-24
+ * mean / spread relative to the result.  Use the centred four (acm_bnorm_fold_centred, acm_linear_fwd_shift, acm_gemm_shift,
+ * acm_bnorm_param_bwd_centred) together, or the uncentred two with acm_linear_fwd and acm_gemm: never a mixture.
  *
  * acm_bnorm_stats  replaces nn.BatchNorm1d's statistics (layers.py:282; torch.nn.functional.batch_norm): stats = [4][f] =
  *                  mu | r | a | c.  train != 0: mu and the biased variance of the n_rows >= 2 rows of H, per-block
@@ -1459,12 +1465,22 @@ int acm_copy_if(int32_t n_tensors, const acm_copy_tensor_t* tensors, const int32
  *                  int64 *num_batches (any of the three may be NULL).  train == 0: mu / var are the running buffers, H is
  *                  not read and nothing but `stats` is written.  Deterministic.  Workspace (train): acm_bnorm_stats_workspace_bytes,
  *                  16-byte aligned, no initialisation.
- * acm_bnorm_fold   W_folded = W diag(a) ([f_out, f_in], nn.Linear's layout), bias_folded = bias + W c (bias NULL: zero) --
- *                  what makes lin(bn(H)) (layers.py:280,282) one acm_linear_fwd on H.
- * acm_bnorm_param_bwd  the BatchNorm's and the following Linear's parameter gradients from M = G^T H ([f_out, f_in]) and
- *                  s = colsum(G) (= that Linear's d_bias), G = dL/d(its pre-activation):
- *                      dW = M diag(a) + s c^T     d_beta[k] = sum_o s[o] W[o, k]     d_gamma[k] = r[k] (sum_o W[o, k] M[o, k] - mu[k] d_beta[k])
+ * acm_bnorm_fold_centred  W_folded = W diag(a) ([f_out, f_in], nn.Linear's layout), bias_folded = bias + W beta (bias NULL:
+ *                  zero; beta: the BatchNorm's own f_in floats, not rebuilt from c) -- what makes lin(bn(H)) (layers.py:280,282)
+ *                  one acm_linear_fwd_shift on H with x_shift = mu (stats row 0).
+ * acm_bnorm_fold   the uncentred form: the same W_folded, bias_folded = bias + W c, for acm_linear_fwd on H itself.
+ * acm_linear_fwd_shift  acm_linear_fwd with X read as X - 1 x_shift^T (x_shift: f_in floats), the subtraction in fp32 where
+ *                  the tiles of X are staged; nothing of size n_rows is written beside Y.  Workspace as acm_linear_fwd.
+ * acm_gemm_shift   C = A^T (B - 1 b_shift^T) (transA = 1, transB = 0; b_shift: N floats, one per column of B): the matrix
+ *                  M_c = G^T (H - 1 mu^T) of the backward.  Taken by the forms of acm_gemm that can subtract in their load (the
+ *                  tile kernel, the bf16-split row-panel form); any other transposition: ACM_EUNSUPPORTED.  Workspace:
+ *                  acm_gemm_workspace_bytes(1, 0, M, N, K).
+ * acm_bnorm_param_bwd_centred  the BatchNorm's and the following Linear's parameter gradients from M_c = G^T (H - 1 mu^T)
+ *                  ([f_out, f_in]) and s = colsum(G) (= that Linear's d_bias), G = dL/d(its pre-activation):
+ *                      dW = M_c diag(a) + s beta^T     d_beta[k] = sum_o s[o] W[o, k]     d_gamma[k] = r[k] sum_o W[o, k] M_c[o, k]
  *                  -- no pass over the rows (replaces the BatchNorm / Linear backward nodes of layers.py:280-282).
+ * acm_bnorm_param_bwd  the uncentred form, from M = G^T H (acm_gemm):
+ *                      dW = M diag(a) + s c^T     d_beta as above     d_gamma[k] = r[k] (sum_o W[o, k] M[o, k] - mu[k] d_beta[k])
  * acm_bnorm_bwd    the row-local pass of that backward: with dZ = G W,
  *                      G_prev = [H > 0] a (dZ - d_beta / n - (H - mu) r d_gamma / n)
  *                  (BatchNorm and ReLU backward of layers.py:281-282 in one pass) and d_bias = colsum(G_prev), the previous
@@ -1480,8 +1496,19 @@ int acm_bnorm_stats(int64_t n_rows, int f, const float* H, int64_t ldh, const fl
                     float* stats, void* workspace, size_t workspace_bytes, acm_stream_t stream);
 int acm_bnorm_fold(int f_out, int f_in, const float* W, int64_t ldw, const float* bias, const float* stats, float* W_folded,
                    int64_t ldwf, float* bias_folded, acm_stream_t stream);
+int acm_bnorm_fold_centred(int f_out, int f_in, const float* W, int64_t ldw, const float* bias, const float* beta, const float* stats,
+                           float* W_folded, int64_t ldwf, float* bias_folded, acm_stream_t stream);
+int acm_linear_fwd_shift(int64_t n_rows, int64_t f_in, int64_t f_out, const float* X, int64_t ldx, const float* x_shift,
+                         const float* W, int64_t ldw, const float* bias, int relu, const acm_dropout_t* drop, float* Y, int64_t ldy,
+                         void* workspace, size_t workspace_bytes, acm_stream_t stream);
+int acm_gemm_shift(int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
+                   int64_t ldb, const float* b_shift, float* C, int64_t ldc, void* workspace, size_t workspace_bytes,
+                   acm_stream_t stream);
 int acm_bnorm_param_bwd(int f_out, int f_in, const float* M, int64_t ldm, const float* s, const float* W, int64_t ldw,
                         const float* stats, float* dW, int64_t lddw, float* d_beta, float* d_gamma, acm_stream_t stream);
+int acm_bnorm_param_bwd_centred(int f_out, int f_in, const float* M, int64_t ldm, const float* s, const float* W, int64_t ldw,
+                                const float* beta, const float* stats, float* dW, int64_t lddw, float* d_beta, float* d_gamma,
+                                acm_stream_t stream);
 int acm_bnorm_bwd_workspace_bytes(int64_t n_rows, int f, size_t* bytes);
 int acm_bnorm_bwd(int64_t n_rows, int f, const float* dZ, int64_t lddz, const float* H, int64_t ldh, const float* stats,
                   const float* d_beta, const float* d_gamma, float keep_scale, int relu, float* G, int64_t ldg,
