@@ -40,12 +40,15 @@ EXPORTED_SYMBOLS = (
     "acm_linear_fwd_shift", "acm_gemm_shift", "acm_bnorm_fold_centred", "acm_bnorm_param_bwd_centred",
     "acm_proj_blocks_fwd", "acm_proj_blocks_bwd_workspace_bytes", "acm_proj_blocks_bwd",
     "acm_csr_build_loss_rows", "acm_csr_loss_rows_info", "acm_conv_fwd_tail_rows",
+    "acm_conv_agg_out_optional",
 )
 # the loss-row entry points (new symbols under ABI 29): callers look them up with getattr(lib, name, None) and keep the full
 # path where a library -- or a test double -- does not have them
 LOSS_ROWS_SYMBOLS = ("acm_csr_build_loss_rows", "acm_csr_loss_rows_info", "acm_conv_fwd_tail_rows")
 # the centred form of a deep mlpX stack (new symbols under ABI 29, looked up the same way): all four together, or the first form of
 # the stack (acm_bnorm_fold + acm_linear_fwd, acm_gemm + acm_bnorm_param_bwd) where a library or a test double lacks one
+# whether the hidden layer's `out` may stay unwritten (new symbol under ABI 29, looked up the same way: without it `out` is stored)
+OUT_OPTIONAL_SYMBOL = "acm_conv_agg_out_optional"
 BNORM_CENTRED_SYMBOLS = ("acm_bnorm_fold_centred", "acm_linear_fwd_shift", "acm_gemm_shift", "acm_bnorm_param_bwd_centred")
 
 
@@ -345,6 +348,7 @@ def _declare(lib):
     lib.acm_conv_bwd_local.argtypes = [i64, C.POINTER(ConvBwdLocal), vp, sz, vp]
     lib.acm_conv_bwd_spmm.argtypes = [vp, C.POINTER(ConvBwdSpmm), vp, sz, vp]
     lib.acm_conv_agg_fwd.argtypes = [vp, C.POINTER(ConvAggFwd), vp, sz, vp]
+    lib.acm_conv_agg_out_optional.argtypes = [C.POINTER(ConvAggFwd), i64, i32]
     lib.acm_conv_agg_bwd_workspace_bytes.argtypes = [i64, i32, i32, C.POINTER(sz)]
     lib.acm_conv_agg_bwd.argtypes = [i64, C.POINTER(ConvAggBwd), vp, sz, vp]
     lib.acm_nll_loss_workspace_bytes.argtypes = [i64, C.POINTER(sz)]

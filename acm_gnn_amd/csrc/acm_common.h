@@ -164,6 +164,9 @@ int acm_bwd_local_reduce(const acm_conv_bwd_local_t* p, const float* partial, in
 int acm_bwd_local16(const acm_conv_bwd_local_t* p, int64_t n_rows, float* partial, int max_blocks, hipStream_t s);
 // acm_conv_agg16.hip: the row-local forward stage in the transposed matrix-core layout (-1: not its case)
 int acm_agg_epi16(const acm_conv_agg_fwd_t* p, int64_t n_rows, bool* next_done, hipStream_t s);
+// ... the two halves of its out == NULL form: the predicates both launchers and acm_conv_agg_out_optional decide by
+bool acm_agg16_fwd_out_optional(const acm_conv_agg_fwd_t* p, int64_t n_rows);
+bool acm_agg16_bwd_out_optional(int n_channels, int f_pad, int f_out, bool head_stats, bool post_relu, bool post_scale, int proj_f);
 struct GatherRole;   // (acm_stream_device.h) ... and the row-local backward (blocks launched; 0: not its case; < 0: error)
 int acm_agg_bwd16(const acm_conv_agg_bwd_t* p, int64_t n_rows, float* partial, int max_blocks, hipStream_t s, const GatherRole* gr,
                   int gather_blocks);

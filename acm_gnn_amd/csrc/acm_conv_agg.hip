@@ -651,7 +651,10 @@ extern "C" int acm_conv_agg_fwd(const acm_csr_t* a, const acm_conv_agg_fwd_t* p,
     ACM_REQUIRE(a && p, ACM_EINVAL, "acm_conv_agg_fwd: NULL argument");
     int st = check_common(p, "acm_conv_agg_fwd");
     if (st != ACM_OK) return st;
-    ACM_REQUIRE((p->xg || p->agg_given) && p->out && p->agg && p->att, ACM_EINVAL, "acm_conv_agg_fwd: NULL tensor pointer");
+    ACM_REQUIRE((p->xg || p->agg_given) && p->agg && p->att, ACM_EINVAL, "acm_conv_agg_fwd: NULL tensor pointer");
+    // out == NULL: only where the sixteen-rows row-local stage hands the row on as next_zlh / next_zi (acm_conv_agg_out_optional)
+    ACM_REQUIRE(p->out || acm_agg16_fwd_out_optional(p, a->n_rows), ACM_EINVAL,
+                "acm_conv_agg_fwd: NULL tensor pointer (out may be NULL with agg_given, three channels, f_out 64 and next_zlh only)");
     ACM_REQUIRE((p->agg_given || (((uintptr_t)p->xg) % 16 == 0 && (p->ld_xg * 4) % 16 == 0 && p->ld_xg >= p->f_pad)) &&
                     ((uintptr_t)p->agg) % 16 == 0 && (p->ld_agg * 4) % 16 == 0 && p->ld_agg >= p->f_pad &&
                     ((uintptr_t)p->att) % 16 == 0, ACM_EINVAL,
@@ -723,6 +726,7 @@ extern "C" int acm_conv_agg_fwd(const acm_csr_t* a, const acm_conv_agg_fwd_t* p,
         if (st == ACM_OK) return next_done ? ACM_OK : next_projection(a, p, stream);
         if (st > 0) return st;
     }
+    ACM_REQUIRE(p->out, ACM_EUNSUPPORTED, "acm_conv_agg_fwd: out is NULL and the sixteen-rows row-local stage did not run");
     int grid = (int)((a->n_rows + 15) / 16);
     if (grid > 2048) grid = 2048;
     const CsrView cv = acm_view(a);
@@ -738,6 +742,19 @@ extern "C" int acm_conv_agg_fwd(const acm_csr_t* a, const acm_conv_agg_fwd_t* p,
         if (st != ACM_OK) return st;
     }
     return next_projection(a, p, stream);
+}
+
+// Whether acm_conv_agg_fwd takes `out == NULL` for this argument block (p->out itself is not looked at) and, with
+// proj_f > 0, whether acm_conv_agg_bwd will take it too for the backward of the same layer carrying a following layer of
+// proj_f columns (proj_dz).  proj_f == 0: a forward without a backward.  1: yes, 0: no.
+extern "C" int acm_conv_agg_out_optional(const acm_conv_agg_fwd_t* p, int64_t n_rows, int proj_f) {
+    if (!p || n_rows < 0 || proj_f < 0) return 0;
+    if (p->f_in < 1 || p->f_in > 16 || p->f_pad != agg_pad(p->f_in)) return 0;
+    if (!acm_agg16_fwd_out_optional(p, n_rows)) return 0;
+    if (proj_f == 0) return 1;
+    return proj_f == p->next_f && acm_agg16_bwd_out_optional(p->n_channels, p->f_pad, p->f_out, p->head_stats != nullptr, p->post_relu != 0,
+                                                             p->post_scale != nullptr, proj_f)
+               ? 1 : 0;
 }
 
 extern "C" int acm_conv_agg_bwd_workspace_bytes(int64_t n_rows, int f_in, int f_out, size_t* bytes) {

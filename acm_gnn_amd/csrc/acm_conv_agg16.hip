@@ -244,8 +244,8 @@ __device__ __forceinline__ void epi16_body(const acm_conv_agg_fwd_t& p, int n_ro
                 for (int t = 0; t < 4; ++t) o[t][r] *= (w[t] >= dc.thresh) ? dc.inv_keep : 0.f;
             }
         }
-        if (valid) {
-#pragma unroll
+        if (valid && p.out) {                      // (out == NULL, wave-uniform: the row lives on in next_zlh / next_zi only and
+#pragma unroll                                     //  the backward forms it again -- bwd16_body, REOUT)
             for (int t = 0; t < 4; ++t) *reinterpret_cast<f32x4*>(p.out + rr * ld_out + 16 * t + 4 * g) = o[t];
         }
         if (NEXT) {
@@ -319,10 +319,15 @@ struct B16Lds {
 // id streams for the next training step's P = A_low dropout(x) (acm_conv_agg_bwd_t.next_agg; stream_gather_role).  The
 // kernel is compiled for two waves per SIMD either way, so the pair costs the backward no occupancy; its waves get the
 // vector and matrix pipes almost to themselves (the gather waves wait on memory), the gather waves the memory system.
-template <int NC, int FP, bool LN, bool OUT_MASK, bool PROJ, bool GATHER>
+// REOUT (with PROJ, three channels, behind a fused ReLU without post_scale): acm_conv_agg_bwd_t.out is NULL -- the forward did
+// not store the row.  It is formed again from the three channels this kernel projects anyway, the stored alpha_c and the
+// dropout counter, with the expressions of epi16_body (same operands, same order: the same bits), instead of being read
+// (256 B per row, the one wide load that cannot be requested a step ahead).
+template <int NC, int FP, bool LN, bool OUT_MASK, bool PROJ, bool GATHER, bool REOUT = false>
 __device__ __forceinline__ void bwd16_body(const acm_conv_agg_bwd_t& p, int n_rows, float* __restrict__ partial, const GatherRole* gr) {
     using L = B16Lds<NC, FP, PROJ>;
     constexpr int KB = L::KB, PS = L::PS;
+    static_assert(!REOUT || (NC == 3 && PROJ && OUT_MASK), "the output row is formed again for the proj_* carriers of three channels only");
     __shared__ __attribute__((aligned(16))) float lds[L::TOTAL];
     const int lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4, wv = threadIdx.x >> 6;
     float* gt = lds + wv * (16 * ACM_B16_TS);                 // this wave's G tile
@@ -376,6 +381,9 @@ __device__ __forceinline__ void bwd16_body(const acm_conv_agg_bwd_t& p, int n_ro
     const float lo_a = p.relu_after ? 0.f : -INFINITY, lo_m = p.relu_mlp ? 0.f : -INFINITY;
     constexpr bool out_mask = OUT_MASK;
     const float post_gain = p.post_drop.p > 0.f ? 1.0f / (1.0f - p.post_drop.p) : 1.f;
+    AcmDropCtx dc = {};                             // REOUT: the forward's post-op mask, drawn again
+    if (REOUT) dc = acm_drop_ctx(p.post_drop);
+    const float lo_post = p.post_relu ? 0.f : -INFINITY;
     const unsigned ld_agg = (unsigned)p.ld_agg, ld_xs = (unsigned)p.ld_xs, ld_go = (unsigned)p.ld_grad_out,
                    ld_out = (unsigned)p.ld_out, ld_hs = (unsigned)p.ld_head_stats;
     const int wave = blockIdx.x * 4 + wv, nwaves = gridDim.x * 4;
@@ -425,7 +433,7 @@ __device__ __forceinline__ void bwd16_body(const acm_conv_agg_bwd_t& p, int n_ro
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 if (!PROJ) ngo[t] = *reinterpret_cast<const f32x4*>(p.grad_out + r1 * ld_go + 16 * t + 4 * g);
-                if (out_mask || PROJ) nou[t] = *reinterpret_cast<const f32x4*>(p.out + r1 * ld_out + 16 * t + 4 * g);
+                if ((out_mask || PROJ) && !REOUT) nou[t] = *reinterpret_cast<const f32x4*>(p.out + r1 * ld_out + 16 * t + 4 * g);
             }
 #pragma unroll
             for (int q = 0; q < NC; ++q) nst[q] = *reinterpret_cast<const f32x4*>(p.head_stats + r1 * ld_hs + 4 * q);
@@ -442,6 +450,20 @@ __device__ __forceinline__ void bwd16_body(const acm_conv_agg_bwd_t& p, int n_ro
         }
         ACM_B16_LOAD(base + nwaves * 16);           // the next step's operands (the addresses are clamped)
         const int gq = acm_opaque(g), mq = acm_opaque(m);
+        // REOUT: the forward's keep decisions of the lane's sixteen elements, bit 4 t + r, drawn while the loads are in flight and
+        // before the channels occupy their registers (the opaque copy keeps the four Philox calls up here; the opaque lane
+        // indices keep their counter words from being hoisted out of the row loop, four registers)
+        int keep = 0;
+        if (REOUT && dc.on) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                unsigned w[4];
+                acm_philox7(dc, base + mq, 4 * gq + r, w);   // word t <-> column 16 t + (4 g + r), as epi16_body draws it
+#pragma unroll
+                for (int t = 0; t < 4; ++t) keep |= (w[t] >= dc.thresh ? 1 : 0) << (4 * t + r);
+            }
+            keep = acm_opaque(keep);
+        }
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) px[mq * PS + 4 * kb + gq] = P[kb], px[mq * PS + FP + 4 * kb + gq] = x[kb];
         // RECOMP (four channels): a projected channel lives in 16 registers at a time -- computed for its dot product with dO,
@@ -469,20 +491,49 @@ __device__ __forceinline__ void bwd16_body(const acm_conv_agg_bwd_t& p, int n_ro
                                                                                 kb == 0 ? (f32x4){0.f, 0.f, 0.f, 0.f} : D[RECOMP ? 0 : c][t], 0, 0, 0);
             }
         }
+        if (REOUT) {
+            // the forward's row (epi16_body: mix, post-op ReLU, dropout) from the channels, clamped as there, and alpha_c of
+            // head_stats; a padding lane forms the row n_rows - 1 with another mask: finite, and multiplied by zeros below
+            const float a0 = nst[(3 * NC) >> 2][(3 * NC) & 3] * p.scale, a1 = nst[(3 * NC + 1) >> 2][(3 * NC + 1) & 3] * p.scale,
+                        a2 = nst[(3 * NC + 2) >> 2][(3 * NC + 2) & 3] * p.scale;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float lo = c < 2 ? lo_a : lo_m;
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) D[RECOMP ? 0 : c][t][r] = fmaxf(D[RECOMP ? 0 : c][t][r], lo);
+            }
+            // (straight into the wave's LDS tile, where the acc2 products want it: the mask below reads it back from there
+            //  sixteen bytes at a time instead of holding the row in sixteen registers beside the channels)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                f32x4 o;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float v = fmaf(a2, D[RECOMP ? 0 : 2][t][r], fmaf(a1, D[RECOMP ? 0 : 1][t][r], a0 * D[0][t][r]));
+                    o[r] = fmaxf(v, lo_post);
+                    if (dc.on) o[r] *= ((keep >> (4 * t + r)) & 1) ? dc.inv_keep : 0.f;
+                }
+                *reinterpret_cast<f32x4*>(gt + mq * ACM_B16_TS + 16 * t + 4 * gq) = o;
+            }
+        }
         f32x4 dO[4];
         const float gate = valid ? post_gain : 0.f;
         if (PROJ) {
             // the following layer's weight gradient: out^T proj_dz, the `out` tile through LDS like the G_c below; then this
             // layer's output gradient row by row, proj_dz[row] [W_L' | W_H' | W_I']^T, masked by the post-op right away
 #pragma unroll
-            for (int t = 0; t < 4; ++t) *reinterpret_cast<f32x4*>(gt + mq * ACM_B16_TS + 16 * t + 4 * gq) = nou[t];
+            for (int t = 0; t < 4; ++t)
+                if (!REOUT) *reinterpret_cast<f32x4*>(gt + mq * ACM_B16_TS + 16 * t + 4 * gq) = nou[t];
 #pragma unroll
             for (int s = 0; s < 4; ++s)
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
                     acc2[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(dza[s], gt[(4 * gq + s) * ACM_B16_TS + 16 * t + mq], acc2[t], 0, 0, 0);
 #pragma unroll
-            for (int t = 0; t < 4; ++t)
+            for (int t = 0; t < 4; ++t) {
+                if (REOUT) nou[t] = *reinterpret_cast<const f32x4*>(gt + mq * ACM_B16_TS + 16 * t + 4 * gq);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float4 wa = *reinterpret_cast<const float4*>(pw + (16 * t + 4 * gq + r) * 8);
@@ -492,6 +543,7 @@ __device__ __forceinline__ void bwd16_body(const acm_conv_agg_bwd_t& p, int n_ro
                     v = fmaf(dzr[4], wb.x, v), v = fmaf(dzr[5], wb.y, v);
                     dO[t][r] = out_mask ? ((nou[t][r] != 0.f) ? v * gate : 0.f) : v;        // (dzr is zero on padding rows)
                 }
+            }
         } else {
 #pragma unroll
             for (int t = 0; t < 4; ++t)
@@ -704,14 +756,14 @@ __device__ __forceinline__ void bwd16_body(const acm_conv_agg_bwd_t& p, int n_ro
     }
 }
 
-template <int NC, int FP, bool LN, bool OUT_MASK, bool PROJ>
+template <int NC, int FP, bool LN, bool OUT_MASK, bool PROJ, bool REOUT = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void agg_bwd16_kernel(acm_conv_agg_bwd_t p, int n_rows, float* __restrict__ partial) {
-    bwd16_body<NC, FP, LN, OUT_MASK, PROJ, false>(p, n_rows, partial, nullptr);
+    bwd16_body<NC, FP, LN, OUT_MASK, PROJ, false, REOUT>(p, n_rows, partial, nullptr);
 }
-template <int NC, bool LN, bool PROJ>
+template <int NC, bool LN, bool PROJ, bool REOUT = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void agg_bwd16_gather_kernel(acm_conv_agg_bwd_t p, int n_rows, float* __restrict__ partial,
                                                                                                    GatherRole gr) {
-    bwd16_body<NC, 8, LN, true, PROJ, true>(p, n_rows, partial, &gr);
+    bwd16_body<NC, 8, LN, true, PROJ, true, REOUT>(p, n_rows, partial, &gr);
 }
 
 }  // namespace
@@ -719,17 +771,38 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // The row-local forward stage over an existing P = A_low X (p->agg; with four channels also p->ps = A_low S).  Returns
 // ACM_OK after a launch, -1 when the configuration is not one this kernel is written for (the caller then runs
 // agg_epilogue_kernel), or an error.
+// The configurations agg_epi16_kernel is written for.  with_out: the row is stored (else p->out / ld_out are not looked at).
+static bool epi16_takes(const acm_conv_agg_fwd_t* p, int64_t n_rows, bool with_out) {
+    const int NC = p->n_channels, FP = p->f_pad;
+    if ((NC != 3 && NC != 4) || (FP != 4 && FP != 8 && FP != 16) || p->f_out != 64 || !(acm_tuning().rows16 & ACM_ROWS16_EPI)) return false;
+    int64_t ld_max = 64;
+    for (int64_t ld : {p->ld_agg, p->ld_xs, with_out ? p->ld_out : (int64_t)0, p->ld_head_stats, p->ld_post_scale, p->ld_agg_copy, p->ld_xs_copy,
+                       p->ld_ps, p->ld_ss})
+        ld_max = ld > ld_max ? ld : ld_max;
+    if (n_rows * ld_max >= (int64_t)INT32_MAX) return false;               // 32-bit element offsets
+    if (with_out && ((((uintptr_t)p->out) % 16) != 0 || (p->ld_out % 4) != 0)) return false;
+    if (p->post_scale && ((((uintptr_t)p->post_scale) % 16) != 0 || (p->ld_post_scale % 4) != 0)) return false;
+    if (NC == 4 && ((((uintptr_t)p->ps) % 16) != 0 || (((uintptr_t)p->ss) % 16) != 0 || p->ld_ps % 4 != 0 || p->ld_ss % 4 != 0)) return false;
+    return true;
+}
+
+// out == NULL, forward half: the row-local stage as its own launch (P given), three channels, and the row leaves as the
+// following layer's narrow projection (next_zlh / next_zi) -- whatever p->out holds.
+bool acm_agg16_fwd_out_optional(const acm_conv_agg_fwd_t* p, int64_t n_rows) {
+    return p->agg_given && p->n_channels == 3 && p->next_f >= 1 && p->next_f <= 2 && p->next_zlh && p->next_zi && epi16_takes(p, n_rows, false);
+}
+
+// out == NULL, backward half (REOUT of bwd16_body): the proj_* carriers of the hidden layer of a training step.
+bool acm_agg16_bwd_out_optional(int n_channels, int f_pad, int f_out, bool head_stats, bool post_relu, bool post_scale, int proj_f) {
+    return n_channels == 3 && f_pad == 8 && f_out == 64 && head_stats && post_relu && !post_scale && proj_f >= 1 && proj_f <= 2 &&
+           (acm_tuning().rows16 & ACM_ROWS16_BWD) != 0;
+}
+
 int acm_agg_epi16(const acm_conv_agg_fwd_t* p, int64_t n_rows, bool* next_done, hipStream_t s) {
     *next_done = false;
     const int NC = p->n_channels, FP = p->f_pad;
-    if ((NC != 3 && NC != 4) || (FP != 4 && FP != 8 && FP != 16) || p->f_out != 64 || !(acm_tuning().rows16 & ACM_ROWS16_EPI)) return -1;
-    int64_t ld_max = 64;
-    for (int64_t ld : {p->ld_agg, p->ld_xs, p->ld_out, p->ld_head_stats, p->ld_post_scale, p->ld_agg_copy, p->ld_xs_copy, p->ld_ps, p->ld_ss})
-        ld_max = ld > ld_max ? ld : ld_max;
-    if (n_rows * ld_max >= (int64_t)INT32_MAX) return -1;                  // 32-bit element offsets
-    if ((((uintptr_t)p->out) % 16) != 0 || (p->ld_out % 4) != 0) return -1;
-    if (p->post_scale && ((((uintptr_t)p->post_scale) % 16) != 0 || (p->ld_post_scale % 4) != 0)) return -1;
-    if (NC == 4 && ((((uintptr_t)p->ps) % 16) != 0 || (((uintptr_t)p->ss) % 16) != 0 || p->ld_ps % 4 != 0 || p->ld_ss % 4 != 0)) return -1;
+    if (!epi16_takes(p, n_rows, p->out != nullptr)) return -1;
+    if (!p->out && !acm_agg16_fwd_out_optional(p, n_rows)) return -1;
     const bool next = p->next_f > 0;
     int grid = (int)((n_rows + 63) / 64);
     if (grid > 1024) grid = 1024;                    // four workgroups (sixteen waves) per CU
@@ -753,12 +826,14 @@ int acm_agg_bwd16(const acm_conv_agg_bwd_t* p, int64_t n_rows, float* partial, i
     if ((NC != 3 && NC != 4) || (FP != 4 && FP != 8 && FP != 16) || p->f_out != 64 || !p->head_stats ||
         !(acm_tuning().rows16 & ACM_ROWS16_BWD))
         return 0;
-    const bool out_mask = p->out != nullptr && p->post_relu && !p->post_scale;
+    const bool proj = p->proj_dz != nullptr;
+    // (out == NULL: the row is formed again, REOUT)
+    const bool reout = !p->out && proj && acm_agg16_bwd_out_optional(NC, FP, p->f_out, true, p->post_relu != 0, p->post_scale != nullptr, p->proj_f);
+    const bool out_mask = (p->out != nullptr || reout) && p->post_relu && !p->post_scale;
     const bool no_post = !p->post_relu && !p->post_scale && !(p->post_drop.p > 0.f);
     if (!out_mask && !no_post) return 0;
-    const bool proj = p->proj_dz != nullptr;
     if ((proj || gr) && (FP != 8 || !out_mask)) return 0;      // the carriers exist for the hidden layer of a training step
-    if (proj && (!p->out || p->proj_f < 1 || p->proj_f > 2 || !p->proj_w_low || !p->proj_w_high || !p->proj_w_mlp || !p->proj_d_w ||
+    if (proj && ((!p->out && !reout) || p->proj_f < 1 || p->proj_f > 2 || !p->proj_w_low || !p->proj_w_high || !p->proj_w_mlp || !p->proj_d_w ||
                  p->ld_proj_dz < 3 * p->proj_f || p->proj_ld_w < p->proj_f || n_rows * p->ld_proj_dz >= (int64_t)INT32_MAX))
         return 0;
     for (const void* q : {(const void*)(proj ? nullptr : p->grad_out), (const void*)p->out, (const void*)p->head_stats,
@@ -781,7 +856,17 @@ int acm_agg_bwd16(const acm_conv_agg_bwd_t* p, int64_t n_rows, float* partial, i
     const auto ln_of = acm_flag(p->layernorm != 0);
     int st;
     // the carriers (FP = 8, the output read behind a fused ReLU): + next_agg (with or without proj_*), or proj_* alone
-    if (gr)
+    if (reout && gr)
+        st = acm_pick([&](auto ln) {
+            hipLaunchKernelGGL((agg_bwd16_gather_kernel<3, ln(), true, true>), dim3(grid), dim3(512), 0, s, q, (int)n_rows, partial, *gr);
+            return ACM_OK;
+        }, ln_of);
+    else if (reout)
+        st = acm_pick([&](auto ln) {
+            hipLaunchKernelGGL((agg_bwd16_kernel<3, 8, ln(), true, true, true>), dim3(grid), dim3(256), 0, s, q, (int)n_rows, partial);
+            return ACM_OK;
+        }, ln_of);
+    else if (gr)
         st = acm_pick([&](auto nc, auto ln, auto pj) {
             hipLaunchKernelGGL((agg_bwd16_gather_kernel<nc(), ln(), pj()>), dim3(grid), dim3(512), 0, s, q, (int)n_rows, partial, *gr);
             return ACM_OK;

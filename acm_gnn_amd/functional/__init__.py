@@ -14,8 +14,9 @@ residual branch), ``gcn`` (the one-channel layers of the study's baselines), ``b
 from .. import _lib, tuning  # noqa: F401
 from ..graph import CsrGraph, FilterOperators, SparseFeatures, _device_ctx, _require_cuda, _stream  # noqa: F401  (the seams)
 from ._launch import KernelTimer, _Timed, set_kernel_timer  # noqa: F401
-from ._context import (CallContext, DeferredReductions, InputPipeline, Tape, TapeBroken, _ambient,  # noqa: F401
-                       deferred_reductions, deferred_reductions_as, fused_loss_tail, input_pipeline, on_tape)
+from ._context import (CallContext, DeferredReductions, HiddenToken, InputPipeline, Tape, TapeBroken, _ambient,  # noqa: F401
+                       deferred_reductions, deferred_reductions_as, ensure_hidden_written, fused_loss_tail, hidden_elision_why_not,
+                       input_pipeline, lazy_hidden_why_not, on_tape)
 from .ops import (DropoutState, _drop_spec, agg_pad_width, bce_loss, bce_loss_and_grad, cast_bf16, dropout, eval_metrics,  # noqa: F401
                   eval_metrics_buffers, eval_rocauc, gemm, gemm_drop_supported, gemm_split, masked_bce, masked_nll, mm, nll_loss_and_grad, proj3, proj_bwd,
                   proj_bwd_supported, proj_fwd, rocauc_buffers, spmm, spmm_v)

@@ -4,7 +4,7 @@ import torch
 
 from .. import tuning
 from ..graph import SparseFeatures
-from ._context import _call_or_ambient, _run
+from ._context import _call_or_ambient, _run, ensure_hidden_written
 from .blocks import project_blocks
 from ._conv_shared import PROJECTED, _chan_block
 from ._launch import _F32
@@ -88,6 +88,10 @@ def acm_conv(x, params, ops, cfg, post_relu=False, post_scale=None, post_drop=No
     else:
         fn = _ROUTES[_conv_route(x, ops, cfg, p["weight_low"].shape[0], p["weight_low"].shape[1], post_scale, call, tail_layer)]
         pregathered = getattr(ops, "_pregathered", None)                          # one-shot hand-over from models.GCN
+        if fn is not _AcmLiteral:                 # (the literal route knows how to leave an unwritten hidden activation unread)
+            ensure_hidden_written(call, x)
+        if call is not None:
+            call.grad_enabled = torch.is_grad_enabled()
     ops._pregathered = None
     return _run(
         fn, x, p["weight_low"], p["weight_high"], p["weight_mlp"], p["att_vec_low"], p["att_vec_high"],

@@ -6,11 +6,44 @@ import torch
 
 from .. import _lib, tuning
 from .. import functional as _pkg
-from ._context import _call_or_ambient, _next_proj_request
+from ._context import HiddenToken, _call_or_ambient, _next_proj_request, hidden_elision_why_not
 from ._conv_shared import _NO_GRADS, _conv_prologue, _flat_views, _gathered_input, _grads, _head_params, _k3_setup, \
     _narrow_tables, _pack_head, _reduce_replicated, _set_head, _set_post, _struc_grad, _struc_rows, _unpack_head
 from ._launch import EUNSUPPORTED, _F32, _as_f32c, _vp, _workspace, launch
 from .ops import _drop_spec, cast_bf16, gemm, proj_bwd, spmm
+
+
+def _out_optional_query(p, n):
+    """proj_f -> the library's answer to acm_conv_agg_out_optional for the argument block ``p``; None without the symbol."""
+    fn = getattr(_lib.load(), _lib.OUT_OPTIONAL_SYMBOL, None)
+    if fn is None:
+        return None
+    return lambda proj_f: int(fn(C.byref(p), n, int(proj_f))) == 1
+
+
+class _WriteOut:
+    """What writes a hidden activation its forward left unwritten, should a consumer turn out to need its bytes
+    (_context.HiddenToken): one more launch of the row-local stage over the rows the forward worked on -- ``xs`` / ``agg``, the
+    copies it left for the backward -- with only ``out`` requested.  The post-op's counter does not move between a step's
+    forward and its backward, so the mask and every bit are the forward's."""
+
+    def __init__(self, p, graph, shape, label, dev, xs, agg, keep):
+        q = self.q = _lib.ConvAggFwd()
+        C.memmove(C.byref(q), C.byref(p), C.sizeof(q))
+        q.xs, q.ld_xs = xs.data_ptr(), xs.stride(0)
+        q.agg, q.ld_agg, q.agg_given = agg.data_ptr(), agg.stride(0), 1
+        q.agg_copy = q.xs_copy = q.next_x = q.head_stats = None
+        q.next_f, q.next_w_low, q.next_w_high, q.next_w_mlp, q.next_zlh, q.next_zi = 0, None, None, None, None, None
+        self.graph, self.shape, self.label, self.dev, self.keep = graph, shape, label, dev, (xs, agg) + tuple(keep)
+
+    def fresh(self):
+        return torch.empty(*self.shape, dtype=_F32, device=self.dev)
+
+    def __call__(self, out):
+        q = self.q
+        att = torch.empty(self.shape[0], 4, dtype=_F32, device=self.dev)
+        q.out, q.ld_out, q.att = out.data_ptr(), out.stride(0), att.data_ptr()
+        launch("acm_conv_agg_fwd", self.label, self.dev, self.graph.handle, C.byref(q), None, 0)    # (P is given: no workspace)
 
 
 class _AcmAggFirst(torch.autograd.Function):
@@ -94,6 +127,17 @@ class _AcmAggFirst(torch.autograd.Function):
             p.next_ld_w, p.next_f, p.next_relu = n_w3[0].stride(0), f2, int(n_relu)
             p.next_zlh, p.ld_next_zlh = n_zlh.data_ptr(), n_zlh.stride(0)
             p.next_zi, p.ld_next_zi = n_zi.data_ptr(), n_zi.stride(0)
+        # the output stays unwritten where only the following layer consumes it and does so through next_zlh / next_zi
+        # (forward) and this layer's own backward kernel (acm_conv_agg_bwd_t.proj_*): decided here, before the launch
+        # (a backward may follow: the caller's grad mode as acm_conv saw it -- in here gradients are always switched off)
+        will_backward = any(ctx.needs_input_grad) and call.grad_enabled
+        why = hidden_elision_why_not(call, nxt, agg_given is not None, ops.sharded, will_backward,
+                                     int(getattr(ops, "hops", 1)), ctx.post_relu, ctx.post_scale, stats is not None, f,
+                                     _out_optional_query(p, n))
+        call.elision = (why is None, why)
+        ctx.out_elided = why is None
+        if ctx.out_elided:
+            p.out = None
         ws = ops.low.workspace(max(fp, f) if four else fp)
         launch("acm_conv_agg_fwd", f"conv_agg_{'epi' if agg_given is not None else 'fwd'}/F{f}k{k}i{f_in}", dev, ops.low.handle, C.byref(p),
                _vp(ws), ws.numel() * 4)
@@ -106,9 +150,15 @@ class _AcmAggFirst(torch.autograd.Function):
         ctx.ops, ctx.cfg, ctx.f_in = ops, cfg, f_in
         # with a fused ReLU the output itself records which elements the post-op let through: the backward reads it
         # instead of regenerating the dropout mask (no extra memory: the next layer keeps the same tensor alive)
-        ctx.out_mask = bool(ctx.post_relu) and ctx.post_scale is None
+        # (an unwritten output is an identity token for pre_proj / hidden_private only: not saved, never read -- ctx.elide, its
+        #  HiddenToken, writes it for a consumer that needs its bytes after all)
+        ctx.out_mask = bool(ctx.post_relu) and ctx.post_scale is None and not ctx.out_elided
         if ctx.pipe is not None:
             xpad, agg = ctx.pipe.saved[0], ctx.pipe.saved[1]
+        ctx.elide = None
+        if ctx.out_elided:
+            call.elided = ctx.elide = HiddenToken(out, _WriteOut(p, ops.low, (n, f), f"conv_agg_out/F{f}k{k}i{f_in}", dev, xpad, agg,
+                                                                 (wl, wh, wm, mix, *vecs, *lnw, *lnb, ctx.post_drop)))
         ctx.save_for_backward(xpad, agg, wl, wh, wm, *_pack_head(vecs, lnw, lnb, mix), *extra, *((out,) if ctx.out_mask else ()))
         ctx.mark_non_differentiable(att)
         return out, att
@@ -135,9 +185,16 @@ class _AcmAggFirst(torch.autograd.Function):
         if lazy is not None and (grad_out is not lazy["placeholder"] and grad_out.data_ptr() != lazy["placeholder"].data_ptr()):
             raise RuntimeError("acm_conv: the hidden activation marked private (CallContext.hidden_private) received a gradient "
                                "from somewhere else as well")
-        fuse_proj = (lazy is not None and fp == 8 and f == 64 and out_fwd is not None and ctx.post_scale is None
-                     and ctx.head_stats is not None)
+        elide = getattr(ctx, "elide", None)                     # the HiddenToken of an `out` the forward left unwritten
+        elided = elide is not None and not elide.written        # ... and nobody has written since
         defer = ctx.call.defer
+        token_x = lazy["x"] if lazy is not None else None       # (the token itself, where the following layer handed it back)
+        if elide is not None and not elided:              # a consumer asked for its bytes in the meantime: read like a stored one
+            out_fwd = elide.write(token_x)
+        fuse_proj = (lazy is not None and fp == 8 and f == 64 and (out_fwd is not None or elided) and ctx.post_scale is None
+                     and ctx.head_stats is not None and bool(ctx.post_relu))
+        if elided and not fuse_proj:                      # no kernel here forms the row again: written now, the mask is read
+            out_fwd, elided = elide.write(token_x), False
         if lazy is not None and not fuse_proj:            # the kernel cannot take it: materialise dX and dW' now
             proj_bwd(lazy["x"], lazy["dz"], lazy["w3"], lazy["d_w"], defer=defer, dx_out=lazy["placeholder"])
             lazy = None
@@ -185,6 +242,9 @@ class _AcmAggFirst(torch.autograd.Function):
         st = launch("acm_conv_agg_bwd", f"conv_agg_bwd{'+gather' if carry else ''}{'+proj' if lazy is not None else ''}/F{f}k{k}i{f_in}", dev, n,
                     C.byref(q), _vp(ws), ws.numel() * 4, unsupported_ok=lazy is not None or carry)
         if st == EUNSUPPORTED:                            # not with these riders after all: the plain launch(es)
+            if elided:                                    # (acm_conv_agg_out_optional said otherwise: the row is written first)
+                out_fwd, elided = elide.write(token_x), False
+                q.out, q.ld_out = out_fwd.data_ptr(), out_fwd.stride(0)
             if lazy is not None:
                 proj_bwd(lazy["x"], lazy["dz"], lazy["w3"], lazy["d_w"], defer=defer, dx_out=lazy["placeholder"])
                 q.grad_out, q.proj_dz, lazy = grad_out.data_ptr(), None, None

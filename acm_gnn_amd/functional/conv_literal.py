@@ -7,7 +7,7 @@ import torch
 from .. import _lib, tuning
 from .. import functional as _pkg
 from ..graph import SparseFeatures
-from ._context import _current_tape, _take_pre_proj
+from ._context import _current_tape, _take_pre_proj, ensure_hidden_written, hidden_token_of, lazy_hidden_why_not
 from ._conv_shared import _NO_GRADS, _chan_block, _conv_prologue, _flat_views, _gathered_input, _grads, _head_params, _hop_buffer, \
     _k3_setup, _low_product, _narrow_tables, _pack_head, _reduce_replicated, _set_head, _set_post, _struc_grad, _struc_rows, \
     _unpack_head, _z_pitch, PROJECTED
@@ -41,6 +41,8 @@ def _literal_project(ctx, x, w3, ops, cfg):
     # one aligned vector fetch, so rows are padded to a multiple of that block.
     ldz = _z_pitch(f, fb)
     pre = _take_pre_proj(call, x, w3, cfg.relu_before) if use_proj else None
+    if pre is None and not sparse_x:              # this layer projects x itself: a hidden activation left unwritten is written first
+        ensure_hidden_written(call, x)
     drop_spec = _drop_spec(ctx.in_drop, ops.row_offset) if ctx.in_drop is not None else None
     # [Z_L | Z_H] as a compact table of its own (what a narrow gather / the k-hop chain walks: 16-byte-block rows at
     # their own pitch instead of [Z_L | Z_H | Z_I | pad] rows), Z_I next to it
@@ -246,8 +248,19 @@ class _AcmLiteral(torch.autograd.Function):
         tape = _current_tape()
         prod = (getattr(x, "grad_fn", None) or (tape.producer(x) if tape is not None else None)) if not sparse_x else None
         if (call.hidden_private is x and prod is not None and getattr(prod, "agg_first", False) and getattr(prod, "call", None) is call
-                and not zero_padded and hops == 1 and call.defer is not None):
+                and not zero_padded and lazy_hidden_why_not(call.defer, hops) is None):
             ctx.lazy_producer = prod
+        # an input its layer left unwritten (CallContext.elided): only the lazy backward does without its bytes -- a layer that
+        # will not go lazy writes it now (the backward's acm_proj_bwd / acm_gemm reads x); one that means to keeps the means to
+        # write it should its backward take another branch after all
+        ctx.unwritten_x = None
+        tok = hidden_token_of(call, x) if not sparse_x else None
+        if tok is not None:
+            # (call.grad_enabled: the caller's grad mode, acm_conv -- a forward under no_grad has no backward to read x)
+            if ctx.lazy_producer is None and any(ctx.needs_input_grad) and call.grad_enabled:
+                ensure_hidden_written(call, x)
+            else:
+                ctx.unwritten_x = tok
         ctx.save_for_backward(w3[0] if sparse_x else x, *w3, zlh, zi, pre, *_pack_head(vecs, lnw, lnb, mix))
         ctx.mark_non_differentiable(att)
         return out, att
@@ -303,6 +316,13 @@ def _fwd_tail(ctx, ops, cfg, graph, p, ws, tail_req, w3, pre, zi, vecs, lnw, lnb
         if call.defer is not None:
             call.defer.hold(wt, [loss, st3["d_mix"], *st3["d_vec"], *st3["d_lnw"], *st3["d_lnb"]], keep=[loss, st3["flat"]])
     return st
+
+
+def _write_unwritten_x(ctx, x):
+    """The backward is about to read x: a hidden activation its layer left unwritten (ctx.unwritten_x) is written first."""
+    tok = getattr(ctx, "unwritten_x", None)
+    if tok is not None and not tok.written:
+        tok.write(x)
 
 
 def _k3_backward(ctx, grad_out):
@@ -442,8 +462,10 @@ def _literal_backward(ctx, grad_out):
             d_x = torch.empty(n, x.shape[1], dtype=_F32, device=dev)
             prod.lazy = dict(dz=dz, w3=w3, d_w=d_wcat, x=x, placeholder=d_x)
         else:
+            _write_unwritten_x(ctx, x)
             d_x = proj_bwd(x, dz, w3, d_wcat, defer=defer)                # pass over x (acm_proj_bwd)
     else:
+        _write_unwritten_x(ctx, x)
         d_wcat = gemm(x, dz, trans_a=True, col_blocks=3,
                       out=flat[:nw].view(3, f_in_w, f),                   # contiguous per weight
                       a_drop=_drop_spec(ctx.in_drop, ops.row_offset) if getattr(ctx, "in_drop_used", False) else None)

@@ -158,9 +158,10 @@ class GCN(nn.Module):
         # the output layer's narrow projection may ride the hidden layer's epilogue (CallContext.next_proj / pre_proj); not
         # with the ACM-GCN++ residual, which changes the hidden activations in between
         call.next_proj = self.gcns[1] if self.model_type != "acmgcnpp" else None
+        call.next_private = self._hidden_is_private()
         fea = self.gcns[0](x, adj_low, adj_high, adj_low_unnormalized, post_relu=True, post_drop=(p, 1, st), **kw,
                            rows_permuted=self._rows_permuted, call=call)
-        call.next_proj = None
+        call.next_proj, call.next_private = None, False
         if add_fused:
             ops_ = adj_low if isinstance(adj_low, FilterOperators) else None
             xr = x
@@ -175,7 +176,7 @@ class GCN(nn.Module):
         try:
             return self.gcns[1](fea, adj_low, adj_high, adj_low_unnormalized, rows_permuted=self._rows_permuted, call=call)
         finally:
-            call.hidden_private = None
+            call.hidden_private = call.elided = None
 
     def _forward_snowball(self, x, adj_low, adj_high, fused, call):
         """models.py:57-64: h_k = dropout(relu(layer_k([x | h_0 | ... | h_{k-1}]))), out = layer_last([x | h_0 | ...]).
@@ -211,6 +212,27 @@ class GCN(nn.Module):
                 h = self.gcns[k](inp, adj_low, adj_high, None, post_relu=True, post_scale=scale, rows_permuted=self._rows_permuted, call=call)
             blocks.append(h)
         return self.gcns[-1](cat(blocks), adj_low, adj_high, None, rows_permuted=self._rows_permuted, call=call)
+
+    def _hidden_is_private(self):
+        """The promise CallContext.next_private makes before the hidden layer runs: its output goes to the output layer and
+        nowhere else -- the two-layer models without the ACM-GCN++ residual (which adds to it), no forward hook on either
+        layer that could look at it, and neither layer's ``forward`` replaced on the instance or in a subclass (a wrapper
+        could read its input).  The hidden layer may then leave the tensor unwritten (functional: hidden elision).  The hook
+        registries are torch's private attributes; a torch that lacks one of them gets no promise."""
+        from .layers import GraphConvolution
+        if self.model_type == "acmgcnpp" or len(self.gcns) != 2:
+            return False
+        for layer in self.gcns:
+            if "forward" in layer.__dict__ or type(layer).forward is not GraphConvolution.forward:
+                return False
+            if not all(hasattr(layer, a) for a in ("_forward_hooks", "_forward_pre_hooks")):
+                return False
+        from torch.nn.modules import module as _m
+        if not (hasattr(_m, "_global_forward_hooks") and hasattr(_m, "_global_forward_pre_hooks")):
+            return False
+        hooked = bool(_m._global_forward_hooks) or bool(_m._global_forward_pre_hooks)
+        return not hooked and not self.gcns[0]._forward_hooks and not self.gcns[1]._forward_pre_hooks \
+            and not self.gcns[1]._forward_hooks
 
     def auto_csr(self, x, ops):
         """Wide, mostly-zero features handed over dense -> their CSR twin (graph.SparseFeatures.auto, tuning key
@@ -275,9 +297,10 @@ class GCN(nn.Module):
             ones = self._ones_like_hidden(x.shape[0], self.gcns[0].out_features, x.device)
             scale = drop(ones)
         call.next_proj = self.gcns[1] if self.model_type != "acmgcnpp" else None     # see _forward_fused_dropout
+        call.next_private = self._hidden_is_private()
         fea = self.gcns[0](x, adj_low, adj_high, adj_low_unnormalized, post_relu=True, post_scale=scale,
                            rows_permuted=self._rows_permuted, call=call)
-        call.next_proj = None
+        call.next_proj, call.next_private = None, False
         if self.model_type == "acmgcnpp":
             fea = fea + xx
         else:
@@ -285,4 +308,4 @@ class GCN(nn.Module):
         try:
             return self.gcns[1](fea, adj_low, adj_high, adj_low_unnormalized, rows_permuted=self._rows_permuted, call=call)
         finally:
-            call.hidden_private = None
+            call.hidden_private = call.elided = None

@@ -231,6 +231,9 @@ class TrainStep:
         self.loss_rows, self.loss_rows_refused = None, "not requested"
         if self.small is None:
             self._attach_loss_rows()
+        # whether the last forward (the captured one, with use_graph) left the hidden activation unwritten (tuning key
+        # ``elide_hidden``; functional.hidden_elision_why_not), and the reason if it did not
+        self.hidden_elided, self.hidden_elided_refused = False, "no forward has run"
         if use_graph:
             self._capture()
 
@@ -384,6 +387,7 @@ class TrainStep:
             with AF.deferred_reductions_as(call.defer), AF.input_pipeline(call.pipe), tail:
                 out = self.model(self.x, self.adj, self.adj_high, self.adj_un, **kw)
         call.tail = None
+        self._note_elision(call)
         if tail.matches(out):
             return tail.loss, tail.dz, out
         loss, dz = AF.nll_loss_and_grad(out, self.labels, self.weights, defer=call.defer)   # = masked_nll(...).backward(), two launches less
@@ -399,8 +403,13 @@ class TrainStep:
         else:
             with AF.deferred_reductions_as(call.defer), AF.input_pipeline(call.pipe):
                 out = self.model(self.x, self.adj, self.adj_high, self.adj_un, **kw)
+        self._note_elision(call)
         loss, dz = AF.bce_loss_and_grad(out, self.labels, self.weights, defer=call.defer)
         return loss, dz, out
+
+    def _note_elision(self, call):
+        done, why = call.elision if call.elision is not None else (False, "no aggregate-first hidden layer ran with this call")
+        self.hidden_elided, self.hidden_elided_refused = bool(done), why
 
     def _eager(self):
         if not self.model.training:
@@ -621,6 +630,13 @@ class EvalStep:
         self.graph, self.out, self.res = None, None, None
         self._held = None
         self._use_graph = bool(use_graph)
+        import inspect
+        try:                                             # models.GCN takes the pass's CallContext as a keyword (TrainStep does the same)
+            self._takes_call = "call" in inspect.signature(model.forward).parameters
+        except (TypeError, ValueError):
+            self._takes_call = False
+        # whether the last pass (the captured one, with use_graph) left the hidden activation unwritten, and why not
+        self.hidden_elided, self.hidden_elided_refused = False, "no forward has run"
         if use_graph:
             self._capture()
 
@@ -650,6 +666,11 @@ class EvalStep:
         self.model.eval()
         if self.small is not None:
             out = self.small.run()                       # three launches, one C-ABI call (acm_small_step, train = 0)
+        elif self._takes_call:
+            call = AF.CallContext.from_ambient()         # (what the model would make itself: here to read what the layers report)
+            out = self.model(self.x, self.adj, self.adj_high, self.adj_un, call=call)
+            done, why = call.elision if call.elision is not None else (False, "no aggregate-first hidden layer ran with this call")
+            self.hidden_elided, self.hidden_elided_refused = bool(done), why
         else:
             out = self.model(self.x, self.adj, self.adj_high, self.adj_un)
         if self.metric == "rocauc" or self.criterion == "bce":

@@ -35,6 +35,10 @@ Host-level keys:
                weight is 0 -- acm_conv_fwd_tail_rows over a loss-row attachment of the operator, built once per step object;
                same bits as the full path.  1 = where it
                applies (default), 0 = never
+    elide_hidden  the hidden activation of a two-layer ACM model that only the output layer consumes is not stored: the hidden
+               layer's row-local forward (agg_epi16) hands the row on as the output layer's narrow projection, and its backward
+               forms the row again (acm_conv_agg_out_optional decides; functional.hidden_elision); same bits as the storing
+               path.  1 = where it applies (default), 0 = never
 
 One policy for a malformed ACM_TUNING in both readers: the item is REPORTED on stderr and IGNORED -- by the
 library when it is loaded, by this module when it is imported (``parse(text)`` itself stays strict for programmatic use:
@@ -50,9 +54,9 @@ import threading
 
 KERNEL_KEYS = ("chunk", "wide_form", "bwd_split", "rows16", "agg_fused", "gemm_forms")
 HOST_DEFAULTS = {"rewrites": 15, "implicit": 1, "relabel": -1, "pipeline": 8192, "csr_features": 256, "small_step": 16384,
-                 "mlp_stack": 1, "loss_rows": 1}
+                 "mlp_stack": 1, "loss_rows": 1, "elide_hidden": 1}
 HOST_RANGES = {"rewrites": (0, 15), "implicit": (0, 1), "relabel": (-1, 1), "pipeline": (0, 1 << 31), "csr_features": (0, 1 << 31),
-               "small_step": (0, 16384), "mlp_stack": (0, 1), "loss_rows": (0, 1)}
+               "small_step": (0, 16384), "mlp_stack": (0, 1), "loss_rows": (0, 1), "elide_hidden": (0, 1)}
 
 REWRITE_AGG_FIRST = 1
 REWRITE_ACMII_RECOMPUTE = 2

@@ -678,7 +678,9 @@ typedef struct {
     const float* ln_weight[4];
     const float* ln_bias[4];
     const float* att_mix;              /* 3 x 3 */
-    float* out; int64_t ld_out;        /* [n_rows, F]                                          */
+    float* out; int64_t ld_out;        /* [n_rows, F].  May be NULL where acm_conv_agg_out_optional says so (agg_given,
+                                        * three channels, F = 64, next_zlh requested): the row is then not stored --
+                                        * it leaves as next_zlh / next_zi, and acm_conv_agg_bwd forms it again        */
     float* agg; int64_t ld_agg;        /* [n_rows, f_pad]  P = A_low X, saved for backward     */
     float* att;                        /* [n_rows, 4]                                          */
     const float* post_scale; int64_t ld_post_scale;   /* fused post-op, as in acm_conv_fwd_t   */
@@ -728,6 +730,11 @@ typedef struct {
 
 int acm_conv_agg_fwd(const acm_csr_t* a_low, const acm_conv_agg_fwd_t* p,
                      void* workspace, size_t workspace_bytes, acm_stream_t stream);
+/* 1 if acm_conv_agg_fwd takes p->out == NULL for this block (p->out itself is not looked at; every other field as it will
+ * be passed) and, with proj_f > 0, acm_conv_agg_bwd takes out == NULL for the same layer's backward carrying proj_dz of a
+ * following layer with proj_f (= p->next_f) columns; proj_f = 0 asks about the forward alone (an evaluation pass).  0
+ * otherwise.  Decided by the predicates the two launchers use; launches nothing.  (Added under ABI 29.) */
+int acm_conv_agg_out_optional(const acm_conv_agg_fwd_t* p, int64_t n_rows, int proj_f);
 
 typedef struct {
     int32_t f_in, f_pad, f_out, relu_after, relu_mlp, layernorm;
@@ -757,7 +764,12 @@ typedef struct {
     const float* out; int64_t ld_out;     /* the forward's `out`, or NULL.  With post_relu set and no post_scale the fused
                                            * post-op is undone by reading it -- out != 0 <=> the ReLU passed AND the dropout
                                            * kept the element (relu'(0) = 0 as in torch) -- instead of recomputing the mixed
-                                           * row and regenerating the Philox mask (an eighth of the kernel's VALU work)  */
+                                           * row and regenerating the Philox mask.  NULL together with proj_dz, head_stats,
+                                           * post_relu, no post_scale, three channels, f_pad 8, F = 64 (the backward half of
+                                           * acm_conv_agg_out_optional): the sixteen-rows kernel forms the row again from the
+                                           * channels it projects anyway, alpha_c of head_stats and post_drop -- the forward's
+                                           * expressions, the same bits -- instead of reading 256 B per row; any other
+                                           * combination of NULL and proj_dz is ACM_EUNSUPPORTED                         */
     /* The NEXT step's input aggregation, carried by this launch (NULL next_agg: off).  This kernel is bound by its vector
      * instructions and leaves the memory system idle; the narrow gather  next_agg = next_row_scale * (A_low next_xg)  of the
      * next training step's first layer is bound by memory latency and depends on nothing this step computes (the input
