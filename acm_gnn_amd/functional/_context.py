@@ -1,6 +1,6 @@
 """What lives for one training step or one model call beside the tensors: the deferred second phases, the CallContext
 handed down a forward, the calling thread's ambient context and Tape (``_TLS``: read and written in this module only), the
-``with`` blocks that set them, the input pipeline and the projection hand-off between two layers."""
+``with`` blocks that set them and the input pipeline."""
 import bisect
 import ctypes as C
 import threading
@@ -110,32 +110,19 @@ class CallContext:
     * ``defer``     a DeferredReductions the second phases of the call's kernels are appended to (or None: reduce at once)
     * ``tail``      a pending fused_loss_tail request for the model's output layer
     * ``pipe``      the training loop's InputPipeline
-    * ``next_proj`` / ``pre_proj``  the narrow-projection hand-off between a hidden layer and the layer that follows it
-    * ``hidden_private``  the hidden activation tensor only the following layer consumes (backward-side hand-off)
-    * ``next_private``  the same promise made BEFORE the hidden layer runs: its output will be consumed by the layer named in
-      ``next_proj`` and by nothing else, so the layer may leave it unwritten (``elided``; ``elision`` = (elided, why not))
+    * ``link``      the HiddenLink (_hidden.py) between the hidden layer and the layer after it, while the model runs the two
+    * ``elision``   what the last aggregate-first hidden layer did with its output: (left unwritten?, the reason if not)
 
     A context belongs to ONE model call: models.GCN / layers.GraphConvolution take it as ``call=`` (train.TrainStep passes
     its own) or derive a fresh one from the thread's ambient context -- what ``with deferred_reductions()`` /
     ``with fused_loss_tail()`` blocks of the calling thread have set.  Nothing lives in module globals: two models, two
     threads or an exception between two layers cannot see each other's hand-offs, and a backward (which autograd may run on
     another thread) uses the context its forward captured."""
-    __slots__ = ("defer", "tail", "pipe", "next_proj", "pre_proj", "hidden_private", "next_private", "elided", "elision",
-                 "grad_enabled")
+    __slots__ = ("defer", "tail", "pipe", "link", "elision", "grad_enabled")
 
     def __init__(self, defer=None, tail=None, pipe=None):
         self.defer, self.tail, self.pipe = defer, tail, pipe
-        self.next_proj = self.pre_proj = None
-        # set by a model around the call of a layer whose input tensor is the previous layer's output and is used NOWHERE
-        # else (models.GCN: the hidden activations of the two-layer models): that layer's backward may then leave its input
-        # gradient to the previous layer's backward kernel (acm_conv_agg_bwd_t.proj_*) instead of materialising it
-        self.hidden_private = None
-        # set by the model BEFORE the hidden layer runs (beside next_proj): the promise hidden_private makes afterwards.  An
-        # aggregate-first layer that takes it leaves the HiddenToken of its unwritten output in ``elided`` until the
-        # model call ends, and says what it did in ``elision`` = (elided?, the reason if not)
-        self.next_private = False
-        self.elided = None
-        self.elision = None
+        self.link = self.elision = None
         self.grad_enabled = True         # torch.is_grad_enabled() where the layer was called (acm_conv notes it: inside a
                                          # Function's forward it is always off); True = a backward may follow
 
@@ -207,11 +194,6 @@ class Tape:
     def __init__(self):
         self.records = []
         self.produced = {}                    # id(tensor) -> tensor (kept alive: an id must not be handed to another object)
-        self.ctx_of = {}                      # id(tensor) -> the record's ctx: the stand-in for ``tensor.grad_fn`` of the
-                                              # lazy-gradient hand-off.  On the TAPE, not on the tensor: a tensor that outlives
-                                              # the step (a layer's ``att``, an output a caller keeps) must not pin the step's
-                                              # saved activations, and ``out -> ctx -> saved out`` must not be a cycle only the
-                                              # cyclic collector frees (live bytes grew 1.5 -> 8.9 MB in ten steps)
 
     def run(self, fn, args):
         needs = []
@@ -233,20 +215,15 @@ class Tape:
         for o in outs:
             if isinstance(o, torch.Tensor) and o.is_floating_point() and id(o) not in ctx.non_differentiable:
                 o.requires_grad_(True)
-                self.ctx_of[id(o)] = ctx
                 self.produced[id(o)] = o
         self.records.append((fn, ctx, args, outs))
         return out
-
-    def producer(self, t):
-        """The ctx of the record that produced ``t`` on this tape (None: not a differentiable output of one)."""
-        return self.ctx_of.get(id(t)) if self.produced.get(id(t)) is t else None
 
     def release(self):
         """End of the step (or of the attempt): every record lets go of what it saved."""
         for _, ctx, _, _ in self.records:
             ctx.release()
-        self.records, self.produced, self.ctx_of = [], {}, {}
+        self.records, self.produced = [], {}
 
     def backward(self, out, grad):
         if id(out) not in self.produced:
@@ -541,126 +518,3 @@ class InputPipeline:
             self.primed = False
         self.next_table_ready = self.next_agg_ready = self.adopted = False
         self._host_steps = self.state.host_steps
-
-
-def lazy_hidden_why_not(defer, hops, post_relu=True, post_scale=None, head_stats=True):
-    """Why the gradient of a hidden activation cannot be left to the producing layer's backward kernel
-    (acm_conv_agg_bwd_t.proj_*) -- None: it can.  The ONE statement of the rule: the consuming layer decides with it whether
-    to go lazy (_AcmLiteral: its own two arguments), the producing layer whether it may leave the activation unwritten, which
-    only the lazy backward can do without it (_AcmAggFirst: with its post-op and head statistics as well)."""
-    if defer is None:
-        return "no deferral list (CallContext.defer): the following layer materialises its input gradient"
-    if int(hops) != 1:
-        return "k-hop operators"
-    if not post_relu:
-        return "no fused ReLU behind the layer"
-    if post_scale is not None:
-        return "a post_scale mask tensor"
-    if not head_stats:
-        return "no head statistics (no gradient is asked of the layer)"
-    return None
-
-
-def hidden_elision_why_not(call, nxt, agg_given, sharded, needs_grad, hops, post_relu, post_scale, head_stats, f, query):
-    """Why an aggregate-first layer stores its output although only the following layer consumes it -- None: it may stay
-    unwritten.  ``nxt``: the projection request its epilogue carries (_next_proj_request); ``query(proj_f)``: the library's
-    answer (acm_conv_agg_out_optional), or None where it lacks the symbol."""
-    if not tuning.HOST.elide_hidden:
-        return "tuning: elide_hidden=0"
-    if not call.next_private:
-        return "the model did not promise that only the following layer reads the hidden activation"
-    if query is None:
-        return "library has no query symbol (acm_conv_agg_out_optional)"
-    if nxt is None:
-        return "the following layer's projection does not ride this layer's epilogue"
-    if not agg_given:
-        return "the row-local stage is not a launch of its own (no P = A_low X at hand)"
-    if sharded:
-        return "row-sharded operators"
-    if 0 < tuning.HOST.csr_features <= f:
-        return "tuning: csr_features would count the hidden activation's zeros"
-    if needs_grad:
-        why = lazy_hidden_why_not(call.defer, hops, post_relu, post_scale, head_stats)
-        if why is not None:
-            return why
-    if not query(nxt[2] if needs_grad else 0):
-        return "the library declines these shapes (acm_conv_agg_out_optional)"
-    return None
-
-
-class HiddenToken:
-    """A hidden activation its layer left unwritten (acm_conv_agg_fwd_t.out == NULL): the tensor the layer returned is an
-    identity token for pre_proj / hidden_private, and this object is the one place that knows whether its bytes exist
-    (``written``) and how to make them (``write``).  The producing layer's ctx, the call context (``CallContext.elided``, for
-    the length of the model call) and the consuming layer's ctx hold it; it holds the token weakly and nothing of theirs, so it
-    closes no reference cycle (a cycle would keep the step's tensors and operators for the cyclic collector, which may then
-    free them in the middle of a later stream capture)."""
-    __slots__ = ("written", "_launch", "_token", "_fresh")
-
-    def __init__(self, token, launch):
-        import weakref
-        self.written, self._launch, self._token, self._fresh = False, launch, weakref.ref(token), None
-
-    def names(self, x):
-        """``x`` is the unwritten token (the object, or a tensor over the same memory)."""
-        tok = self._token()
-        return (not self.written and tok is not None and isinstance(x, torch.Tensor)
-                and (x is tok or (x.data_ptr() == tok.data_ptr() and x.shape == tok.shape)))
-
-    def write(self, into=None):
-        """The row, written now unless it has been: into ``into`` (a tensor over the token's memory), else into the token while
-        it is alive, else into a fresh tensor.  Returns the tensor that holds it (None: written once into a token that is gone)."""
-        if not self.written:
-            out = into if into is not None else self._token()
-            if out is None:
-                out = self._fresh = self._launch.fresh()
-            self._launch(out)
-            self.written, self._launch = True, None
-            return out
-        return into if into is not None else (self._token() if self._token() is not None else self._fresh)
-
-
-def hidden_token_of(call, x):
-    """call.elided if ``x`` is the unwritten output it stands for, else None."""
-    tok = getattr(call, "elided", None) if call is not None else None
-    return tok if (tok is not None and tok.names(x)) else None
-
-
-def ensure_hidden_written(call, x):
-    """A consumer is about to read the bytes of ``x``: if it is a hidden activation its layer left unwritten, write it now."""
-    tok = hidden_token_of(call, x)
-    if tok is not None:
-        tok.write(x)
-
-
-def _next_proj_request(call, f, dev, row_local_only=False):
-    """(weights, relu_before, F') of the layer named in ``call.next_proj`` when its projection can ride this layer's epilogue.
-    Default: only where the row-local stage runs as its own kernel (``row_local_only``: P = A_low X is given -- the input
-    pipeline, evaluation passes -- and the sixteen-rows-per-wave kernel of acm_conv_agg16.hip carries the projection for
-    ~6 us against the ~20 us of a separate acm_proj_fwd launch); inside the fused gather kernel it costs what it saves
-    (built, measured, removed)."""
-    nxt, call.next_proj = call.next_proj, None
-    if nxt is None or not row_local_only or not (tuning.kernel()["rows16"] & tuning.ROWS16_EPI):
-        return None
-    try:
-        w3 = (nxt.weight_low, nxt.weight_high, nxt.weight_mlp)
-        cfg = nxt._config()
-    except AttributeError:
-        return None
-    f2 = w3[0].shape[1]
-    ok = (f2 <= 2 and all(w.dtype == _F32 and w.is_contiguous() and w.device == dev and
-                                                   tuple(w.shape) == (f, f2) for w in w3))
-    # (a four-channel two-column consumer gathers [Z_L | Z_H | struc_low] from packed 32-byte rows: _narrow_tables)
-    return (w3, bool(cfg.relu_before), f2, cfg.n_channels == 4 and f2 == 2) if ok else None
-
-
-def _take_pre_proj(call, x, w3, relu):
-    """The projection a preceding layer of the same model call left for (x, w3, relu), or None."""
-    pre, call.pre_proj = call.pre_proj, None
-    if pre is None or not isinstance(x, torch.Tensor):
-        return None
-    out, zlh, zi, ptrs, prelu = pre
-    if (x.data_ptr() == out.data_ptr() and x.shape == out.shape and x.stride() == out.stride() and prelu == bool(relu)
-            and tuple(w.data_ptr() for w in w3) == ptrs):
-        return zlh, zi
-    return None

@@ -4,7 +4,8 @@ import torch
 
 from .. import tuning
 from ..graph import SparseFeatures
-from ._context import _call_or_ambient, _run, ensure_hidden_written
+from ._context import _call_or_ambient, _run
+from ._hidden import ensure_hidden_written
 from .blocks import project_blocks
 from ._conv_shared import PROJECTED, _chan_block
 from ._launch import _F32

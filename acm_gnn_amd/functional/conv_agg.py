@@ -6,7 +6,8 @@ import torch
 
 from .. import _lib, tuning
 from .. import functional as _pkg
-from ._context import HiddenToken, _call_or_ambient, _next_proj_request, hidden_elision_why_not
+from ._context import _call_or_ambient
+from ._hidden import HiddenToken, PreProj, hidden_elision_why_not
 from ._conv_shared import _NO_GRADS, _conv_prologue, _flat_views, _gathered_input, _grads, _head_params, _k3_setup, \
     _narrow_tables, _pack_head, _reduce_replicated, _set_head, _set_post, _struc_grad, _struc_rows, _unpack_head
 from ._launch import EUNSUPPORTED, _F32, _as_f32c, _vp, _workspace, launch
@@ -23,7 +24,7 @@ def _out_optional_query(p, n):
 
 class _WriteOut:
     """What writes a hidden activation its forward left unwritten, should a consumer turn out to need its bytes
-    (_context.HiddenToken): one more launch of the row-local stage over the rows the forward worked on -- ``xs`` / ``agg``, the
+    (_hidden.HiddenToken): one more launch of the row-local stage over the rows the forward worked on -- ``xs`` / ``agg``, the
     copies it left for the backward -- with only ``out`` requested.  The post-op's counter does not move between a step's
     forward and its backward, so the mask and every bit are the forward's."""
 
@@ -63,7 +64,7 @@ class _AcmAggFirst(torch.autograd.Function):
                 agg_holder, in_drop, pregathered):
         x = _conv_prologue(ctx, x, w_low, ops, post_relu, post_scale, post_drop, call, in_drop)
         call = ctx.call
-        ctx.agg_first = True                      # what a following layer's lazy input gradient looks for (_AcmLiteral)
+        link = ctx.link = call.link if (call.link is not None and not call.link.sealed) else None     # the HiddenLink it produces for
         dev, n = x.device, x.shape[0]
         f_in, f = w_low.shape
         k = cfg.n_channels
@@ -118,15 +119,17 @@ class _AcmAggFirst(torch.autograd.Function):
             p.head_stats, p.ld_head_stats = stats.data_ptr(), stats.stride(0)
         ctx.head_stats = stats
         # (the row-local stage is a kernel of its own when P is given, and always with the structure channel)
-        nxt = _next_proj_request(call, f, dev, row_local_only=f == 64 and (agg_given is not None or four))
+        nxt = link.take_request(f, dev, f == 64 and (agg_given is not None or four)) if link is not None else None
+        pre = None
         if nxt is not None:
-            n_w3, n_relu, f2, n_pack = nxt
-            n_zlh, _ = _narrow_tables(n, f2, f2, dev, n_pack)
+            f2 = nxt.f2
+            n_zlh, _ = _narrow_tables(n, f2, f2, dev, nxt.pack4)
             n_zi = torch.empty(n, f2, dtype=_F32, device=dev)
-            p.next_w_low, p.next_w_high, p.next_w_mlp = (w.data_ptr() for w in n_w3)
-            p.next_ld_w, p.next_f, p.next_relu = n_w3[0].stride(0), f2, int(n_relu)
+            p.next_w_low, p.next_w_high, p.next_w_mlp = ptrs = tuple(w.data_ptr() for w in nxt.w3)
+            p.next_ld_w, p.next_f, p.next_relu = nxt.w3[0].stride(0), f2, int(nxt.relu)
             p.next_zlh, p.ld_next_zlh = n_zlh.data_ptr(), n_zlh.stride(0)
             p.next_zi, p.ld_next_zi = n_zi.data_ptr(), n_zi.stride(0)
+            pre = PreProj(n_zlh, n_zi, ptrs, nxt.relu)
         # the output stays unwritten where only the following layer consumes it and does so through next_zlh / next_zi
         # (forward) and this layer's own backward kernel (acm_conv_agg_bwd_t.proj_*): decided here, before the launch
         # (a backward may follow: the caller's grad mode as acm_conv saw it -- in here gradients are always switched off)
@@ -135,8 +138,7 @@ class _AcmAggFirst(torch.autograd.Function):
                                      int(getattr(ops, "hops", 1)), ctx.post_relu, ctx.post_scale, stats is not None, f,
                                      _out_optional_query(p, n))
         call.elision = (why is None, why)
-        ctx.out_elided = why is None
-        if ctx.out_elided:
+        if why is None:
             p.out = None
         ws = ops.low.workspace(max(fp, f) if four else fp)
         launch("acm_conv_agg_fwd", f"conv_agg_{'epi' if agg_given is not None else 'fwd'}/F{f}k{k}i{f_in}", dev, ops.low.handle, C.byref(p),
@@ -145,20 +147,20 @@ class _AcmAggFirst(torch.autograd.Function):
             ctx.pipe.next_table_ready = True
         if agg_holder is not None and agg_given is None:
             agg_holder["agg"] = agg
-        if nxt is not None:
-            call.pre_proj = (out, n_zlh, n_zi, tuple(w.data_ptr() for w in n_w3), n_relu)
         ctx.ops, ctx.cfg, ctx.f_in = ops, cfg, f_in
         # with a fused ReLU the output itself records which elements the post-op let through: the backward reads it
         # instead of regenerating the dropout mask (no extra memory: the next layer keeps the same tensor alive)
-        # (an unwritten output is an identity token for pre_proj / hidden_private only: not saved, never read -- ctx.elide, its
-        #  HiddenToken, writes it for a consumer that needs its bytes after all)
-        ctx.out_mask = bool(ctx.post_relu) and ctx.post_scale is None and not ctx.out_elided
+        # (an unwritten output is an identity token only: not saved, never read -- the link's HiddenToken writes it for a
+        #  consumer that needs its bytes after all)
+        ctx.out_mask = bool(ctx.post_relu) and ctx.post_scale is None and why is not None
         if ctx.pipe is not None:
             xpad, agg = ctx.pipe.saved[0], ctx.pipe.saved[1]
-        ctx.elide = None
-        if ctx.out_elided:
-            call.elided = ctx.elide = HiddenToken(out, _WriteOut(p, ops.low, (n, f), f"conv_agg_out/F{f}k{k}i{f_in}", dev, xpad, agg,
-                                                                 (wl, wh, wm, mix, *vecs, *lnw, *lnb, ctx.post_drop)))
+        if link is not None:
+            token = None
+            if why is None:
+                token = HiddenToken(out, _WriteOut(p, ops.low, (n, f), f"conv_agg_out/F{f}k{k}i{f_in}", dev, xpad, agg,
+                                                   (wl, wh, wm, mix, *vecs, *lnw, *lnb, ctx.post_drop)))
+            link.produced(out, will_backward, pre, token)
         ctx.save_for_backward(xpad, agg, wl, wh, wm, *_pack_head(vecs, lnw, lnb, mix), *extra, *((out,) if ctx.out_mask else ()))
         ctx.mark_non_differentiable(att)
         return out, att
@@ -181,14 +183,15 @@ class _AcmAggFirst(torch.autograd.Function):
         vecs, lnw, lnb, mix = _unpack_head(saved, cfg, 5)
         dev = xpad.device
         n, f, fp = xpad.shape[0], wl.shape[1], xpad.shape[1]
-        lazy, ctx.lazy = getattr(ctx, "lazy", None), None
-        if lazy is not None and (grad_out is not lazy["placeholder"] and grad_out.data_ptr() != lazy["placeholder"].data_ptr()):
-            raise RuntimeError("acm_conv: the hidden activation marked private (CallContext.hidden_private) received a gradient "
+        link = ctx.link
+        lazy = link.take_lazy() if link is not None else None
+        if lazy is not None and (grad_out is not lazy.placeholder and grad_out.data_ptr() != lazy.placeholder.data_ptr()):
+            raise RuntimeError("acm_conv: the hidden activation marked private (HiddenLink.grad_private) received a gradient "
                                "from somewhere else as well")
-        elide = getattr(ctx, "elide", None)                     # the HiddenToken of an `out` the forward left unwritten
+        elide = link.token if link is not None else None        # the HiddenToken of an `out` the forward left unwritten
         elided = elide is not None and not elide.written        # ... and nobody has written since
         defer = ctx.call.defer
-        token_x = lazy["x"] if lazy is not None else None       # (the token itself, where the following layer handed it back)
+        token_x = lazy.x if lazy is not None else None          # (the token itself, where the following layer handed it back)
         if elide is not None and not elided:              # a consumer asked for its bytes in the meantime: read like a stored one
             out_fwd = elide.write(token_x)
         fuse_proj = (lazy is not None and fp == 8 and f == 64 and (out_fwd is not None or elided) and ctx.post_scale is None
@@ -196,7 +199,7 @@ class _AcmAggFirst(torch.autograd.Function):
         if elided and not fuse_proj:                      # no kernel here forms the row again: written now, the mask is read
             out_fwd, elided = elide.write(token_x), False
         if lazy is not None and not fuse_proj:            # the kernel cannot take it: materialise dX and dW' now
-            proj_bwd(lazy["x"], lazy["dz"], lazy["w3"], lazy["d_w"], defer=defer, dx_out=lazy["placeholder"])
+            proj_bwd(lazy.x, lazy.dz, lazy.w3, lazy.d_w, defer=defer, dx_out=lazy.placeholder)
             lazy = None
         grad_out = _as_f32c(grad_out, "grad_out")
         # [dW_L | dW_H | dW_I | d att_vec | d LayerNorm weights | biases | d att_mix] (the LayerNorm parts whether used or not)
@@ -207,12 +210,12 @@ class _AcmAggFirst(torch.autograd.Function):
         _set_head(q, cfg, vecs, lnw, lnb, mix)
         q.grad_out, q.ld_grad_out = grad_out.data_ptr(), grad_out.stride(0)
         if lazy is not None:                              # the following layer's projection backward rides this launch
-            dz2, w32 = lazy["dz"], lazy["w3"]
+            dz2, w32 = lazy.dz, lazy.w3
             q.grad_out = None
             q.proj_dz, q.ld_proj_dz = dz2.data_ptr(), dz2.stride(0)
             q.proj_w_low, q.proj_w_high, q.proj_w_mlp = (w.data_ptr() for w in w32)
             q.proj_ld_w, q.proj_f = w32[0].stride(0), w32[0].shape[1]
-            q.proj_d_w = lazy["d_w"].data_ptr()
+            q.proj_d_w = lazy.d_w.data_ptr()
         q.agg, q.ld_agg = agg.data_ptr(), agg.stride(0)
         if ctx.head_stats is not None:
             q.head_stats, q.ld_head_stats = ctx.head_stats.data_ptr(), ctx.head_stats.stride(0)
@@ -246,7 +249,7 @@ class _AcmAggFirst(torch.autograd.Function):
                 out_fwd, elided = elide.write(token_x), False
                 q.out, q.ld_out = out_fwd.data_ptr(), out_fwd.stride(0)
             if lazy is not None:
-                proj_bwd(lazy["x"], lazy["dz"], lazy["w3"], lazy["d_w"], defer=defer, dx_out=lazy["placeholder"])
+                proj_bwd(lazy.x, lazy.dz, lazy.w3, lazy.d_w, defer=defer, dx_out=lazy.placeholder)
                 q.grad_out, q.proj_dz, lazy = grad_out.data_ptr(), None, None
             if carry:                                     # the gather as its own launch, right here: the pipeline stays valid
                 q.next_a, q.next_xg, q.next_row_scale, q.next_agg = None, None, None, None          # (also inside a capture, where
@@ -255,8 +258,8 @@ class _AcmAggFirst(torch.autograd.Function):
         if carry:
             pipe.next_agg_ready = True
         if defer is not None:
-            defer.hold(ws, [d_params] + ([lazy["d_w"]] if lazy is not None else []),
-                       keep=[d_params] + ([lazy["d_w"]._base if lazy["d_w"]._base is not None else lazy["d_w"]] if lazy is not None else []))
+            defer.hold(ws, [d_params] + ([lazy.d_w] if lazy is not None else []),
+                       keep=[d_params] + ([lazy.d_w._base if lazy.d_w._base is not None else lazy.d_w] if lazy is not None else []))
         d_struc = _struc_grad(ops, cfg, gs) if four else None
         _reduce_replicated(d_params, ops, defer)
         d_w = d_params[:nw].view(3, f_in, f)
@@ -319,7 +322,8 @@ class _AcmAggWide(torch.autograd.Function):
                 agg_holder, in_drop, pregathered):
         ctx.set_materialize_grads(False)
         call = ctx.call = _call_or_ambient(call)
-        call.next_proj = None                      # (the narrow projection hand-off rides the f_pad <= 16 kernels only)
+        if call.link is not None:                  # consumed unheard: the narrow projection rides the f_pad <= 16 kernels only
+            call.link.take_request(0, None)
         x = _as_f32c(x, "input")
         dev = x.device
         n, f_in = x.shape

@@ -7,7 +7,7 @@ import torch
 from .. import _lib, tuning
 from .. import functional as _pkg
 from ..graph import SparseFeatures
-from ._context import _current_tape, _take_pre_proj, ensure_hidden_written, hidden_token_of, lazy_hidden_why_not
+from ._hidden import LazyGrad, ensure_hidden_written, lazy_hidden_why_not
 from ._conv_shared import _NO_GRADS, _chan_block, _conv_prologue, _flat_views, _gathered_input, _grads, _head_params, _hop_buffer, \
     _k3_setup, _low_product, _narrow_tables, _pack_head, _reduce_replicated, _set_head, _set_post, _struc_grad, _struc_rows, \
     _unpack_head, _z_pitch, PROJECTED
@@ -40,7 +40,7 @@ def _literal_project(ctx, x, w3, ops, cfg):
     # Row pitch of Z: for narrow layers the gathered block [Z_L | Z_H] (2F floats) must be
     # one aligned vector fetch, so rows are padded to a multiple of that block.
     ldz = _z_pitch(f, fb)
-    pre = _take_pre_proj(call, x, w3, cfg.relu_before) if use_proj else None
+    pre = call.link.take_pre(x, w3, cfg.relu_before) if (use_proj and call.link is not None) else None
     if pre is None and not sparse_x:              # this layer projects x itself: a hidden activation left unwritten is written first
         ensure_hidden_written(call, x)
     drop_spec = _drop_spec(ctx.in_drop, ops.row_offset) if ctx.in_drop is not None else None
@@ -234,33 +234,22 @@ class _AcmLiteral(torch.autograd.Function):
             launch("acm_conv_fwd", f"conv_fwd/F{f}k{k}", dev, graph.handle, C.byref(p), _vp(ws), ws.numel() * 4)
         ctx.ops, ctx.cfg = ops, cfg
         ctx.sparse_x = x if sparse_x else None
-        # Lazy input gradient: when the input IS the output tensor of an aggregate-first layer of the same model call and
-        # the model vouches that nothing else consumes it (call.hidden_private), this layer's backward may hand
-        # dX = dZ Wcat^T and dW = X^T dZ to that layer's backward kernel (acm_conv_agg_bwd_t.proj_*) instead of running
-        # acm_proj_bwd: the [n, F] gradient then never exists in memory.
-        # ONLY under a deferral list (call.defer): this layer's dW' is then written by a LATER kernel than the one this
-        # backward returns from -- exactly the contract of DeferredReductions ("every .grad is undefined until the flush";
-        # the loop that owns the step checks all_adopted() and flushes before anything reads a gradient).  Without one,
-        # autograd's AccumulateGrad may ADD the still unwritten dW' to an existing .grad right behind this node
-        # (zero_grad(set_to_none=False), gradient accumulation, hooks), or the producer's backward may never run
-        # (torch.autograd.grad on a subset): the plain GCN API therefore materialises dX and dW' here.
-        ctx.lazy_producer = None
-        tape = _current_tape()
-        prod = (getattr(x, "grad_fn", None) or (tape.producer(x) if tape is not None else None)) if not sparse_x else None
-        if (call.hidden_private is x and prod is not None and getattr(prod, "agg_first", False) and getattr(prod, "call", None) is call
-                and not zero_padded and lazy_hidden_why_not(call.defer, hops) is None):
-            ctx.lazy_producer = prod
-        # an input its layer left unwritten (CallContext.elided): only the lazy backward does without its bytes -- a layer that
-        # will not go lazy writes it now (the backward's acm_proj_bwd / acm_gemm reads x); one that means to keeps the means to
-        # write it should its backward take another branch after all
-        ctx.unwritten_x = None
-        tok = hidden_token_of(call, x) if not sparse_x else None
-        if tok is not None:
-            # (call.grad_enabled: the caller's grad mode, acm_conv -- a forward under no_grad has no backward to read x)
-            if ctx.lazy_producer is None and any(ctx.needs_input_grad) and call.grad_enabled:
-                ensure_hidden_written(call, x)
-            else:
-                ctx.unwritten_x = tok
+        # Lazy input gradient: when the input IS the output of an aggregate-first layer of the same model call and the model
+        # vouches that nothing else consumes it (the call's HiddenLink), this layer's backward may hand dX = dZ Wcat^T and
+        # dW = X^T dZ to that layer's backward kernel (acm_conv_agg_bwd_t.proj_*) instead of running acm_proj_bwd: the [n, F]
+        # gradient then never exists in memory.  The ctx keeps the link only where ``x`` is its activation.
+        link = None if sparse_x else call.link
+        lazy = (link is not None and link.carries_gradient_of(x) and not zero_padded
+                and lazy_hidden_why_not(call.defer, hops) is None)
+        if lazy:
+            link.lazy_agreed = True
+        # left unwritten: only the lazy backward does without its bytes -- a layer that will not go lazy writes it now (the
+        # backward's acm_proj_bwd / acm_gemm reads x); one that means to keeps the link, to write it should its backward take
+        # another branch after all (call.grad_enabled: a forward under no_grad has no backward to read x)
+        unwritten = link is not None and link.unwritten(x)
+        if unwritten and not lazy and any(ctx.needs_input_grad) and call.grad_enabled:
+            link.ensure_written(x)
+        ctx.link = link if (lazy or unwritten) else None
         ctx.save_for_backward(w3[0] if sparse_x else x, *w3, zlh, zi, pre, *_pack_head(vecs, lnw, lnb, mix))
         ctx.mark_non_differentiable(att)
         return out, att
@@ -318,11 +307,10 @@ def _fwd_tail(ctx, ops, cfg, graph, p, ws, tail_req, w3, pre, zi, vecs, lnw, lnb
     return st
 
 
-def _write_unwritten_x(ctx, x):
-    """The backward is about to read x: a hidden activation its layer left unwritten (ctx.unwritten_x) is written first."""
-    tok = getattr(ctx, "unwritten_x", None)
-    if tok is not None and not tok.written:
-        tok.write(x)
+def _ensure_x_written(ctx, x):
+    """The backward is about to read x: a hidden activation its layer left unwritten (ctx.link) is written first."""
+    if getattr(ctx, "link", None) is not None:
+        ctx.link.ensure_written(x)
 
 
 def _k3_backward(ctx, grad_out):
@@ -455,17 +443,17 @@ def _literal_backward(ctx, grad_out):
     elif (ctx.needs_input_grad[0] and proj_bwd_supported(3 * f)
           and w3[0].stride(0) == w3[1].stride(0) == w3[2].stride(0)):
         d_wcat = flat[:nw].view(3, f_in_w, f)                             # narrow output layer: dX and dW in one
-        prod = getattr(ctx, "lazy_producer", None)
-        if (prod is not None and f <= 2 and f_in_w == 64 and x.shape[1] == 64 and getattr(prod, "lazy", None) is None
+        link = getattr(ctx, "link", None)
+        if (link is not None and link.awaits_lazy() and f <= 2 and f_in_w == 64 and x.shape[1] == 64
                 and all(w.stride(0) == f and w.is_contiguous() for w in w3)):
             # ... left to the producing layer's backward kernel: the placeholder is what autograd carries there
             d_x = torch.empty(n, x.shape[1], dtype=_F32, device=dev)
-            prod.lazy = dict(dz=dz, w3=w3, d_w=d_wcat, x=x, placeholder=d_x)
+            link.lazy = LazyGrad(dz, w3, d_wcat, x, d_x)
         else:
-            _write_unwritten_x(ctx, x)
+            _ensure_x_written(ctx, x)
             d_x = proj_bwd(x, dz, w3, d_wcat, defer=defer)                # pass over x (acm_proj_bwd)
     else:
-        _write_unwritten_x(ctx, x)
+        _ensure_x_written(ctx, x)
         d_wcat = gemm(x, dz, trans_a=True, col_blocks=3,
                       out=flat[:nw].view(3, f_in_w, f),                   # contiguous per weight
                       a_drop=_drop_spec(ctx.in_drop, ops.row_offset) if getattr(ctx, "in_drop_used", False) else None)

@@ -155,28 +155,37 @@ class GCN(nn.Module):
             # (piped: x is the pipeline's table, which the first layer's forward below refills for the next step)
             xx = self._residual(x, adj_low, drop=(p, 2, st, off), call=call,
                                 pipe=call.pipe if (not isinstance(x, SparseFeatures) and piped) else None)
-        # the output layer's narrow projection may ride the hidden layer's epilogue (CallContext.next_proj / pre_proj); not
-        # with the ACM-GCN++ residual, which changes the hidden activations in between
-        call.next_proj = self.gcns[1] if self.model_type != "acmgcnpp" else None
-        call.next_private = self._hidden_is_private()
-        fea = self.gcns[0](x, adj_low, adj_high, adj_low_unnormalized, post_relu=True, post_drop=(p, 1, st), **kw,
-                           rows_permuted=self._rows_permuted, call=call)
-        call.next_proj, call.next_private = None, False
-        if add_fused:
+        def add_residual(fea):
             ops_ = adj_low if isinstance(adj_low, FilterOperators) else None
             xr = x
             if call.pipe is not None and x.data_ptr() == call.pipe.local_table().data_ptr() and call.pipe.adopted:
                 xr = call.pipe.saved[0]        # the table holds step t + 1's rows by now: this step's are in the saved copy
-            fea = AF.residual_add_linear(fea, xr, lin.weight, lin.bias, relu=True, drop=(p, 2, st, off),
-                                         group=ops_.group if (ops_ is not None and ops_.sharded) else None, call=call)
-        elif self.model_type == "acmgcnpp":
-            fea = fea + xx
-        else:
-            call.hidden_private = fea          # consumed by the output layer only: its gradient may stay implicit
+            return AF.residual_add_linear(fea, xr, lin.weight, lin.bias, relu=True, drop=(p, 2, st, off),
+                                          group=ops_.group if (ops_ is not None and ops_.sharded) else None, call=call)
+
+        between = add_residual if add_fused else (lambda fea: fea + xx) if self.model_type == "acmgcnpp" else None
+        return self._two_layers(x, adj_low, adj_high, adj_low_unnormalized, call, between, post_drop=(p, 1, st), **kw)
+
+    def _two_layers(self, x, adj_low, adj_high, adj_low_unnormalized, call, between, **layer0):
+        """The tail of both two-layer forwards: layer 0 with its fused ReLU and post-op (``layer0``: post_scale / post_drop /
+        input_drop), ``between(fea)`` (the ACM-GCN++ residual, or None), layer 1.  Without a residual -- it changes the hidden
+        activations in between -- the two layers share a functional.HiddenLink for the length of this section: the output
+        layer's narrow projection may ride the hidden layer's epilogue, its input gradient that layer's backward kernel, and
+        (``_hidden_is_private``) the activation may stay unwritten."""
+        link = None
+        if self.model_type != "acmgcnpp":
+            link = AF.HiddenLink(self.gcns[1], grad_private=True, bytes_private=self._hidden_is_private())
+        call.link = link
         try:
+            fea = self.gcns[0](x, adj_low, adj_high, adj_low_unnormalized, post_relu=True, **layer0,
+                               rows_permuted=self._rows_permuted, call=call)
+            if link is not None:
+                link.seal()
+            if between is not None:
+                fea = between(fea)
             return self.gcns[1](fea, adj_low, adj_high, adj_low_unnormalized, rows_permuted=self._rows_permuted, call=call)
         finally:
-            call.hidden_private = call.elided = None
+            call.link = None
 
     def _forward_snowball(self, x, adj_low, adj_high, fused, call):
         """models.py:57-64: h_k = dropout(relu(layer_k([x | h_0 | ... | h_{k-1}]))), out = layer_last([x | h_0 | ...]).
@@ -214,7 +223,7 @@ class GCN(nn.Module):
         return self.gcns[-1](cat(blocks), adj_low, adj_high, None, rows_permuted=self._rows_permuted, call=call)
 
     def _hidden_is_private(self):
-        """The promise CallContext.next_private makes before the hidden layer runs: its output goes to the output layer and
+        """The promise HiddenLink.bytes_private makes before the hidden layer runs: its output goes to the output layer and
         nowhere else -- the two-layer models without the ACM-GCN++ residual (which adds to it), no forward hook on either
         layer that could look at it, and neither layer's ``forward`` replaced on the instance or in a subclass (a wrapper
         could read its input).  The hidden layer may then leave the tensor unwritten (functional: hidden elision).  The hook
@@ -296,16 +305,5 @@ class GCN(nn.Module):
         if self.training and self.dropout > 0:
             ones = self._ones_like_hidden(x.shape[0], self.gcns[0].out_features, x.device)
             scale = drop(ones)
-        call.next_proj = self.gcns[1] if self.model_type != "acmgcnpp" else None     # see _forward_fused_dropout
-        call.next_private = self._hidden_is_private()
-        fea = self.gcns[0](x, adj_low, adj_high, adj_low_unnormalized, post_relu=True, post_scale=scale,
-                           rows_permuted=self._rows_permuted, call=call)
-        call.next_proj, call.next_private = None, False
-        if self.model_type == "acmgcnpp":
-            fea = fea + xx
-        else:
-            call.hidden_private = fea          # see _forward_fused_dropout
-        try:
-            return self.gcns[1](fea, adj_low, adj_high, adj_low_unnormalized, rows_permuted=self._rows_permuted, call=call)
-        finally:
-            call.hidden_private = call.elided = None
+        between = (lambda fea: fea + xx) if self.model_type == "acmgcnpp" else None
+        return self._two_layers(x, adj_low, adj_high, adj_low_unnormalized, call, between, post_scale=scale)

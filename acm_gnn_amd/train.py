@@ -120,6 +120,12 @@ def _warm_up(fn, times):
     torch.cuda.synchronize()
 
 
+def _note_elision(step, call):
+    """``step.hidden_elided`` / ``hidden_elided_refused`` (TrainStep, EvalStep) from what the model call's hidden layer reported."""
+    done, why = call.elision if call.elision is not None else (False, "no aggregate-first hidden layer ran with this call")
+    step.hidden_elided, step.hidden_elided_refused = bool(done), why
+
+
 class TrainStep:
     def __init__(self, model, optimizer, x, adj, labels, weights, adj_high=None, adj_un=None, use_graph=False,
                  fused_dropout=None, pipeline_input=None, steps_per_graph=1, flush_in_optimizer=True, small_step=None, tape=True,
@@ -387,7 +393,7 @@ class TrainStep:
             with AF.deferred_reductions_as(call.defer), AF.input_pipeline(call.pipe), tail:
                 out = self.model(self.x, self.adj, self.adj_high, self.adj_un, **kw)
         call.tail = None
-        self._note_elision(call)
+        _note_elision(self, call)
         if tail.matches(out):
             return tail.loss, tail.dz, out
         loss, dz = AF.nll_loss_and_grad(out, self.labels, self.weights, defer=call.defer)   # = masked_nll(...).backward(), two launches less
@@ -403,13 +409,9 @@ class TrainStep:
         else:
             with AF.deferred_reductions_as(call.defer), AF.input_pipeline(call.pipe):
                 out = self.model(self.x, self.adj, self.adj_high, self.adj_un, **kw)
-        self._note_elision(call)
+        _note_elision(self, call)
         loss, dz = AF.bce_loss_and_grad(out, self.labels, self.weights, defer=call.defer)
         return loss, dz, out
-
-    def _note_elision(self, call):
-        done, why = call.elision if call.elision is not None else (False, "no aggregate-first hidden layer ran with this call")
-        self.hidden_elided, self.hidden_elided_refused = bool(done), why
 
     def _eager(self):
         if not self.model.training:
@@ -669,8 +671,7 @@ class EvalStep:
         elif self._takes_call:
             call = AF.CallContext.from_ambient()         # (what the model would make itself: here to read what the layers report)
             out = self.model(self.x, self.adj, self.adj_high, self.adj_un, call=call)
-            done, why = call.elision if call.elision is not None else (False, "no aggregate-first hidden layer ran with this call")
-            self.hidden_elided, self.hidden_elided_refused = bool(done), why
+            _note_elision(self, call)
         else:
             out = self.model(self.x, self.adj, self.adj_high, self.adj_un)
         if self.metric == "rocauc" or self.criterion == "bce":

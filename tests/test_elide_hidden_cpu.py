@@ -1,9 +1,11 @@
 """The unwritten hidden activation (tuning key ``elide_hidden``) without a GPU: the one predicate the hidden layer and the
-layer behind it decide by, and the test double -- which lacks acm_conv_agg_out_optional -- training exactly as before."""
+layer behind it decide by, the test double -- which lacks acm_conv_agg_out_optional -- training exactly as before, and, with
+the add-on that has the symbol (tests/fake_lib_elide.py), the eliding branch of the host code and the launches of a warm step."""
 import os
 import sys
 
 import numpy as np
+import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -66,12 +68,12 @@ def test_shared_lazy_and_elide_predicates():
 
     asked = []
     yes = lambda pf: (asked.append(pf), True)[1]                     # noqa: E731
-    nxt = ((None, None, None), False, 2, False)
+    nxt = AF.ProjRequest((None, None, None), False, 2, False)
 
     def why(defer=d, promise=True, nxt=nxt, agg_given=True, sharded=False, grad=True, hops=1, relu=True, scale=None, stats=True,
             f=64, query=yes):
         call = AF.CallContext(defer=defer)
-        call.next_private = promise
+        call.link = AF.HiddenLink(bytes_private=promise)
         return AF.hidden_elision_why_not(call, nxt, agg_given, sharded, grad, hops, relu, scale, stats, f, query)
 
     assert why() is None and asked == [2]                            # a training step asks about both halves ...
@@ -111,7 +113,8 @@ def test_an_unwritten_token_is_written_once_for_whoever_asks():
     call = AF.CallContext()
     token, other, launch = torch.zeros(3, 2), torch.zeros(3, 2), Launch()
     log = launch.log
-    call.elided = tok = AF.HiddenToken(token, launch)
+    call.link = AF.HiddenLink()
+    call.link.token = tok = AF.HiddenToken(token, launch)
     AF.ensure_hidden_written(call, other)
     AF.ensure_hidden_written(call, None)
     AF.ensure_hidden_written(None, token)
@@ -154,18 +157,22 @@ def test_the_model_promises_only_for_untouched_layers():
     assert not GCN(7, 64, 2, 2, 50, 0.0, "acmgcnpp", 0)._hidden_is_private()
 
 
-def _setup(seed=3):
+def _setup(seed=3, dropout=0.0, model_type="acmgcnp", pattern_only=False, **model_kw):
     from acm_gnn_amd import GCN, data as D
     from acm_gnn_amd.graph import CsrGraph, FilterOperators
     adj, _, y_np, _, _ = D.synthetic_dataset("tiny", seed=seed)
-    low, _ = D.build_filters(adj)
-    ops = FilterOperators(CsrGraph.from_scipy(low, "cpu"))
+    low, deg = D.build_filters(adj)
+    if pattern_only:                             # (the operators the input pipeline takes: the pattern and a row scale)
+        from acm_gnn_amd.distributed import make_sharded_operators
+        ops = make_sharded_operators(low, deg, torch.device("cpu"))
+    else:
+        ops = FilterOperators(CsrGraph.from_scipy(low, "cpu"))
     n = adj.shape[0]
     x = torch.randn(n, 7, generator=torch.Generator().manual_seed(seed))
     y = torch.from_numpy(y_np)
     w = torch.full((n,), 1.0 / n)
     torch.manual_seed(0)
-    model = GCN(7, 64, int(y.max()) + 1, 2, n, 0.0, "acmgcnp", 0)
+    model = GCN(7, 64, int(y.max()) + 1, 2, n, dropout, model_type, 0, **model_kw)
     return model, ops, x, y, w
 
 
@@ -190,3 +197,216 @@ def test_the_double_lacks_the_query_symbol_stores_the_row_and_trains_as_before(m
     assert outs and all(outs)                                        # every forward of the hidden layer was handed an `out`
     assert runs[1][0] == runs[0][0] and np.isfinite(runs[1][0]).all() and runs[1][0][-1] < runs[1][0][0]
     assert all(torch.equal(a, b) for a, b in zip(runs[1][1], runs[0][1])) and torch.equal(runs[1][2], runs[0][2])
+
+
+# ---- the eliding branch of the host code on the double (tests/fake_lib_elide.py) ------------------------------------------
+_RIDERS = {"acm_conv_agg_fwd": ("out", "next_zlh", "agg_copy", "next_x"), "acm_conv_agg_bwd": ("out", "grad_out", "proj_dz", "next_agg")}
+_NO_COMPUTE = ("acm_version", "acm_last_error", "acm_tuning_get", "acm_tuning_set")
+
+
+class _Calls:
+    """A recording wrapper around the double: the ``acm_*`` compute entry points it receives, in order (workspace and info
+    queries left out) -- the two gradient-carrying calls of the hidden layer as (name, the optional riders that were non-NULL)
+    -- and, apart, the ``proj_f`` of every acm_conv_agg_out_optional question."""
+
+    def __init__(self, monkeypatch, fake):
+        self.log, self.asked = [], []
+        for name in dir(fake):
+            fn = getattr(fake, name)
+            if name.startswith("acm_") and callable(fn) and not name.endswith("_bytes") and not name.startswith("acm_csr_") \
+                    and name not in _NO_COMPUTE:
+                monkeypatch.setattr(fake, name, self._wrap(name, fn))
+
+    def _wrap(self, name, fn):
+        def call(*args):
+            if name == "acm_conv_agg_out_optional":
+                self.asked.append(int(args[2]))
+            elif name in _RIDERS:
+                self.log.append((name,) + tuple(r for r in _RIDERS[name] if getattr(args[1]._obj, r)))
+            else:
+                self.log.append(name)
+            return fn(*args)
+        return call
+
+    def clear(self):
+        del self.log[:], self.asked[:]
+
+    def of(self, name):
+        return [c for c in self.log if c[0] == name]
+
+
+def _headline_step(model_type="acmgcnp", **step_kw):
+    """The headline configuration on ``tiny``: counter-based dropout, the input pipeline on (P = A_low X is given, so the
+    row-local stage is a launch of its own), an eager step on the Tape."""
+    from acm_gnn_amd import FusedAdamW, functional as AF, train as T
+    model, ops, x, y, w = _setup(dropout=0.3, model_type=model_type, pattern_only=True, attn_layernorm=True)
+    model.dropout_state = AF.DropoutState("cpu", seed=3)
+    step = T.TrainStep(model, FusedAdamW(model.parameters(), lr=0.01), x, ops, y, w, small_step=False, tape=True, **step_kw)
+    return step, model, ops, x, y
+
+
+def _eval_step(model, ops, x, y):
+    from acm_gnn_amd import train as T
+    return T.EvalStep(model, x, ops, y, [torch.arange(0, x.shape[0], 2)], loss_set=0, small_step=False)
+
+
+def test_the_eliding_host_path_trains_and_evaluates_as_the_storing_one(monkeypatch):
+    """With the query symbol on the double the hidden layer's ``out`` stays NULL in the forward and in the backward that carries
+    the output layer's projection gradient; losses, parameters and evaluation logits equal the storing run's (elide_hidden=0)."""
+    import fake_lib_elide
+    from acm_gnn_amd import tuning
+    fake = fake_lib_elide.install(monkeypatch)
+    calls = _Calls(monkeypatch, fake)
+    runs = {}
+    for switch in (1, 0):
+        with tuning.override(elide_hidden=switch, pipeline=32):
+            step, model, ops, x, y = _headline_step()
+            assert step.pipe is not None
+            calls.clear()
+            losses = []
+            for _ in range(4):                                   # (the pipeline is primed inside the first step, before its forward)
+                losses.append(float(step()))
+                assert step.hidden_elided == bool(switch), step.hidden_elided_refused
+            assert step._tape is True
+            fwd, bwd = calls.of("acm_conv_agg_fwd"), calls.of("acm_conv_agg_bwd")
+            assert len(fwd) == len(bwd) == 4
+            if switch:
+                assert all("out" not in c and "next_zlh" in c for c in fwd) and calls.asked == [2] * 4
+                assert all("out" not in c and "proj_dz" in c for c in bwd)
+            else:
+                assert all("out" in c for c in fwd + bwd) and calls.asked == []
+                assert "elide_hidden=0" in step.hidden_elided_refused
+            ev = _eval_step(model, ops, x, y)
+            ev()                                                 # (the first pass over a static input leaves P for the next)
+            calls.clear()
+            logits = ev()[0].clone()
+            assert ev.hidden_elided == bool(switch), ev.hidden_elided_refused
+            assert [("out" in c) for c in calls.of("acm_conv_agg_fwd")] == [not switch] and calls.asked == ([0] if switch else [])
+            runs[switch] = (losses, [p.detach().clone() for p in model.parameters()], logits)
+    assert runs[1][0] == runs[0][0] and np.isfinite(runs[1][0]).all()
+    assert all(torch.equal(a, b) for a, b in zip(runs[1][1], runs[0][1])) and torch.equal(runs[1][2], runs[0][2])
+
+
+def test_a_reader_of_the_unwritten_row_has_it_written_once_and_the_step_keeps_its_bits(monkeypatch):
+    """A consumer that asks for the bytes of the unwritten hidden activation (ensure_hidden_written, here from a spy on the
+    output layer's acm_conv) costs exactly one more acm_conv_agg_fwd -- the launch that writes ``out`` alone -- and the backward
+    then reads a stored row; losses and parameters stay those of the step nobody looked into."""
+    import fake_lib_elide
+    from acm_gnn_amd import functional as AF, layers as L, tuning
+    fake = fake_lib_elide.install(monkeypatch)
+    calls = _Calls(monkeypatch, fake)
+    conv = L.AF.acm_conv
+    runs = {}
+    for look in (False, True):
+        def spy(inp, *a, **k):
+            if look and isinstance(inp, torch.Tensor) and inp.shape[1] == 64:
+                AF.ensure_hidden_written(k["call"], inp)
+            return conv(inp, *a, **k)
+
+        monkeypatch.setattr(L.AF, "acm_conv", spy)
+        with tuning.override(pipeline=32):
+            step, model, _, _, _ = _headline_step()
+            calls.clear()
+            losses = [float(step()) for _ in range(3)]
+            assert step.hidden_elided
+        fwd, bwd = calls.of("acm_conv_agg_fwd"), calls.of("acm_conv_agg_bwd")
+        if look:                                                 # forward (no `out`), then the write (`out` and nothing else)
+            assert fwd == [("acm_conv_agg_fwd", "next_zlh", "agg_copy", "next_x"), ("acm_conv_agg_fwd", "out")] * 3
+            assert all("out" in c and "proj_dz" in c for c in bwd) and len(bwd) == 3
+        else:
+            assert len(fwd) == 3 and all("out" not in c for c in fwd + bwd)
+        runs[look] = (losses, [p.detach().clone() for p in model.parameters()])
+    assert runs[True][0] == runs[False][0] and all(torch.equal(a, b) for a, b in zip(runs[True][1], runs[False][1]))
+
+
+def test_the_eliding_taped_step_releases_what_it_saved(monkeypatch):
+    """test_deferred_reductions_cpu.test_a_taped_step_releases_what_it_saved for the eliding step: the hand-off between the two
+    layers leaves no reference cycle -- with the collector off, the bytes of live tensors stay constant over six steps."""
+    import gc
+    import fake_lib_elide
+    from acm_gnn_amd import tuning
+    fake_lib_elide.install(monkeypatch)
+
+    def live_bytes():
+        seen, total = set(), 0
+        for o in gc.get_objects():
+            if isinstance(o, torch.Tensor) and o.device.type == "cpu":
+                st = o.untyped_storage()
+                if st.data_ptr() not in seen:
+                    seen.add(st.data_ptr())
+                    total += st.nbytes()
+        return total
+
+    with tuning.override(pipeline=32):
+        step = _headline_step()[0]
+        for _ in range(3):
+            step()
+        gc.collect()
+        gc.disable()
+        try:
+            before = live_bytes()
+            for _ in range(6):
+                step()
+                assert step.hidden_elided
+            after = live_bytes()
+        finally:
+            gc.enable()
+    assert step._tape is True
+    assert after <= before + 4096, (before, after)
+
+
+# the launches of one warm step / pass, recorded on the commit before the hand-off between the two layers became one object
+# (functional._hidden.HiddenLink): that refactoring, and any after it, must reproduce them
+_AGG_FWD, _AGG_BWD = "acm_conv_agg_fwd", "acm_conv_agg_bwd"
+_OUTPUT_LAYER = ["acm_conv_fwd_tail", "acm_conv_fwd", "acm_nll_loss", "acm_conv_bwd_local", "acm_conv_bwd_spmm"]   # (the double declines the tail)
+_UPDATE = ["acm_adam_step", "acm_reduce_flush"]
+_LAUNCHES = {
+    "eliding": [(_AGG_FWD, "next_zlh", "agg_copy", "next_x")] + _OUTPUT_LAYER + [(_AGG_BWD, "proj_dz", "next_agg")] + _UPDATE,
+    "lazy-stored": [(_AGG_FWD, "out", "next_zlh", "agg_copy", "next_x")] + _OUTPUT_LAYER + [(_AGG_BWD, "out", "proj_dz", "next_agg")] + _UPDATE,
+    "autograd-no-deferral": ["acm_dropout", (_AGG_FWD, "out"), "acm_proj_fwd_at", "acm_conv_fwd", "acm_nll_loss", "acm_conv_bwd_local",
+                             "acm_conv_bwd_spmm", "acm_proj_bwd", (_AGG_BWD, "out", "grad_out")],
+    "residual": [(_AGG_FWD, "out", "agg_copy", "next_x"), "acm_linear_fwd_add", "acm_proj_fwd_at"] + _OUTPUT_LAYER
+                + ["acm_proj_bwd", "acm_linear_bwd_recompute", (_AGG_BWD, "out", "grad_out", "next_agg")] + _UPDATE,
+    "hooked": [(_AGG_FWD, "out", "next_zlh", "agg_copy", "next_x")] + _OUTPUT_LAYER + [(_AGG_BWD, "out", "proj_dz", "next_agg")] + _UPDATE,
+    "eval": [(_AGG_FWD, "next_zlh"), "acm_conv_fwd", "acm_eval_metrics"],
+    "mask-tensors": [(_AGG_FWD, "out"), "acm_proj_fwd_at"] + _OUTPUT_LAYER + ["acm_proj_bwd", (_AGG_BWD, "grad_out")] + _UPDATE,
+}
+
+
+def _warm_launches(monkeypatch, case):
+    import fake_lib_elide
+    from acm_gnn_amd import functional as AF, tuning
+    fake = (fake_lib if case == "lazy-stored" else fake_lib_elide).install(monkeypatch)
+    calls = _Calls(monkeypatch, fake)
+    with tuning.override(pipeline=32):
+        if case == "autograd-no-deferral":                       # the plain API: no lazy gradient, acm_proj_bwd, nothing elided
+            model, ops, x, y, w = _setup(dropout=0.3, pattern_only=True, attn_layernorm=True)
+            model.fused_dropout, model.dropout_state = True, AF.DropoutState("cpu", seed=3)
+            model.train()
+            for _ in range(2):
+                calls.clear()
+                out = model(x, ops)
+                _, dz = AF.nll_loss_and_grad(out, y, w)
+                out.backward(dz)
+        elif case == "eval":
+            step, model, ops, x, y = _headline_step()
+            ev = _eval_step(model, ops, x, y)
+            ev()
+            calls.clear()
+            ev()
+        else:
+            kw = dict(fused_dropout=False) if case == "mask-tensors" else {}
+            step, model, _, _, _ = _headline_step("acmgcnpp" if case == "residual" else "acmgcnp", **kw)
+            if case == "hooked":                                 # bytes_private withdrawn: the row is stored, the lazy gradient stays
+                model.gcns[1].register_forward_hook(lambda m, i, o: None)
+            torch.manual_seed(7)                                 # (mask-tensors: F.dropout draws from the global generator)
+            step(), step()
+            calls.clear()
+            step()
+    return calls.log
+
+
+@pytest.mark.parametrize("case", ["eliding", "lazy-stored", "autograd-no-deferral", "residual", "hooked", "eval", "mask-tensors"])
+def test_the_launch_sequence_of_a_warm_step(monkeypatch, case):
+    got = _warm_launches(monkeypatch, case)
+    assert got == _LAUNCHES[case], (case, got)

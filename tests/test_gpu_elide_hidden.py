@@ -270,7 +270,7 @@ def _hidden_layer_pass(ops, x, elide, tune, with_defer, write=False):
 
     def spy(inp, *a, **k):                      # (the layers' entry point: the second call is the output layer's)
         if isinstance(inp, torch.Tensor) and inp.shape[1] == 64:
-            seen["elided"] = call.elided is not None and not call.elided.written
+            seen["elided"] = call.link is not None and call.link.token is not None and not call.link.token.written
             if write:
                 AF.ensure_hidden_written(call, inp)
                 seen["hidden"] = inp.detach().clone()
