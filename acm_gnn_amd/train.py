@@ -10,13 +10,23 @@ cannot run.
                      whole step is one graph launch instead of ~60 kernel launches).
 * ``evaluate``       eval-mode forward + accuracy (or, ``metric="rocauc"``, ROC-AUC) on index sets, on device (the
                      reference pulls the predictions to the host three times per epoch, data_utils.py:117-118, 132-135).
+* ``EvalStep``       the same pass as an object: index sets as averaging weights, one device-to-host copy per pass, optionally
+                     a hipGraph replay, optionally ending in the device-resident selection (functional.SelectionState).
 * ``fit``            the two model-selection rules of the reference; with ``sync_every`` / ``keep_best`` the selection state
                      stays on the device across epochs (functional.SelectionState) and the selected model is returned.
+* ``fit_concurrent`` several runs of ``fit`` on the same graph, ``streams`` at a time, each on a stream of its own.
+* ``fit_batched``    several runs on the same small graph, ``batch`` at a time in the same launches (small.SmallBatch).
+
+Stated once for all of them: the model call (``_call_model``), the capture (``_captured``), the epoch loop (``_drive``) around
+``enqueue`` / ``finished`` / ``result`` and the construction of a run (``_new_run``).
 """
+import contextlib
+from types import SimpleNamespace
+
 import torch
 import torch.nn.functional as F
 
-from . import functional as AF
+from . import _lib, functional as AF
 from . import tuning
 from .graph import FilterOperators, SparseFeatures, operators_for
 
@@ -73,8 +83,11 @@ def _buffers_restore(snap):
 
 
 def _held_entries(model):
-    """What a captured pass over ``model`` reads beyond its graph's own pool: the layers' P = A_low X cache entries
-    (layers.GraphConvolution._eval_agg_holder: key, input, {"agg": P, "xpad": ...}, operators) as they are right now."""
+    """What a captured step or pass over ``model`` reads beyond its graph's own pool: the layers' P = A_low X cache entries
+    (layers.GraphConvolution._eval_agg_holder: key, input, {"agg": P, "xpad": ...}, operators) as they are right now.  The graph
+    bakes in the address of the P its capture read (a dropout-0 step, every evaluation pass); only the layer's cache entry keeps
+    that tensor alive, and another forward of the same model on another input object replaces the entry.  Held by the captured
+    object, the replay keeps reading valid memory whatever the layers cache afterwards (use-after-free)."""
     held = []
     for m in model.modules():
         entries = getattr(m, "held_entries", None)
@@ -118,6 +131,43 @@ def _warm_up(fn, times):
             fn()
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
+
+
+def _captured(fn):
+    """(a new hipGraph with ``fn()`` captured into it, what ``fn`` returned); warm-up, snapshots and resets are the caller's."""
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, **_capture_mode()):
+        result = fn()
+    return graph, result
+
+
+def _takes_call(model):
+    """Whether ``model.forward`` takes a step's or pass's CallContext as the ``call`` keyword (models.GCN does)."""
+    import inspect
+    try:
+        return "call" in inspect.signature(model.forward).parameters
+    except (TypeError, ValueError):
+        return False
+
+
+def _call_model(model, takes_call, inputs, call, tail=None, rows_permuted=False, ambient=True):
+    """``model(*inputs)`` (x, adj, adj_high, adj_un) for a training step or an evaluation pass, with what ``call`` carries -- the
+    deferral list, the input pipeline -- and the loss-tail request ``tail``: as the ``call`` keyword where ``forward`` takes it,
+    otherwise (a wrapper around the model) as the thread's ambient contexts, from which the model derives its own context.
+    ``ambient=False`` (EvalStep): a model without the keyword is called plainly -- the one known difference between a step and
+    a pass, decided here and nowhere else: a pass has no context of its own to enter, and enters none."""
+    kw = {"rows_permuted": True} if rows_permuted else {}
+    if takes_call:
+        if tail is not None:
+            call.tail = tail
+        out = model(*inputs, call=call, **kw)
+        if tail is not None:
+            call.tail = None
+        return out
+    if not ambient:
+        return model(*inputs, **kw)
+    with AF.deferred_reductions_as(call.defer), AF.input_pipeline(call.pipe), tail if tail is not None else contextlib.nullcontext():
+        return model(*inputs, **kw)
 
 
 def _note_elision(step, call):
@@ -210,11 +260,7 @@ class TrainStep:
             else:
                 self._manual_advance = True
         self._params = list(model.parameters())          # walked every step: module.parameters() costs 0.1 ms of host time
-        import inspect
-        try:                                             # models.GCN takes the step's CallContext as a keyword
-            self._takes_call = "call" in inspect.signature(model.forward).parameters
-        except (TypeError, ValueError):
-            self._takes_call = False
+        self._takes_call = _takes_call(model)
         # the first layer's input aggregation one step ahead, inside its own backward (functional.InputPipeline);
         # pipeline_input: None = when the configuration qualifies (InputPipeline.eligible), False = never
         self.pipe = None
@@ -249,7 +295,6 @@ class TrainStep:
 
     def _attach_loss_rows(self):
         """Build (or rebuild, after an in-place edit of the weights) the operators' loss-row attachment; never under capture."""
-        from . import _lib
         old, self.loss_rows = self.loss_rows, None
         ops, w = self.adj, self.weights
         why = None
@@ -323,30 +368,21 @@ class TrainStep:
                 self._tape_proven = True
             else:
                 out.backward(dz)
-        except (AF.TapeBroken, RuntimeError) as err:
+        except BaseException as err:
+            # what abandoning an attempt releases, whatever ended it: the tape's records and the deferral list
             if tape is not None:
                 tape.release()
             if pending is not None:
                 pending.discard()
             # an in-place torch operation on a taped output fails inside torch ("a leaf Variable that requires grad is being
             # used in an in-place operation") before the tape can notice: the same verdict
-            broken = tape is not None and not self._tape_proven and (isinstance(err, AF.TapeBroken) or "leaf Variable" in str(err))
+            broken = isinstance(err, RuntimeError) and tape is not None and not self._tape_proven \
+                and (isinstance(err, AF.TapeBroken) or "leaf Variable" in str(err))
             if not broken:
                 raise
             # torch operations between the layers: this model's steps run on autograd from now on; the step is redone
             self._tape = False
-            _rng_restore(rng)
-            _buffers_restore(buffers)
-            self.opt.zero_grad(set_to_none=True)
-            if pipe is not None:
-                pipe.primed = False
-            return self._forward_backward(for_optimizer)
-        except BaseException:
-            if tape is not None:
-                tape.release()
-            if pending is not None:
-                pending.discard()
-            raise
+            return self._redo(for_optimizer, pipe, buffers, rng)
         if pending is None:
             self._pass_proven = True
             return loss
@@ -360,57 +396,45 @@ class TrainStep:
             return loss
         pending.flush()
         if not adopted:
+            # a gradient was copied before the flush: no deferral from now on; the step is redone.  (No generator snapshot is
+            # handed on: this redo draws its F.dropout masks from where the attempt left the generators, as it always has.)
             self._defer = False
-            _buffers_restore(buffers)
-            self.opt.zero_grad(set_to_none=True)
-            if pipe is not None:
-                pipe.primed = False               # the first pass has already refilled its buffers for the next step
-            return self._forward_backward(for_optimizer)
+            return self._redo(for_optimizer, pipe, buffers)
         self._pass_proven = True
         return loss
 
+    def _redo(self, for_optimizer, pipe, buffers, rng=None):
+        """The step again, after an attempt that must not count: what it moved is put back first -- the generators' states
+        (where a snapshot is handed on), the model's buffers, the gradients, and the pipeline, whose buffers the attempt has
+        already refilled for the NEXT step.  State that a step changes before its backward ends is added HERE."""
+        _rng_restore(rng)
+        _buffers_restore(buffers)
+        self.opt.zero_grad(set_to_none=True)
+        if pipe is not None:
+            pipe.primed = False
+        return self._forward_backward(for_optimizer)
+
     def _forward_loss(self, call):
-        """Forward and fused loss: (loss, dloss/dlogits, logits).  The model's output layer is asked to run its row
-        phase, the loss and its own row-local backward as one kernel (AF.fused_loss_tail); when it does not qualify
-        (wide output, structure channel, a wrapper around the output) the loss is its own launch."""
-        if self.criterion == "bce":
-            return self._forward_bce(call)
+        """Forward and loss: (loss, dloss/dlogits, logits).  With the NLL the model's output layer is asked to run its row
+        phase, the loss and its own row-local backward as one kernel (AF.fused_loss_tail); where it does not qualify
+        (wide output, structure channel, a wrapper around the output) -- and with ``criterion="bce"``, which asks for no tail
+        (the fused tail computes the NLL) -- the loss is its own launch."""
+        nll = self.criterion == "nll"
         lr = self.loss_rows
-        if lr is not None and not lr.current_for(self.weights):
+        if nll and lr is not None and not lr.current_for(self.weights):
             # the weights were edited in place: re-attach -- or, under a capture (no host-side preprocessing there), the full path
             if self.weights.is_cuda and torch.cuda.is_current_stream_capturing():
                 lr = None
             else:
                 self._attach_loss_rows()
                 lr = self.loss_rows
-        tail = call.tail = AF.fused_loss_tail(self.labels, self.weights, loss_rows=lr)
-        kw = {"call": call} if self._takes_call else {}
-        if self._permuted:
-            kw["rows_permuted"] = True
-        if self._takes_call:
-            out = self.model(self.x, self.adj, self.adj_high, self.adj_un, **kw)
-        else:                                     # a wrapper without the ``call`` keyword: the thread's ambient context
-            with AF.deferred_reductions_as(call.defer), AF.input_pipeline(call.pipe), tail:
-                out = self.model(self.x, self.adj, self.adj_high, self.adj_un, **kw)
-        call.tail = None
+        tail = AF.fused_loss_tail(self.labels, self.weights, loss_rows=lr) if nll else None
+        out = _call_model(self.model, self._takes_call, (self.x, self.adj, self.adj_high, self.adj_un), call, tail, self._permuted)
         _note_elision(self, call)
-        if tail.matches(out):
+        if tail is not None and tail.matches(out):
             return tail.loss, tail.dz, out
-        loss, dz = AF.nll_loss_and_grad(out, self.labels, self.weights, defer=call.defer)   # = masked_nll(...).backward(), two launches less
-        return loss, dz, out
-
-    def _forward_bce(self, call):
-        """The same forward without a loss-tail request (the fused tail computes the NLL), then acm_bce_loss."""
-        kw = {"call": call} if self._takes_call else {}
-        if self._permuted:
-            kw["rows_permuted"] = True
-        if self._takes_call:
-            out = self.model(self.x, self.adj, self.adj_high, self.adj_un, **kw)
-        else:
-            with AF.deferred_reductions_as(call.defer), AF.input_pipeline(call.pipe):
-                out = self.model(self.x, self.adj, self.adj_high, self.adj_un, **kw)
-        _note_elision(self, call)
-        loss, dz = AF.bce_loss_and_grad(out, self.labels, self.weights, defer=call.defer)
+        # = masked_nll(...).backward() / masked_bce(...).backward(), two launches less
+        loss, dz = (AF.nll_loss_and_grad if nll else AF.bce_loss_and_grad)(out, self.labels, self.weights, defer=call.defer)
         return loss, dz, out
 
     def _eager(self):
@@ -473,25 +497,23 @@ class TrainStep:
         if self.pipe is not None:
             self.pipe.prime()                   # for the restored counter, outside the capture
             torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
         self.model.train()
         self.opt.zero_grad(set_to_none=True)
-        losses = []
-        with torch.cuda.graph(self.graph, **_capture_mode()):
-            for k in range(self.steps_per_call):
-                if k:
-                    self.opt.zero_grad(set_to_none=True)
-                loss = self._one_step()
-                if self.small is not None and self.steps_per_call > 1:
-                    loss = loss.clone()          # the plan's loss scalar is rewritten by the next step of the same graph
-                losses.append(loss)
-            self.loss, self.losses = loss, losses
-        del loss, losses
-        # A dropout-0 model reuses the first layer's P = A_low X from the layer's cache (layers._eval_agg_holder): the
-        # graph bakes in the address of the P its capture read.  Only the layer's cache entry keeps that tensor alive, and
-        # another forward of the same model on another input object replaces the entry -- held here (as EvalStep does), the
-        # replay keeps reading valid memory whatever the layers cache afterwards (use-after-free).
+        self.graph, self.losses = _captured(self._steps_of_a_call)
+        self.loss = self.losses[-1]
         self._held = _held_entries(self.model)
+
+    def _steps_of_a_call(self):
+        """The ``steps_per_call`` consecutive steps one graph holds: every step's loss scalar."""
+        losses = []
+        for k in range(self.steps_per_call):
+            if k:
+                self.opt.zero_grad(set_to_none=True)
+            loss = self._one_step()
+            if self.small is not None and self.steps_per_call > 1:
+                loss = loss.clone()              # the plan's loss scalar is rewritten by the next step of the same graph
+            losses.append(loss)
+        return losses
 
     def refresh(self):
         """Re-capture after an in-place edit of the features (or of anything else the captured step read once: a captured
@@ -512,21 +534,29 @@ class TrainStep:
             self.opt.step()
 
     def _count_advance(self):
-        """The dropout counter moves once per optimizer step: by FusedAdam's kernel (also_advance) or by hand."""
-        ds = getattr(self.model, "dropout_state", None)
+        """The dropout counter moves once per optimizer step: by hand, or by the optimizer's kernel (the shadow follows)."""
         if self._manual_advance:
-            ds.advance()
-        elif ds is not None and getattr(self.opt, "also_advance", None) is ds.step:
-            ds.host_steps += 1
+            self.model.dropout_state.advance()
+        else:
+            self._counter_moved(1, by="optimizer")
+
+    def _counter_moved(self, k, by):
+        """The dropout counter on the device has moved by ``k`` optimizer steps: its host shadow (``host_steps``) follows.  ``by``:
+        "optimizer"  an eager ``optimizer.step()``: FusedAdam's kernel advances the counter where its ``also_advance`` is it
+        "replay"     the captured step(s): they advanced it, and refilled this step's pipeline buffers for the new value
+        "plan"       launches of fit_batched over this step's SmallPlan: an updating plan advances it"""
+        ds = getattr(self.model, "dropout_state", None)
+        if ds is None or (by == "optimizer" and getattr(self.opt, "also_advance", None) is not ds.step) \
+                or (by == "plan" and not self.small.update):
+            return
+        ds.host_steps += k
+        if by == "replay" and self.pipe is not None:
+            self.pipe._host_steps = ds.host_steps
 
     def __call__(self):
         if self.graph is not None:
             self.graph.replay()
-            ds = getattr(self.model, "dropout_state", None)
-            if ds is not None:
-                ds.host_steps += self.steps_per_call      # the replayed step(s) advanced the device counter
-                if self.pipe is not None:     # ... and refilled the pipeline's buffers for the new value
-                    self.pipe._host_steps = ds.host_steps
+            self._counter_moved(self.steps_per_call, by="replay")
             return self.loss
         return self._eager()
 
@@ -632,11 +662,7 @@ class EvalStep:
         self.graph, self.out, self.res = None, None, None
         self._held = None
         self._use_graph = bool(use_graph)
-        import inspect
-        try:                                             # models.GCN takes the pass's CallContext as a keyword (TrainStep does the same)
-            self._takes_call = "call" in inspect.signature(model.forward).parameters
-        except (TypeError, ValueError):
-            self._takes_call = False
+        self._takes_call = _takes_call(model)
         # whether the last pass (the captured one, with use_graph) left the hidden activation unwritten, and why not
         self.hidden_elided, self.hidden_elided_refused = False, "no forward has run"
         if use_graph:
@@ -668,12 +694,12 @@ class EvalStep:
         self.model.eval()
         if self.small is not None:
             out = self.small.run()                       # three launches, one C-ABI call (acm_small_step, train = 0)
-        elif self._takes_call:
-            call = AF.CallContext.from_ambient()         # (what the model would make itself: here to read what the layers report)
-            out = self.model(self.x, self.adj, self.adj_high, self.adj_un, call=call)
-            _note_elision(self, call)
         else:
-            out = self.model(self.x, self.adj, self.adj_high, self.adj_un)
+            # (the context the model would make itself: here to read what the layers report into it)
+            call = AF.CallContext.from_ambient() if self._takes_call else None
+            out = _call_model(self.model, self._takes_call, (self.x, self.adj, self.adj_high, self.adj_un), call, ambient=False)
+            if call is not None:
+                _note_elision(self, call)
         if self.metric == "rocauc" or self.criterion == "bce":
             return out, self._second_protocol(out)
         if self._metrics_ok(out):
@@ -720,12 +746,7 @@ class EvalStep:
         if self.selector is not None:
             self.selector.reset()               # the warm-up passes folded two epochs in
             torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, **_capture_mode()):
-            self.out, self.res = self._run()
-        # what the captured kernels read beyond the pool of the graph: the layers' evaluation-pass cache entries
-        # (key, input, {"agg": P}, operators) as they are now -- held here so that a later eval-mode forward of the same
-        # model on another input cannot free them under the replay
+        self.graph, (self.out, self.res) = _captured(self._run)
         self._held = _held_entries(self.model)
 
     def launch(self):
@@ -786,14 +807,35 @@ def fit(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, 
                          "evaluation pass")
     if resident and int(epochs) < 1:
         return 0.0, []
-    args = (model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, rule, early_stopping, adj_high, adj_un,
-            fused_dropout, pipeline_input, criterion, metric)
-    run = _ResidentRun(*args, keep_best) if resident else _HostRun(*args, use_graph)
-    done = int(epochs) < 1                  # (the host-selected run has built, and with use_graph captured, its step by now)
+    run = _new_run(resident, use_graph, keep_best, model=model, optimizer=optimizer, x=x, adj=adj, labels=labels, train_idx=train_idx,
+                   val_idx=val_idx, test_idx=test_idx, epochs=epochs, rule=rule, early_stopping=early_stopping, adj_high=adj_high,
+                   adj_un=adj_un, fused_dropout=fused_dropout, pipeline_input=pipeline_input, criterion=criterion, metric=metric)
+    # (without a budget the host-selected run has still built, and with use_graph captured, its step by now)
+    return _drive(run, sync_every, done=int(epochs) < 1)
+
+
+def _drive(run, sync_every, done=False):
+    """The epoch loop of a ``_HostRun``, a ``_ResidentRun`` or ``_BatchedRuns`` on the current stream."""
     while not done:
         run.enqueue(sync_every)
         done = run.finished()
     return run.result()
+
+
+def _new_run(resident, use_graph, keep_best, *, model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, rule,
+             early_stopping, adj_high, adj_un, fused_dropout, pipeline_input, criterion, metric):
+    """One run of ``fit`` / ``fit_concurrent`` around what both kinds have: the training step and the evaluation pass's arguments
+    (its own captured graph when the step is one).  The problem by keyword, every part of it: no call site counts positions."""
+    _checked(metric, METRICS, "metric")
+    if resident and _is_sharded(adj):
+        raise NotImplementedError("fit(sync_every > 1 or keep_best=True): the selection state lives on ONE device; "
+                                  "row-sharded operators are not supported")
+    step = TrainStep(model, optimizer, x, adj, labels, row_weights(train_idx, x.shape[0], device=labels.device), adj_high, adj_un,
+                     use_graph=use_graph or resident, fused_dropout=fused_dropout, pipeline_input=pipeline_input, criterion=criterion)
+    eval_args = (model, x, adj, labels, (train_idx, val_idx, test_idx), adj_high, adj_un)         # EvalStep's and evaluate's
+    if resident:
+        return _ResidentRun(step, eval_args, metric, criterion, epochs, rule, early_stopping, keep_best)
+    return _HostRun(step, eval_args, metric, criterion, epochs, rule, early_stopping, use_graph)
 
 
 def _resident_loop(sync_every, keep_best):
@@ -807,23 +849,16 @@ class _ResidentRun:
     """One run of ``fit`` with its selection state on the device: the captured training step, the captured evaluation pass
     whose graph ends in the selection launches, and how many epochs have been enqueued."""
 
-    def __init__(self, model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, rule, early_stopping, adj_high,
-                 adj_un, fused_dropout, pipeline_input, criterion, metric, keep_best):
-        _checked(metric, METRICS, "metric")
-        if _is_sharded(adj):
-            raise NotImplementedError("fit(sync_every > 1 or keep_best=True): the selection state lives on ONE device; "
-                                      "row-sharded operators are not supported")
-        self.model, self.epochs, self.enqueued = model, int(epochs), 0
-        self.select = AF.SelectionState(rule, early_stopping, epochs, labels.device,
+    def __init__(self, step, eval_args, metric, criterion, epochs, rule, early_stopping, keep_best):
+        self.step, self.model, self.epochs, self.enqueued = step, eval_args[0], int(epochs), 0
+        model = self.model
+        self.select = AF.SelectionState(rule, early_stopping, epochs, eval_args[3].device,
                                         params=list(model.parameters()) if keep_best else None,
                                         # (the running statistics of a deep mlpX stack's BatchNorms: the selected epoch's
                                         #  evaluation pass read them, so the returned model must hold them too)
                                         buffers=[b for b in model.buffers() if b.dtype == torch.float32] if keep_best else None)
-        w = row_weights(train_idx, x.shape[0], device=labels.device)
-        self.step = TrainStep(model, optimizer, x, adj, labels, w, adj_high, adj_un, use_graph=True, fused_dropout=fused_dropout,
-                              pipeline_input=pipeline_input, criterion=criterion)
-        self.ev = EvalStep(model, x, adj, labels, (train_idx, val_idx, test_idx), adj_high, adj_un, loss_set=1, use_graph=True,
-                           metric=metric, criterion=criterion, selector=self.select, train_loss=self.step.loss)
+        self.ev = EvalStep(*eval_args, loss_set=1, use_graph=True, metric=metric, criterion=criterion, selector=self.select,
+                           train_loss=step.loss)
 
     def enqueue(self, sync_every):
         """Up to ``sync_every`` epochs (step replay + evaluation replay) on the current stream, within the budget."""
@@ -849,18 +884,11 @@ class _HostRun:
     captured evaluation pass (without ``use_graph`` an epoch is ``evaluate`` + ``_eager_val_loss``), the history and the
     selection.  The host loop's selection and early-stopping rule is stated once, in ``_fold``."""
 
-    def __init__(self, model, optimizer, x, adj, labels, train_idx, val_idx, test_idx, epochs, rule, early_stopping, adj_high,
-                 adj_un, fused_dropout, pipeline_input, criterion, metric, use_graph):
-        _checked(metric, METRICS, "metric")
+    def __init__(self, step, eval_args, metric, criterion, epochs, rule, early_stopping, use_graph):
+        self.step, self.eval_args, self.metric, self.criterion = step, eval_args, metric, criterion
         self.epochs, self.rule, self.early_stopping = epochs, rule, early_stopping
         self.best_key, self.selected, self.history, self.val_hist = None, 0.0, [], []
-        w = row_weights(train_idx, x.shape[0], device=labels.device)
-        self.step = TrainStep(model, optimizer, x, adj, labels, w, adj_high, adj_un, use_graph=use_graph,
-                              fused_dropout=fused_dropout, pipeline_input=pipeline_input, criterion=criterion)
-        self.labels, self.val_idx, self.metric, self.criterion = labels, val_idx, metric, criterion
-        self.eval_args = (model, x, adj, labels, (train_idx, val_idx, test_idx), adj_high, adj_un)   # EvalStep's and evaluate's
-        # the evaluation pass of every epoch: its own captured graph when the training step is one
-        self.ev = EvalStep(*self.eval_args, loss_set=1, use_graph=True, metric=metric, criterion=criterion) if use_graph else None
+        self.ev = EvalStep(*eval_args, loss_set=1, use_graph=True, metric=metric, criterion=criterion) if use_graph else None
 
     def enqueue(self, sync_every):
         """One epoch (step + evaluation pass) on the current stream: this loop IS ``sync_every = 1``, whatever it is handed."""
@@ -875,7 +903,8 @@ class _HostRun:
             _, accs, val_loss = self.ev.read()
         else:
             out, accs = evaluate(*self.eval_args, metric=self.metric)
-            val_loss = _eager_val_loss(out, self.labels, self.val_idx, self.criterion)
+            (_, _, _, labels, (_, val_idx, _), _, _) = self.eval_args
+            val_loss = _eager_val_loss(out, labels, val_idx, self.criterion)
         return self._fold(float(self.loss), accs, val_loss)
 
     def _fold(self, loss, accs, val_loss):
@@ -951,11 +980,12 @@ def fit_concurrent(runs, x, adj, labels, epochs, rule="min_val_loss", early_stop
                     adj_un=adj_un, use_graph=on_gpu or resident, fused_dropout=fused_dropout, criterion=criterion, metric=metric,
                     sync_every=sync_every, keep_best=keep_best) for model, opt, tr, va, te in runs]
 
+    shared = dict(x=x, adj=adj, labels=labels, epochs=epochs, rule=rule, early_stopping=early_stopping, adj_high=adj_high,
+                  adj_un=adj_un, fused_dropout=fused_dropout, pipeline_input=None, criterion=criterion, metric=metric)
+
     def start(k):
         model, opt, tr, va, te = runs[k]
-        args = (model, opt, x, adj, labels, tr, va, te, epochs, rule, early_stopping, adj_high, adj_un, fused_dropout, None,
-                criterion, metric)
-        return _ResidentRun(*args, keep_best) if resident else _HostRun(*args, True)
+        return _new_run(resident, True, keep_best, model=model, optimizer=opt, train_idx=tr, val_idx=va, test_idx=te, **shared)
 
     return _run_on_streams(start, len(runs), streams, sync_every)
 
@@ -963,19 +993,6 @@ def fit_concurrent(runs, x, adj, labels, epochs, rule="min_val_loss", early_stop
 # The smallest measured batch size within 3 % of the best one on the Squirrel-shaped workload (scripts/bench_batched_fit.py on
 # the MI355X, profiles/batched_fit.jsonl; EXPERIMENTS.md "A batch of runs in the same six launches" has the table).
 DEFAULT_BATCH = 8
-
-
-class _BatchedSlotRun:
-    """One run of ``fit_batched`` while it holds a slot: its (un-captured) training step and evaluation pass objects -- made
-    exactly as ``fit`` makes them, so the run's plans, optimizer state and dropout state are what ``fit`` would train."""
-
-    def __init__(self, k, run, x, adj, labels, fused_dropout):
-        model, opt, tr, va, te = run
-        self.k, self.model, self.enqueued = k, model, 0
-        w = row_weights(tr, x.shape[0], device=labels.device)
-        self.step = TrainStep(model, opt, x, adj, labels, w, use_graph=False, fused_dropout=fused_dropout)
-        self.ev = EvalStep(model, x, adj, labels, (tr, va, te), loss_set=1, use_graph=False)
-        self.refused = self.step.small_refused or self.ev.small_refused
 
 
 def fit_batched(runs, x, adj, labels, epochs, rule="min_val_loss", early_stopping=0, batch=DEFAULT_BATCH, sync_every=32,
@@ -1001,30 +1018,40 @@ def fit_batched(runs, x, adj, labels, epochs, rule="min_val_loss", early_stoppin
     or 64, <= 8 classes, ... --, runs that differ in configuration, a 32-wide and a 64-wide run among them) the call is ``fit_concurrent(..., sync_every=sync_every)`` and the reason is left in
     ``fit_batched.last_refusal`` (None otherwise).  ``keep_best=True``, ``criterion="bce"`` and ``metric="rocauc"`` are not
     implemented here: use ``fit_concurrent``."""
-    from .small import SmallBatch
     if keep_best or criterion != "nll" or metric != "acc":
         raise NotImplementedError('fit_batched: keep_best=True, criterion="bce" and metric="rocauc" are not implemented for the '
                                   "batched loop; use fit_concurrent")
     _resident_loop(sync_every, False)
     batch = int(batch)
-    if not 1 <= batch <= _lib_batch_max():
-        raise ValueError(f"fit_batched: batch must be 1 .. {_lib_batch_max()}, not {batch}")
+    if not 1 <= batch <= _lib.SMALL_BATCH_MAX:
+        raise ValueError(f"fit_batched: batch must be 1 .. {_lib.SMALL_BATCH_MAX}, not {batch}")
     fit_batched.last_refusal = None
     if int(epochs) < 1 or not runs:
         return [(0.0, []) for _ in runs]
-
-    def fallback(why):
+    # one operator set and one feature object for every run (TrainStep would build them per run: the plans must SHARE them).
+    # This loop takes no adj_high / adj_un: an adjacency TENSOR is handed on as its own un-normalised twin, as it always was.
+    ops, xs = (adj, x) if _is_sharded(adj) else _operators_and_features(runs[0][0], x, adj, None, adj)
+    # every run against the envelope before anything is built: the fallback is decided here, not in the middle of the loop
+    why, batched = _outside_batched_envelope(runs, xs, ops), None
+    if why is None:
+        batched = _BatchedRuns(runs, xs, ops, labels, epochs, rule, early_stopping, min(batch, len(runs)), fused_dropout)
+        why = batched.refused                         # (what only the built plans can tell)
+    if why is not None:
         fit_batched.last_refusal = why
         return fit_concurrent(runs, x, adj, labels, epochs, rule=rule, early_stopping=early_stopping, fused_dropout=fused_dropout,
                               sync_every=sync_every)
+    return _drive(batched, sync_every)
 
-    if _is_sharded(adj):
-        return fallback("row-sharded operators")
-    # one operator set and one feature object for every run (TrainStep would build them per run: the plans must SHARE them).
-    # This loop takes no adj_high / adj_un: an adjacency TENSOR is handed on as its own un-normalised twin, as it always was.
-    ops, xs = _operators_and_features(runs[0][0], x, adj, None, adj)
-    # every run against the envelope before anything is built: the fallback is decided here, not in the middle of the loop
+
+fit_batched.last_refusal = None
+
+
+def _outside_batched_envelope(runs, xs, ops):
+    """Why ``fit_batched`` cannot train ``runs`` in the same launches (it then calls ``fit_concurrent``), or None: every run
+    inside the fused small-graph step's envelope, all of them configured alike."""
     from .small import SmallPlan
+    if _is_sharded(ops):
+        return "row-sharded operators"
     shape0 = None
     for k, (model, opt, _, _, _) in enumerate(runs):
         why = SmallPlan.why_not(model, xs, ops, opt, need_dropout_state=False)
@@ -1037,104 +1064,112 @@ def fit_batched(runs, x, adj, labels, epochs, rule="min_val_loss", early_stoppin
                 if shape[-1] != shape0[-1]:
                     why = f"hidden width {shape[-1]} (run 0: {shape0[-1]}): {why}"
         if why is not None:
-            return fallback(f"run {k}: {why}")
-    n_slots = min(batch, len(runs))
-    dev = labels.device
-    pending = list(range(len(runs)))
-    results = [None] * len(runs)
-    live = [None] * n_slots
+            return f"run {k}: {why}"
+    return None
 
-    def enter(k):
-        return _BatchedSlotRun(k, runs[k], xs, ops, labels, fused_dropout)
 
-    first = [enter(pending.pop(0)) for _ in range(n_slots)]
-    why = next((r.refused for r in first if r.refused), None) or SmallBatch.why_not([r.step.small for r in first]) \
-        or SmallBatch.why_not([r.ev.small for r in first])
-    if why is not None:
-        return fallback(why)
-    for i, r in enumerate(first):
-        live[i] = r
-    train_b = SmallBatch([r.step.small for r in first], n_slots)
-    eval_b = SmallBatch([r.ev.small for r in first], n_slots)
-    n, n_classes = first[0].step.small.n, first[0].step.small.C
-    metrics = AF.BatchMetrics(n_slots, n, n_classes, 3, first[0].ev.labels, loss_set=1)
-    select = AF.BatchSelection(rule, early_stopping, epochs, n_slots, dev)
+class _BatchedRuns:
+    """The runs of ``fit_batched`` behind the three methods of a run (``_drive``): the two ``SmallBatch``es (training step,
+    evaluation forward), the batched metrics and selection, the runs that hold a slot and those still waiting for one.  Built
+    and, on the GPU, captured on construction -- unless the first runs' plans cannot share launches: ``refused`` says why."""
 
-    def bind_slot(i, r):
+    def __init__(self, runs, xs, ops, labels, epochs, rule, early_stopping, n_slots, fused_dropout):
+        from .small import SmallBatch
+        self.runs, self.inputs, self.epochs = runs, (xs, ops, labels, fused_dropout), int(epochs)
+        self.pending, self.results = list(range(len(runs))), [None] * len(runs)
+        self.live = first = [self._enter() for _ in range(n_slots)]
+        self.refused = next((r.refused for r in first if r.refused), None) or SmallBatch.why_not([r.step.small for r in first]) \
+            or SmallBatch.why_not([r.ev.small for r in first])
+        if self.refused is not None:
+            return
+        self.train_b = SmallBatch([r.step.small for r in first], n_slots)
+        self.eval_b = SmallBatch([r.ev.small for r in first], n_slots)
+        n, n_classes = first[0].step.small.n, first[0].step.small.C
+        self.metrics = AF.BatchMetrics(n_slots, n, n_classes, 3, first[0].ev.labels, loss_set=1)
+        self.select = AF.BatchSelection(rule, early_stopping, epochs, n_slots, labels.device)
+        for i, r in enumerate(first):
+            self._bind_slot(i, r)
+        self.metrics.flush(), self.select.flush()
+        self.train_b.bind(), self.eval_b.bind()
+        self.replay = self._epoch                     # (without a GPU there is nothing to capture: an epoch is its launches)
+        if labels.is_cuda:
+            # as TrainStep._capture: warm up on a snapshot of every run in a slot, put it back, then capture -- no run sees the
+            # warm-up steps; the selection states are reset (the warm-up folded epochs in)
+            snaps = [r.step._snapshot() for r in first]
+            _warm_up(self._epoch, 3)
+            for r, snap in zip(first, snaps):
+                r.step._restore(snap)
+            for i in range(n_slots):
+                self.select.reset(i)
+            torch.cuda.synchronize()
+            # No ``_held_entries`` beside this graph: it reads none.  Neither SmallBatch calls ``model.forward`` -- the launches
+            # work on the plans' own buffers, the batched metrics and selection on theirs -- so no layer's P is ever looked up.
+            self.replay = _captured(self._epoch)[0].replay
+
+    def _enter(self):
+        """The next waiting run for a slot, with its (un-captured) training step and evaluation pass objects -- made exactly as
+        ``fit`` makes them, so the run's plans, optimizer state and dropout state are what ``fit`` would train."""
+        k, (xs, ops, labels, fused_dropout) = self.pending.pop(0), self.inputs
+        model, opt, tr, va, te = self.runs[k]
+        step = TrainStep(model, opt, xs, ops, labels, row_weights(tr, xs.shape[0], device=labels.device), use_graph=False,
+                         fused_dropout=fused_dropout)
+        ev = EvalStep(model, xs, ops, labels, (tr, va, te), loss_set=1, use_graph=False)
+        return SimpleNamespace(k=k, model=model, enqueued=0, step=step, ev=ev, refused=step.small_refused or ev.small_refused)
+
+    def _bind_slot(self, i, r):
+        """Slot ``i`` of the metrics and the selection reads run ``r``'s logits and loss (None: the slot idles)."""
         if r is None:
-            metrics.set_slot(i)
-            select.set_slot(i)
+            self.metrics.set_slot(i)
+            self.select.set_slot(i)
         else:
-            metrics.set_slot(i, r.ev.small.logits, r.ev.w)
-            select.set_slot(i, r.step.small.loss, metrics.out[i])
+            self.metrics.set_slot(i, r.ev.small.logits, r.ev.w)
+            self.select.set_slot(i, r.step.small.loss, self.metrics.out[i])
 
-    def epoch():
-        train_b.run()
-        eval_b.run()
-        metrics.launch()
-        select.launch()
+    def _epoch(self):
+        self.train_b.run()
+        self.eval_b.run()
+        self.metrics.launch()
+        self.select.launch()
 
-    for i, r in enumerate(live):
-        bind_slot(i, r)
-    metrics.flush(), select.flush()
-    train_b.bind(), eval_b.bind()
-    graph = None
-    if labels.is_cuda:
-        # as TrainStep._capture: warm up on a snapshot of every run in a slot, put it back, then capture -- no run sees the
-        # warm-up steps; the selection states are reset (the warm-up folded epochs in)
-        snaps = [r.step._snapshot() for r in live]
-        _warm_up(epoch, 3)
-        for r, snap in zip(live, snaps):
-            r.step._restore(snap)
-        for i in range(n_slots):
-            select.reset(i)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, **_capture_mode()):
-            epoch()
-    while any(r is not None for r in live):
-        todo = min(int(sync_every), max(int(epochs) - r.enqueued for r in live if r is not None))
+    def _hand_over(self, i):
+        """Slot ``i``'s run has stopped or used its budget up: its result is read, the slot goes to the next waiting run (or
+        idles) by table writes -- nothing is re-captured."""
+        from .small import SmallBatch
+        r = self.live[i]
+        selected, history, _ = self.select.result(i)
+        self.results[r.k] = (selected, history)
+        r.model.eval()
+        nxt = self.live[i] = self._enter() if self.pending else None
+        if nxt is not None:
+            why = nxt.refused or SmallBatch.why_not([self.train_b._first(), nxt.step.small]) \
+                or SmallBatch.why_not([self.eval_b._first(), nxt.ev.small])
+            if why is not None:
+                raise RuntimeError(f"fit_batched: run {nxt.k} cannot share the launches of the runs before it ({why}); "
+                                   "sort such runs into calls of their own")
+        self.train_b.set_slot(i, nxt.step.small if nxt is not None else None)
+        self.eval_b.set_slot(i, nxt.ev.small if nxt is not None else None)
+        self._bind_slot(i, nxt)
+
+    def enqueue(self, sync_every):
+        """Up to ``sync_every`` epochs of every slot (one graph replay each), within the largest budget left among them."""
+        live = [r for r in self.live if r is not None]
+        todo = min(int(sync_every), max(self.epochs - r.enqueued for r in live))
         for _ in range(todo):
-            if graph is not None:
-                graph.replay()
-            else:
-                epoch()
+            self.replay()
         for r in live:
-            if r is not None:
-                r.enqueued += todo
-                ds = getattr(r.model, "dropout_state", None)
-                if ds is not None and r.step.small.update:
-                    ds.host_steps += todo
-        state = select.poll()                          # the ONE synchronising copy of the look
-        changed = False
-        for i, r in enumerate(live):
-            if r is None:
-                continue
-            _, stopped = state[i]
-            if stopped or r.enqueued >= int(epochs):
-                selected, history, _ = select.result(i)
-                results[r.k] = (selected, history)
-                r.model.eval()
-                live[i] = enter(pending.pop(0)) if pending else None
-                nxt = live[i]
-                if nxt is not None:
-                    why = nxt.refused or SmallBatch.why_not([train_b._first(), nxt.step.small]) \
-                        or SmallBatch.why_not([eval_b._first(), nxt.ev.small])
-                    if why is not None:
-                        raise RuntimeError(f"fit_batched: run {nxt.k} cannot share the launches of the runs before it ({why}); "
-                                           "sort such runs into calls of their own")
-                train_b.set_slot(i, nxt.step.small if nxt is not None else None)
-                eval_b.set_slot(i, nxt.ev.small if nxt is not None else None)
-                bind_slot(i, nxt)
-                changed = True
-        if changed:
-            metrics.flush(), select.flush()
-    return results
+            r.enqueued += todo
+            r.step._counter_moved(todo, by="plan")
 
+    def finished(self):
+        """The look: ONE synchronising copy reads every slot's selection state; runs that are through hand their slots over.
+        True once no slot holds a run."""
+        state = self.select.poll()
+        leaving = [i for i, r in enumerate(self.live) if r is not None and (state[i][1] or r.enqueued >= self.epochs)]
+        for i in leaving:
+            self._hand_over(i)
+        if leaving:
+            self.metrics.flush(), self.select.flush()
+        return all(r is None for r in self.live)
 
-fit_batched.last_refusal = None
-
-
-def _lib_batch_max():
-    from . import _lib
-    return _lib.SMALL_BATCH_MAX
+    def result(self):
+        return self.results

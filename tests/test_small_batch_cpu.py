@@ -152,6 +152,44 @@ def test_fit_batched_equals_fit_concurrent_on_the_double(monkeypatch, rule, es):
         assert any(len(h) < EPOCHS for _, h in want), "no run stops early: the hand-over at different epochs is not exercised"
 
 
+def _looks(lengths, slots, sync, epochs):
+    """The batched loop's schedule restated on the runs' history lengths: per look, (the runs that leave, the slots that were
+    empty during it).  A run leaves at the first look by which its last epoch (the stop, or the budget) has been enqueued."""
+    pending, out = list(range(len(lengths))), []
+    live = [pending.pop(0) for _ in range(min(slots, len(lengths)))]
+    done = {k: 0 for k in range(len(lengths))}
+    while any(k is not None for k in live):
+        todo = min(sync, max(epochs - done[k] for k in live if k is not None))
+        empty = sum(k is None for k in live)
+        leaving = []
+        for i, k in enumerate(live):
+            if k is not None:
+                done[k] += todo
+                if done[k] >= lengths[k]:
+                    leaving.append(k)
+                    live[i] = pending.pop(0) if pending else None
+        out.append((leaving, empty))
+    return out
+
+
+def test_fit_batched_hands_two_slots_over_in_one_look_and_ends_with_an_empty_slot(monkeypatch):
+    """More runs than slots (5 on 2): two runs leave in the same look, both slots are handed over by table writes before the next
+    replay, and the last run trains beside an empty slot."""
+    fake = install_batch(_install(monkeypatch))
+    from acm_gnn_amd import train as T
+    ops, xs, y, make = _problem()
+    want = T.fit_concurrent([make(k) for k in range(5)], xs, ops, y, epochs=EPOCHS, rule="min_val_loss", early_stopping=3, sync_every=4)
+    fake.small_batch_calls = 0
+    got = T.fit_batched([make(k) for k in range(5)], xs, ops, y, EPOCHS, rule="min_val_loss", early_stopping=3, batch=2, sync_every=4)
+    assert T.fit_batched.last_refusal is None and fake.small_batch_calls > 0
+    for k in range(5):
+        assert same_floats(got[k][0], want[k][0]) and same_floats(got[k][1], want[k][1]), k
+    assert any(len(h) < EPOCHS for _, h in want), "no run stops early"
+    looks = _looks([len(h) for _, h in want], 2, 4, EPOCHS)
+    assert any(len(leaving) == 2 for leaving, _ in looks), "no look in which two runs leave"
+    assert looks[-1][1] == 1 and looks[-1][0] == [4], "the last look has no empty slot"
+
+
 def test_fit_batched_falls_back_outside_the_envelope_and_says_why(monkeypatch):
     fake = install_batch(_install(monkeypatch))
     from acm_gnn_amd import GCN, FusedAdam, train as T
