@@ -40,7 +40,7 @@ EXPORTED_SYMBOLS = (
     "acm_linear_fwd_shift", "acm_gemm_shift", "acm_bnorm_fold_centred", "acm_bnorm_param_bwd_centred",
     "acm_proj_blocks_fwd", "acm_proj_blocks_bwd_workspace_bytes", "acm_proj_blocks_bwd",
     "acm_csr_build_loss_rows", "acm_csr_loss_rows_info", "acm_conv_fwd_tail_rows",
-    "acm_conv_agg_out_optional",
+    "acm_conv_agg_out_optional", "acm_gather_form",
 )
 # the loss-row entry points (new symbols under ABI 29): callers look them up with getattr(lib, name, None) and keep the full
 # path where a library -- or a test double -- does not have them
@@ -220,6 +220,24 @@ class ProjBlocks(C.Structure):
                 ("d_h", C.c_void_p * PROJ_BLOCKS_MAX), ("ld_dh", C.c_int64 * PROJ_BLOCKS_MAX)]
 
 
+class GatherQuery(C.Structure):
+    """acm_gather_query_t: what acm_gather_form decides from (host-only: the addresses are numbers, nothing is read behind them)."""
+    _fields_ = [("n_rows", C.c_int64), ("n_cols", C.c_int64), ("nnz", C.c_int64), ("n_long", C.c_int64), ("n_multi", C.c_int64),
+                ("has_long_index", C.c_int32), ("n_gathered", C.c_int32), ("width", C.c_int32), ("bf16", C.c_int32),
+                ("fused_head", C.c_int32), ("reserved", C.c_int32), ("table", C.c_uint64 * 3), ("ld", C.c_int64 * 3)]
+
+
+class GatherFormAnswer(C.Structure):
+    """acm_gather_form_t."""
+    _fields_ = [("kind", C.c_int32), ("lanes", C.c_int32), ("vecmask", C.c_int32), ("merged", C.c_int32), ("f_arg", C.c_int32),
+                ("fixup", C.c_int32), ("k4_split", C.c_int32), ("reserved", C.c_int32)]
+
+
+# acm_gather_form_t.kind (ACM_GATHER_*) and .fixup (ACM_FIXUP_*)
+GATHER_KINDS = ("NARROW", "PAIR3", "VEC16", "VEC", "PAIR_BF16", "PAIR_F32", "WIDE")
+GATHER_FIXUPS = ("none", "narrow", "windows", "wide")
+
+
 class SpmmOpts(C.Structure):
     _fields_ = [("vals", C.c_void_p), ("row_scale", C.c_void_p), ("sub", C.c_void_p), ("ld_sub", C.c_int64),
                 ("sub_scale", C.c_void_p), ("relu", C.c_int32), ("g_bf16", C.c_int32)]
@@ -347,6 +365,7 @@ def _declare(lib):
     lib.acm_conv_bwd_local_workspace_bytes.argtypes = [i64, i32, i32, C.POINTER(sz)]
     lib.acm_conv_bwd_local.argtypes = [i64, C.POINTER(ConvBwdLocal), vp, sz, vp]
     lib.acm_conv_bwd_spmm.argtypes = [vp, C.POINTER(ConvBwdSpmm), vp, sz, vp]
+    lib.acm_gather_form.argtypes = [C.POINTER(GatherQuery), C.POINTER(GatherFormAnswer)]
     lib.acm_conv_agg_fwd.argtypes = [vp, C.POINTER(ConvAggFwd), vp, sz, vp]
     lib.acm_conv_agg_out_optional.argtypes = [C.POINTER(ConvAggFwd), i64, i32]
     lib.acm_conv_agg_bwd_workspace_bytes.argtypes = [i64, i32, i32, C.POINTER(sz)]

@@ -81,6 +81,57 @@ struct EpiBwdStruc {
     }
 };
 
+// Whether K4 runs one channel per pass.
+// wide layers on graphs whose gathered tables exceed the L2: one channel per pass (see EpiBwdLow)
+// (acm_tuning_t.bwd_split = 1 / 0 force either form, for tests and A/B measurements)
+// Measured (profiles/r02_wide_kernels.jsonl): twitch-shaped (mean degree 82) 640 -> 613 us, with the structure channel
+// 1004 -> 899, Penn94-shaped (66) 121 -> 106; arXiv-year-shaped (15) 160 -> 190: short rows pay the per-item cost of
+// every pass, so the split needs a mean degree of K4_SPLIT_MIN_ROW.
+// bf16 tables (gather_bf16): [G_L | G_H] of a neighbour are 2 x 128 bytes -- what ONE fp32 channel is -- so the fused pass
+// keeps the hot set of a single fp32 pass and saves the second walk over the operator (twitch-shaped, F = 64: 430 us in
+// two passes, 387 us fused; fp32: 619 us in two passes)
+constexpr int K4_SPLIT_MIN_ROW = 32;
+static bool conv_bwd_splits(int64_t n_rows, int64_t n_cols, int64_t nnz, int F, bool b16, int want_split) {
+    const bool big = (size_t)n_cols * (size_t)F * sizeof(float) > GATHER_L2_BYTES && nnz >= K4_SPLIT_MIN_ROW * n_rows;
+    const bool split = want_split == 0 ? false : (want_split == 1 ? true : (big && !b16));
+    return F > 8 && F <= 256 && split;
+}
+
+// The host-only query of the chooser (acm_hip.h): the same choose_gather_form / choose_gather_fixup / conv_bwd_splits the launches
+// call, on sizes and addresses the caller states.  Nothing is dereferenced.
+static_assert(GatherForm::NARROW == ACM_GATHER_NARROW && GatherForm::PAIR3 == ACM_GATHER_PAIR3 && GatherForm::VEC16 == ACM_GATHER_VEC16 &&
+                  GatherForm::VEC == ACM_GATHER_VEC && GatherForm::PAIR_BF16 == ACM_GATHER_PAIR_BF16 &&
+                  GatherForm::PAIR_F32 == ACM_GATHER_PAIR_F32 && GatherForm::WIDE == ACM_GATHER_WIDE,
+              "acm_hip.h states the kinds");
+static_assert(FIXUP_NONE == ACM_FIXUP_NONE && FIXUP_NARROW == ACM_FIXUP_NARROW && FIXUP_WINDOWS == ACM_FIXUP_WINDOWS &&
+                  FIXUP_WIDE == ACM_FIXUP_WIDE, "acm_hip.h states the fix-ups");
+extern "C" int acm_gather_form(const acm_gather_query_t* q, acm_gather_form_t* out) {
+    ACM_REQUIRE(q && out, ACM_EINVAL, "acm_gather_form: NULL argument");
+    const int NG = q->n_gathered, F = q->width;
+    ACM_REQUIRE(NG >= 1 && NG <= 3 && F > 0 && q->n_rows >= 0 && q->n_cols >= 0 && q->nnz >= 0 && q->n_long >= 0 && q->n_multi >= 0,
+                ACM_ESHAPE, "acm_gather_form: n_gathered %d width %d", NG, F);
+    ACM_REQUIRE(F <= 256, ACM_EUNSUPPORTED, "acm_gather_form: F = %d > 256 columns per channel", F);
+    const bool b16 = q->bf16 != 0;
+    ACM_REQUIRE(!b16 || (F > 8 && F <= 64 && F % 2 == 0), ACM_EUNSUPPORTED,
+                "acm_gather_form: bf16 gathered operands are implemented for even 8 < F <= 64");
+    static const int32_t some_index = 0;              // (the chooser asks whether the handle has a long index, not what it holds)
+    GatherSrc g = {{nullptr, nullptr, nullptr}, {0, 0, 0}};
+    for (int c = 0; c < NG; ++c) {
+        g.p[c] = reinterpret_cast<const float*>((uintptr_t)q->table[c]);
+        g.ld[c] = (long)q->ld[c];
+    }
+    const GatherForm f = choose_gather_form(q->n_rows, q->n_cols, q->nnz, q->n_long, q->has_long_index ? &some_index : nullptr, g, NG, F,
+                                            b16, acm_tuning().wide_form, q->fused_head != 0);
+    out->kind = (int32_t)f.kind;
+    out->lanes = f.lanes;
+    out->vecmask = f.vecmask;
+    out->merged = f.merged ? 1 : 0;
+    out->f_arg = gather_form_f_arg(f, F);
+    out->fixup = (int32_t)choose_gather_fixup(F, q->n_rows, q->nnz, q->n_long, q->n_multi);
+    out->k4_split = conv_bwd_splits(q->n_rows, q->n_cols, q->nnz, F, b16, acm_tuning().bwd_split) ? 1 : 0;
+    return ACM_OK;
+}
+
 extern "C" int acm_conv_bwd_spmm(const acm_csr_t* at, const acm_conv_bwd_spmm_t* p, void* workspace,
                                  size_t workspace_bytes, acm_stream_t stream) {
     ACM_REQUIRE(at && p, ACM_EINVAL, "acm_conv_bwd_spmm: NULL argument");
@@ -89,19 +140,8 @@ extern "C" int acm_conv_bwd_spmm(const acm_csr_t* at, const acm_conv_bwd_spmm_t*
     ACM_REQUIRE(p->g_low && p->g_high && p->s_high && p->dz_low && p->dz_high, ACM_EINVAL,
                 "acm_conv_bwd_spmm: NULL tensor pointer");
     if (p->g_struc) ACM_REQUIRE(p->s_struc && p->d_struc, ACM_EINVAL, "acm_conv_bwd_spmm: structure channel pointers are NULL");
-    // wide layers on graphs whose gathered tables exceed the L2: one channel per pass (see EpiBwdLow)
-    // (acm_tuning_t.bwd_split = 1 / 0 force either form, for tests and A/B measurements)
-    // Measured (profiles/r02_wide_kernels.jsonl): twitch-shaped (mean degree 82) 640 -> 613 us, with the structure channel
-    // 1004 -> 899, Penn94-shaped (66) 121 -> 106; arXiv-year-shaped (15) 160 -> 190: short rows pay the per-item cost of
-    // every pass, so the split needs a mean degree of 32.
-    const bool big = (size_t)at->n_cols * (size_t)F * sizeof(float) > (8u << 20) && at->nnz >= 32 * at->n_rows;
-    // bf16 tables (gather_bf16): [G_L | G_H] of a neighbour are 2 x 128 bytes -- what ONE fp32 channel is -- so the fused pass
-    // keeps the hot set of a single fp32 pass and saves the second walk over the operator (twitch-shaped, F = 64: 430 us in
-    // two passes, 387 us fused; fp32: 619 us in two passes)
     const bool b16 = p->gather_bf16 != 0;             // launch_gather checks the shape (even 8 < F <= 64) and alignment
-    const int want_split = acm_tuning().bwd_split;
-    const bool split = want_split == 0 ? false : (want_split == 1 ? true : (big && !b16));
-    if (F > 8 && F <= 256 && split) {
+    if (conv_bwd_splits(at->n_rows, at->n_cols, at->nnz, F, b16, acm_tuning().bwd_split)) {
         hipStream_t s = (hipStream_t)stream;
         GatherSrc gl = {{p->g_low, nullptr, nullptr}, {p->ld_g_low, 0, 0}};
         int st = launch_gather<1, EpiBwdLow>(at, gl, F, *p, workspace, workspace_bytes, s, "acm_conv_bwd_spmm", nullptr, b16);

@@ -778,6 +778,12 @@ inline int narrow_lanes(int64_t n_rows, int64_t nnz) {
 // with 16 lanes per item a workgroup round is one window: the narrow gather finishes the long rows itself
 inline bool narrow_finishes_long_rows(const acm_csr* a) { return narrow_lanes(a->n_rows, a->nnz) == ACM_WINDOW; }
 
+// The chooser's figures (tests/launch_forms.py pins them): gathered tables up to GATHER_L2_BYTES count as resident in the L2;
+// the vector form needs a mean row length of VEC_MIN_ROW_ONE with one gathered channel, VEC_MIN_ROW_MANY with several.
+constexpr size_t GATHER_L2_BYTES = 8u << 20;
+constexpr int VEC_MIN_ROW_ONE = 16;
+constexpr int VEC_MIN_ROW_MANY = 4;
+
 // Which kernel of the family a gather takes.  The template arguments that depend on F alone (FP, NB, NREG) follow from the
 // roundings above at the launch.
 struct GatherForm {
@@ -822,7 +828,7 @@ inline GatherForm choose_gather_form(int64_t n_rows, int64_t n_cols, int64_t nnz
     // load + one FMA instruction per neighbour on a half-empty wave and is issue-bound there (81 -> 69 us on
     // Squirrel).  On the 168k-node graph the same gather is bound by the Infinity-Cache fills and the pair form is
     // 5-10 % slower, so it is not used.
-    bool pair32 = !bf16 && F > 32 && F <= 64 && F % 2 == 0 && (size_t)n_cols * F * NG * sizeof(float) <= (8u << 20);
+    bool pair32 = !bf16 && F > 32 && F <= 64 && F % 2 == 0 && (size_t)n_cols * F * NG * sizeof(float) <= GATHER_L2_BYTES;
     for (int c = 0; c < NG && pair32; ++c) pair32 = ((uintptr_t)g.p[c]) % 8 == 0 && g.ld[c] % 2 == 0;
     // vector form: 16-byte aligned rows, 32-bit byte offsets into the gathered tables
     // Measured on the twitch-shaped graph (scripts/probe_wide.py, profiles/r02_probe_wide.txt): rows served by the L2
@@ -837,9 +843,9 @@ inline GatherForm choose_gather_form(int64_t n_rows, int64_t n_cols, int64_t nnz
     // the rows arrive at L2 speed and the instruction count is what bounds the kernel (Squirrel with the structure
     // channel: conv_bwd_spmm 57.8 -> 42.6 us, conv_fwd 64.1 -> 57.7, step 0.283 -> 0.265 ms; it replaces the
     // two-neighbours-per-instruction pair form of round 1 on those graphs).
-    const bool l2_resident = (size_t)n_cols * F * NG * sizeof(float) <= (8u << 20);
+    const bool l2_resident = (size_t)n_cols * F * NG * sizeof(float) <= GATHER_L2_BYTES;
     bool vec = !bf16 && F % 4 == 0 && form != 1 &&
-               ((NG == 1 && nnz >= 16 * n_rows) || (l2_resident && NG > 1 && nnz >= 4 * n_rows) || form == 2);
+               ((NG == 1 && nnz >= VEC_MIN_ROW_ONE * n_rows) || (l2_resident && NG > 1 && nnz >= VEC_MIN_ROW_MANY * n_rows) || form == 2);
     for (int c = 0; c < NG && vec; ++c)
         vec = ((uintptr_t)g.p[c]) % 16 == 0 && g.ld[c] % 4 == 0 &&
               (uint64_t)n_cols * (uint64_t)g.ld[c] * 4u < (1ull << 32);
@@ -854,12 +860,35 @@ inline GatherForm choose_gather_form(int64_t n_rows, int64_t n_cols, int64_t nnz
     // transposed gather of the backward keeps the vector form (2.32 against 2.88 ms): profiles/r04_bench_scale.jsonl
     const bool head_beyond_cache = fused_head && (size_t)n_cols * F * NG * 2u > ((size_t)256 << 20);
     bool vec16 = bf16 && F % 4 == 0 && form != 1 && form != 3 &&
-                 ((NG == 1 && nnz >= 16 * n_rows) || (NG > 1 && nnz >= 4 * n_rows && !head_beyond_cache) ||
+                 ((NG == 1 && nnz >= VEC_MIN_ROW_ONE * n_rows) || (NG > 1 && nnz >= VEC_MIN_ROW_MANY * n_rows && !head_beyond_cache) ||
                   form == 2);
     for (int c = 0; c < NG && vec16; ++c)
         vec16 = ((uintptr_t)g.p[c]) % 8 == 0 && g.ld[c] % 4 == 0 && (uint64_t)n_cols * (uint64_t)g.ld[c] * 2u < (1ull << 32);
     f.kind = vec16 ? GatherForm::VEC16 : (vec && !pair32) ? GatherForm::VEC : bf16 ? GatherForm::PAIR_BF16 : pair32 ? GatherForm::PAIR_F32 : GatherForm::WIDE;
     return f;
+}
+
+// Which launch adds the partial sums of the long rows after the main gather.  Sixteen lanes per item: the narrow gather has
+// finished the long rows itself, except the rows of several windows (n_multi of them).  n_long, n_multi: the counts of the
+// work list the gather walks; n_rows, nnz: the handle's own.
+enum GatherFixup { FIXUP_NONE = 0, FIXUP_NARROW = 1, FIXUP_WINDOWS = 2, FIXUP_WIDE = 3 };
+inline GatherFixup choose_gather_fixup(int F, int64_t n_rows, int64_t nnz, int64_t n_long, int64_t n_multi) {
+    if (F <= 8 && narrow_lanes(n_rows, nnz) == ACM_WINDOW) return n_multi ? FIXUP_WINDOWS : FIXUP_NONE;
+    if (!n_long) return FIXUP_NONE;
+    return F <= 8 ? FIXUP_NARROW : FIXUP_WIDE;
+}
+
+// The template argument that follows from F alone: FP (NARROW, PAIR3), NB (VEC), NREG (WIDE); 1 for the bf16 vector form, 0 for
+// the pair kernels, which have none.
+inline int gather_form_f_arg(const GatherForm& f, int F) {
+    switch (f.kind) {
+    case GatherForm::NARROW:
+    case GatherForm::PAIR3: return acm_fp(F);
+    case GatherForm::VEC: return acm_nb_of(F).v;
+    case GatherForm::WIDE: return acm_nreg_of(F).v;
+    case GatherForm::VEC16: return 1;
+    default: return 0;
+    }
 }
 
 // An epilogue that declares `static constexpr bool kWideOnly = true` is never launched with F <= 8: launch_gather then does not
@@ -925,8 +954,6 @@ int launch_gather(const acm_csr* a, const GatherSrc& g, int F, const typename Ep
         int grid = (int)((n_items + 15) / 16);
         if (grid > NARROW_MAX_BLOCKS) grid = NARROW_MAX_BLOCKS;
         launch_pair3<NG, Epi>(grid, st, v, g.p[0], ea, partial);
-        ACM_CHECK_HIP(hipGetLastError());
-        return finish_window_rows<NG, Epi>(a, v, F, ea, partial, st);
       }
       break;
     }
@@ -953,11 +980,13 @@ int launch_gather(const acm_csr* a, const GatherSrc& g, int F, const typename Ep
     }
     ACM_REQUIRE(rc == ACM_OK, ACM_EUNSUPPORTED, "%s: no narrow gather for %d lanes per item", who, form.lanes);
     ACM_CHECK_HIP(hipGetLastError());
-    // sixteen lanes per item: the narrow gather has finished the long rows itself, except the rows of several windows
-    if constexpr (!epi_wide_only<Epi>::value)
-        if (F <= 8 && narrow_finishes_long_rows(a)) return finish_window_rows<NG, Epi>(a, v, F, ea, partial, st);
-    if (defer_fixup || !n_long) return ACM_OK;      // (deferred: the caller's next kernel adds the partial slots of the long rows)
-    if (F <= 8) {
+    const GatherFixup fix = choose_gather_fixup(F, a->n_rows, a->nnz, n_long, v.n_multi);
+    if (fix == FIXUP_WINDOWS) {
+        if constexpr (!epi_wide_only<Epi>::value) return finish_window_rows<NG, Epi>(a, v, F, ea, partial, st);
+        return ACM_OK;
+    }
+    if (defer_fixup || fix == FIXUP_NONE) return ACM_OK;      // (deferred: the caller's next kernel adds the partial slots of the long rows)
+    if (fix == FIXUP_NARROW) {
       if constexpr (!epi_wide_only<Epi>::value)
         acm_pick([&](auto fp) {
             hipLaunchKernelGGL((spmm_fixup_narrow_kernel<fp(), NG, Epi>), dim3((int)((n_long + 15) / 16)), dim3(256), 0, st, v, F, ea,

@@ -648,6 +648,47 @@ typedef struct {
 int acm_conv_bwd_spmm(const acm_csr_t* a_low_t, const acm_conv_bwd_spmm_t* p,
                       void* workspace, size_t workspace_bytes, acm_stream_t stream);
 
+/* acm_gather_form: which kernel of the gather family a sparse product takes (a new symbol under ABI 29).  Every product of the
+ * library -- acm_spmm*, acm_conv_fwd, acm_conv_bwd_spmm, the k-hop chains -- picks its kernel from the operator's sizes, the
+ * width, the number of gathered tables, their addresses and pitches, and acm_tuning_t.wide_form; this asks that very choice
+ * without a device: host code, nothing is launched and no address is dereferenced (the tests fabricate them).  No reference
+ * counterpart (torch.spmm has one form, ACM-Geometric/layers.py:87-103).
+ *   n_long / n_multi: the operator's long rows (acm_csr_info_t.n_long_rows) and those of them longer than 64 x chunk, which
+ *   take several windows of pieces; has_long_index: it has long rows' index (every handle with long rows does).
+ *   table[c] / ld[c]: address and pitch (in elements) of gathered table c < n_gathered.
+ * The answer: `kind` (ACM_GATHER_*); for ACM_GATHER_NARROW the lanes per work item, the bit mask of the channels fetched with
+ * vector loads and whether channels 0 and 1 are fetched as one block; f_arg = the template argument that follows from the
+ * width (columns per padded row 2 / 4 / 8 for NARROW and PAIR3, 64-column blocks for VEC, registers per channel for WIDE, 1
+ * for VEC16, 0 otherwise); `fixup` = the launch that adds the long rows' partial sums afterwards (ACM_FIXUP_*), as a call that
+ * does not defer it sees it; k4_split = 1 where acm_conv_bwd_spmm at this width over this operator runs one channel per pass
+ * (acm_tuning_t.bwd_split) -- each pass is then the gather this function describes for n_gathered = 1 and that pass's table. */
+#define ACM_GATHER_NARROW 0
+#define ACM_GATHER_PAIR3 1
+#define ACM_GATHER_VEC16 2
+#define ACM_GATHER_VEC 3
+#define ACM_GATHER_PAIR_BF16 4
+#define ACM_GATHER_PAIR_F32 5
+#define ACM_GATHER_WIDE 6
+#define ACM_FIXUP_NONE 0
+#define ACM_FIXUP_NARROW 1
+#define ACM_FIXUP_WINDOWS 2
+#define ACM_FIXUP_WIDE 3
+typedef struct {
+    int64_t n_rows, n_cols, nnz, n_long, n_multi;
+    int32_t has_long_index;
+    int32_t n_gathered;        /* 1..3 */
+    int32_t width;             /* columns per channel, 1..256 */
+    int32_t bf16;              /* the tables hold bf16 (even 8 < width <= 64) */
+    int32_t fused_head;        /* the epilogue is the mixing head (acm_conv_fwd) */
+    int32_t reserved;
+    uint64_t table[3];
+    int64_t ld[3];
+} acm_gather_query_t;
+typedef struct {
+    int32_t kind, lanes, vecmask, merged, f_arg, fixup, k4_split, reserved;
+} acm_gather_form_t;
+int acm_gather_form(const acm_gather_query_t* q, acm_gather_form_t* out);
+
 
 /* ------------------------------ aggregate-first form of the layer (K2a / K3a) --
  * For the ACM (non-variant) and acmsgc models the filter and the projection

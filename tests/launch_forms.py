@@ -24,6 +24,13 @@ THRESHOLDS = {
     "GCN_FWD_SHORT_REST": (CSRC + "acm_gcn.hip", r"left - 256 <= (\d+) \? 128 : 256", 8),
     "NARROW_8_LANES_UP_TO": (CSRC + "acm_gather_device.h", r"return avg <= (\d+)\.0 \? 8 :", 12),
     "NARROW_16_LANES_UP_TO": (CSRC + "acm_gather_device.h", r"\? 8 : \(avg <= (\d+)\.0 \? 16 : 32\)", 160),
+    "GATHER_L2_MIB": (CSRC + "acm_gather_device.h", r"constexpr size_t GATHER_L2_BYTES = (\d+)u << 20;", 8),
+    "VEC_MIN_ROW_ONE": (CSRC + "acm_gather_device.h", r"constexpr int VEC_MIN_ROW_ONE = (\d+);", 16),
+    "VEC_MIN_ROW_MANY": (CSRC + "acm_gather_device.h", r"constexpr int VEC_MIN_ROW_MANY = (\d+);", 4),
+    "VEC_ROW_ONE_IS_USED": (CSRC + "acm_gather_device.h", r"bool vec = [^;]*\(NG == (\d) && nnz >= VEC_MIN_ROW_ONE \* n_rows\)", 1),
+    "VEC_ROW_MANY_IS_USED": (CSRC + "acm_gather_device.h", r"bool vec = [^;]*l2_resident && NG > (\d) && nnz >= VEC_MIN_ROW_MANY \* n_rows\)", 1),
+    "K4_SPLIT_MIN_ROW": (CSRC + "acm_conv_bwd.hip", r"constexpr int K4_SPLIT_MIN_ROW = (\d+);", 32),
+    "K4_SPLIT_IS_USED": (CSRC + "acm_conv_bwd.hip", r"sizeof\(float\) > GATHER_L2_BYTES && nnz >= K4_SPLIT_MIN_ROW \* n_rows;\n[^\n]*want_split == (\d) \? false", 0),
     "COPY_CHUNK": (CSRC + "acm_select.hip", r"constexpr int CHUNK = (\d+);", 2048),
     "COPY_MAX_BLOCKS": (CSRC + "acm_select.hip", r"constexpr int MAX_BLOCKS = (\d+);", 1024),
     "ADAM_CHUNK": (CSRC + "acm_optim.hip", r"constexpr int CHUNK = (\d+);", 2048),
@@ -62,6 +69,12 @@ GCN_BWD_MAX_BLOCKS = T["GCN_BWD_MAX_BLOCKS"]
 GCN_BWD_HELD_GRIDS = [(9000, 6, 33, 3, 8), (2500, 20, 33, 5, 32)]                           # (n, mean degree, hidden, width, lanes)
 GCN_FWD_RIDDEN_WIDTHS = [16, 17, 63, 65, 128, 129, 192, 193, 255, 256]
 GCN_FWD_SPLIT_WIDTHS = [264, 265, 520]
+
+# ---- the gather family's chooser (tests/gather_forms.py) ---------------------------------------------------------------------------
+GATHER_BIG_COLS = 16_500            # table rows of the large operators: two channels of 64 columns, or one of 128, exceed the L2 bound
+GATHER_BIG_ROWS = 300
+GATHER_BIG_MEANS = (48, 20)         # mean row lengths aimed at: at least K4's 32 for the automatic split, and below it
+GATHER_DENSE_SHAPE = (190, 200)     # density 0.9: more than 160 entries per row and per column (32 lanes, both ways)
 
 # ---- acm_copy_if / acm_adam_step -------------------------------------------------------------------------------------------------
 COPY_TABLES = [[2_097_152], [2_097_153, 5, 1025], [3, 4_194_309, 1024, 0, 7]]
@@ -103,6 +116,16 @@ def coverage():
     out.append(("gcn_bwd: hidden at the limit", max(h for h, _ in GCN_BWD_SHAPES) + 1, T["GCN_BWD_MAX_HIDDEN"]))
     out.append(("gcn_fwd: 264 columns split 128 + rest", 256 + T["GCN_FWD_SHORT_REST"] + 1, GCN_FWD_SPLIT_WIDTHS[0]))
     out.append(("gcn_fwd: 265 columns split 256 + rest", GCN_FWD_SPLIT_WIDTHS[1], 256 + T["GCN_FWD_SHORT_REST"]))
+    l2 = T["GATHER_L2_MIB"] << 20
+    out.append(("gather: two channels of 64 columns of the large table exceed the L2 bound", GATHER_BIG_COLS * 64 * 2 * 4, l2))
+    out.append(("gather: one channel of 128 columns of the large table exceeds it", GATHER_BIG_COLS * 128 * 4, l2))
+    out.append(("gather: one channel of 64 columns of the large table stays resident", l2 + 1, GATHER_BIG_COLS * 64 * 4))
+    out.append(("gather: two channels of 32 columns of the large table stay resident", l2 + 1, GATHER_BIG_COLS * 32 * 2 * 4))
+    out.append(("gather: the denser large operator takes K4's automatic split", GATHER_BIG_MEANS[0] + 1, T["K4_SPLIT_MIN_ROW"]))
+    out.append(("gather: the sparser one does not", T["K4_SPLIT_MIN_ROW"], GATHER_BIG_MEANS[1]))
+    out.append(("gather: ... and still takes the vector form with one channel", GATHER_BIG_MEANS[1] + 1, T["VEC_MIN_ROW_ONE"]))
+    out.append(("gather: the dense operator's rows exceed the 16-lane bound", int(0.88 * (min(GATHER_DENSE_SHAPE) - 2)),
+                T["NARROW_16_LANES_UP_TO"]))
     for table in COPY_TABLES[1:]:
         out.append(("copy_if: rounds > 1", max(table), T["COPY_CHUNK"] * T["COPY_MAX_BLOCKS"]))
     out.append(("copy_if: the last size with one round", T["COPY_CHUNK"] * T["COPY_MAX_BLOCKS"] + 1, COPY_TABLES[0][0]))
