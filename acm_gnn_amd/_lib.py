@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "acm_gcn_fwd", "acm_gcn_bwd_workspace_bytes", "acm_gcn_bwd", "acm_gemm_act",
     "acm_select_step", "acm_copy_if",
     "acm_small_batch_table_bytes", "acm_small_batch_bind", "acm_small_batch_step", "acm_eval_metrics_batch", "acm_select_step_batch",
+    "acm_small_batch_grids", "acm_small_batch_bind_graphs", "acm_small_batch_step_graphs",
     "acm_bnorm_stats_workspace_bytes", "acm_bnorm_stats", "acm_bnorm_fold", "acm_bnorm_param_bwd", "acm_bnorm_bwd_workspace_bytes", "acm_bnorm_bwd",
     "acm_linear_fwd_shift", "acm_gemm_shift", "acm_bnorm_fold_centred", "acm_bnorm_param_bwd_centred",
     "acm_proj_blocks_fwd", "acm_proj_blocks_bwd_workspace_bytes", "acm_proj_blocks_bwd",
@@ -303,6 +304,13 @@ class SmallStep(C.Structure):
 
 SMALL_BATCH_MAX = 32          # ACM_SMALL_BATCH_MAX: slots of one acm_small_batch_* table
 
+
+class SmallBatchGrids(C.Structure):
+    """acm_small_batch_grids_t: the launch widths of a batch whose slots stand on different graphs (an element-wise maximum
+    over the runs' own grids; zero-initialised, then folded into by acm_small_batch_grids)."""
+    _fields_ = [("proj", C.c_int32), ("wide", C.c_int32), ("graph", C.c_int32), ("item_blocks", C.c_int32), ("red_blocks", C.c_int32)]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -421,6 +429,10 @@ def _declare(lib):
     lib.acm_small_batch_table_bytes.argtypes = [i32, C.POINTER(sz)]
     lib.acm_small_batch_bind.argtypes = [vp, vp, vp, i32, C.POINTER(C.POINTER(SmallStep)), vp, sz, vp]
     lib.acm_small_batch_step.argtypes = [vp, vp, vp, i32, C.POINTER(SmallStep), vp, vp]
+    lib.acm_small_batch_grids.argtypes = [vp, vp, vp, C.POINTER(SmallStep), C.POINTER(SmallBatchGrids)]
+    lib.acm_small_batch_bind_graphs.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.POINTER(SmallStep)),
+                                                C.POINTER(SmallBatchGrids), vp, sz, vp]
+    lib.acm_small_batch_step_graphs.argtypes = [i32, C.POINTER(SmallStep), C.POINTER(SmallBatchGrids), vp, vp]
     lib.acm_eval_metrics_batch.argtypes = [i64, i32, i64, i64, i32, i32, i32, vp, sz, vp]
     lib.acm_select_step_batch.argtypes = [i32, vp, vp]
     for name in EXPORTED_SYMBOLS:

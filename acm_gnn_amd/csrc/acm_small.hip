@@ -395,11 +395,11 @@ __device__ __forceinline__ void write_tables(const D& d) {
 
 // ------------------------------------------------------------------------------------------------ launch 1: Z1 = drop(X) Wcat
 template <int V, class D>
-__device__ __forceinline__ void small_proj1_body(const D& d) {
+__device__ __forceinline__ void small_proj1_body(const D& d, int n_wg) {
     constexpr int F = 16 * V;
     write_tables<V>(d);
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
-    const int wave = (int)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int)gridDim.x * 4;
+    const int wave = (int)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = n_wg * 4;
     const AcmDropCtx dc = acm_drop_ctx(take(d.drop_in));
     const float* tab[3] = {d.t[0][ACM_SR_W_LOW].p, d.t[0][ACM_SR_W_HIGH].p, d.t[0][ACM_SR_W_MLP].p};
     const int ld[3] = {F, F, F};
@@ -425,11 +425,11 @@ struct Pre2 {
     fv<V> own;
 };
 template <int V, bool FOUR, bool VARIANT, class D>
-__device__ __forceinline__ void small_conv1_fwd_body(const D& d, const float* z1) {
+__device__ __forceinline__ void small_conv1_fwd_body(const D& d, const float* z1, int n_wg) {
     constexpr int F = 16 * V;
     typedef fv<V> vt;
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
-    const int wave = (int)blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = (int)gridDim.x * WAVES;
+    const int wave = (int)blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = n_wg * WAVES;
     constexpr int NCH = FOUR ? 3 : 2;
     constexpr int K = FOUR ? 4 : 3;
     const AcmDropCtx dh = acm_drop_ctx(take(d.drop_hidden));
@@ -531,10 +531,10 @@ struct Pre3 {
     int y;
 };
 template <bool FOUR, class D>
-__device__ __forceinline__ void small_conv2_fwd_body(const D& d) {
+__device__ __forceinline__ void small_conv2_fwd_body(const D& d, int n_wg) {
     __shared__ float red[WAVES][PART3_PITCH];
     const int lane = threadIdx.x & 63, c = lane & 7, wv = threadIdx.x >> 6;
-    const int wave = (int)blockIdx.x * WAVES + wv, n_waves = (int)gridDim.x * WAVES;
+    const int wave = (int)blockIdx.x * WAVES + wv, n_waves = n_wg * WAVES;
     constexpr int NQ = FOUR ? 6 : 4;
     constexpr int K = FOUR ? 4 : 3;
     const int C = d.C;
@@ -727,7 +727,7 @@ struct Pre4 {
     float mean, rstd, sa[8];
 };
 template <int V, bool FOUR, class D>
-__device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1) {
+__device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1, int n_wg) {
     constexpr int F = 16 * V, PART4 = part4_of(F), LONG4 = PART4;
     typedef fv<V> vt;
     __shared__ __attribute__((aligned(16))) float red[WAVES / 2][PART4];  // the waves' sums side by side (two rounds: 37 KB at F = 64)
@@ -735,7 +735,7 @@ __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1
     for (int e = 4 * threadIdx.x; e < 3 * F * C8; e += 4 * 64 * WAVES) st4(w2s + e, ld4(d.W2T + e));
     __syncthreads();
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15, c = lane & 7, wv = threadIdx.x >> 6;
-    const int wave = (int)blockIdx.x * WAVES + wv, n_waves = (int)gridDim.x * WAVES;
+    const int wave = (int)blockIdx.x * WAVES + wv, n_waves = n_wg * WAVES;
     constexpr int NQ = FOUR ? 6 : 4;
     constexpr int K = FOUR ? 4 : 3;
     const int C = d.C;
@@ -938,11 +938,11 @@ struct Pre5 {
     fv<V> a, b, pp, mm, vv;
 };
 template <int V, bool FOUR, bool VARIANT, class D>
-__device__ __forceinline__ void small_conv1_bwd_body(const D& d, const float* z1) {
+__device__ __forceinline__ void small_conv1_bwd_body(const D& d, const float* z1, int n_wg) {
     constexpr int F = 16 * V;
     typedef fv<V> vt;
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
-    const int wave = (int)blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = (int)gridDim.x * WAVES;
+    const int wave = (int)blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = n_wg * WAVES;
     constexpr int NCH = FOUR ? 3 : 2;
     const float* tab[3] = {d.G1, d.G1 + F, d.G1 + 2 * F};
     const int ld[3] = {3 * F, 3 * F, 3 * F};
@@ -1137,28 +1137,40 @@ __device__ __forceinline__ void small_finish_body(const D& d, int item_blocks, i
 
 // ------------------------------------------------------------------------------------------------ the kernels: single and batched forms
 // Single form: the step's SmallDev by value in the kernel arguments (acm_small_step).
-// Batched form (acm_small_batch_step): grid (the single form's x, n_slots); grid row blockIdx.y takes ITS SmallDev from a
-// device table.  The entry is read through the constant address space -- the table is written by copies between launches
-// only, never by a kernel, and the row index is wave-uniform -- so its fields arrive by scalar loads exactly as kernel
-// arguments do; the bodies are templates over the block's reference type, so both forms are the same source.
-// The body runs with the same blockIdx.x / gridDim.x as the single step, on the slot's own part3 / part4 / slots / counters
-// / latch: the same instructions in the same order, the same bits.
+// Batched form (acm_small_batch_step, acm_small_batch_step_graphs): grid (an ENVELOPE of the single forms' x, n_slots); grid
+// row blockIdx.y takes ITS SmallDev from a device table.  The entry is read through the constant address space -- the table is
+// written by copies between launches only, never by a kernel, and the row index is wave-uniform -- so its fields arrive by
+// scalar loads exactly as kernel arguments do; the bodies are templates over the block's reference type, so both forms are
+// the same source.
+// Every body takes n_wg, the producer workgroups of ITS step: the single form hands it gridDim.x, the batched form the width
+// the entry was bound with (the slot's own handles' grid).  The launched grid may be wider -- the slots of one table may
+// stand on different graphs (synthetic-experiments/train.py:64-164: ten graphs per homophily level, each with its own
+// adjacency and features), and the launch is as wide as the widest -- and the workgroups past a slot's own width return before
+// they touch LDS or a barrier (blockIdx is workgroup-uniform).  So a body runs with the blockIdx.x / n_wg of the single step,
+// on the slot's own part3 / part4 / slots / counters / latch: the same instructions in the same order, the same bits.
 struct SmallBatchEntry {
     int32_t active;                  // 0: an empty slot -- every launch returns before it touches anything else
-    int32_t key[6];                  // per launch: gridDim.x * 16 + form (four | variant << 1 | train << 2 | (F == 32) << 3) the
-    int32_t item_blocks;             // entry was bound for: a grid row of any other launch shape -- or of the other hidden width,
-                                     // whose kernels read every table at another pitch -- does nothing
+    int32_t key[6];                  // per launch: the slot's OWN grid width * 16 + form (four | variant << 1 | train << 2 |
+    int32_t item_blocks;             // (F == 32) << 3) the entry was bound for: a grid row of another form -- or of the other
+                                     // hidden width, whose kernels read every table at another pitch -- or a launch narrower
+                                     // than the slot's own width does nothing
     SmallDev first;                  // launch 1: reads the live dropout counter and latches it
     SmallDev rest;                   // launches 2-6: draw their masks with the latched copy
 };
 constexpr int FORM_NARROW = 8;       // the form's width bit: set for F = 32
+constexpr int FORM_BITS = 16;        // a key is width * FORM_BITS + form
 // V: the width the calling kernel was compiled for (it, not the host's word, decides the form's width bit); 0: a kernel
-// that is the same for every width (launch 3), which takes the bit as it is given
+// that is the same for every width (launch 3), which takes the bit as it is given.  n_wg: the slot's own width (where an
+// entry is returned, blockIdx.x < n_wg <= gridDim.x).
 template <int LAUNCH, int V>
-__device__ __forceinline__ const ACM_CONST_AS SmallBatchEntry* batch_entry(const SmallBatchEntry* table, int form) {
+__device__ __forceinline__ const ACM_CONST_AS SmallBatchEntry* batch_entry(const SmallBatchEntry* table, int form, int& n_wg) {
     const ACM_CONST_AS SmallBatchEntry* e = (const ACM_CONST_AS SmallBatchEntry*)table + blockIdx.y;
     if (V != 0) form = (form & (FORM_NARROW - 1)) | (V == 2 ? FORM_NARROW : 0);
-    if (e->active == 0 || e->key[LAUNCH] != (int)gridDim.x * 16 + form) return nullptr;
+    n_wg = 0;
+    if (e->active == 0) return nullptr;
+    const int key = e->key[LAUNCH];
+    n_wg = key / FORM_BITS;
+    if (key % FORM_BITS != form || (int)gridDim.x < n_wg || (int)blockIdx.x >= n_wg) return nullptr;
     return e;
 }
 __host__ __device__ constexpr int form_of(bool four, bool variant, bool train, int hidden) {
@@ -1166,65 +1178,80 @@ __host__ __device__ constexpr int form_of(bool four, bool variant, bool train, i
 }
 
 template <int V>
-__global__ __launch_bounds__(256) void small_proj1_kernel(SmallDev d) { small_proj1_body<V>(d); }
+__global__ __launch_bounds__(256) void small_proj1_kernel(SmallDev d) { small_proj1_body<V>(d, (int)gridDim.x); }
 template <int V>
 __global__ __launch_bounds__(256) void small_proj1_batch_kernel(const SmallBatchEntry* table, int form) {
-    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<0, V>(table, form);
+    int n_wg;
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<0, V>(table, form, n_wg);
     if (!e) return;
     const ACM_CONST_AS SmallDev& d = e->first;
-    small_proj1_body<V>(d);
+    small_proj1_body<V>(d, n_wg);
 }
 
 template <int V, bool FOUR, bool VARIANT>
-__global__ __launch_bounds__(64 * WAVES) void small_conv1_fwd_kernel(SmallDev d, const float* z1) { small_conv1_fwd_body<V, FOUR, VARIANT>(d, z1); }
+__global__ __launch_bounds__(64 * WAVES) void small_conv1_fwd_kernel(SmallDev d, const float* z1) {
+    small_conv1_fwd_body<V, FOUR, VARIANT>(d, z1, (int)gridDim.x);
+}
 template <int V, bool FOUR, bool VARIANT>
 __global__ __launch_bounds__(64 * WAVES) void small_conv1_fwd_batch_kernel(const SmallBatchEntry* table, int form) {
-    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<1, V>(table, form);
+    int n_wg;
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<1, V>(table, form, n_wg);
     if (!e) return;
     const ACM_CONST_AS SmallDev& d = e->rest;
-    small_conv1_fwd_body<V, FOUR, VARIANT>(d, d.Z1);
+    small_conv1_fwd_body<V, FOUR, VARIANT>(d, d.Z1, n_wg);
 }
 
 template <bool FOUR>
-__global__ __launch_bounds__(64 * WAVES) void small_conv2_fwd_kernel(SmallDev d) { small_conv2_fwd_body<FOUR>(d); }
+__global__ __launch_bounds__(64 * WAVES) void small_conv2_fwd_kernel(SmallDev d) { small_conv2_fwd_body<FOUR>(d, (int)gridDim.x); }
 template <bool FOUR>
 __global__ __launch_bounds__(64 * WAVES) void small_conv2_fwd_batch_kernel(const SmallBatchEntry* table, int form) {
-    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<2, 0>(table, form);
+    int n_wg;
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<2, 0>(table, form, n_wg);
     if (!e) return;
     const ACM_CONST_AS SmallDev& d = e->rest;
-    small_conv2_fwd_body<FOUR>(d);
+    small_conv2_fwd_body<FOUR>(d, n_wg);
 }
 
 template <int V, bool FOUR>
-__global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_kernel(SmallDev d, const float* z1) { small_conv2_bwd_body<V, FOUR>(d, z1); }
+__global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_kernel(SmallDev d, const float* z1) {
+    small_conv2_bwd_body<V, FOUR>(d, z1, (int)gridDim.x);
+}
 template <int V, bool FOUR>
 __global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_batch_kernel(const SmallBatchEntry* table, int form) {
-    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<3, V>(table, form);
+    int n_wg;
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<3, V>(table, form, n_wg);
     if (!e) return;
     const ACM_CONST_AS SmallDev& d = e->rest;
-    small_conv2_bwd_body<V, FOUR>(d, d.Z1);
+    small_conv2_bwd_body<V, FOUR>(d, d.Z1, n_wg);
 }
 
 template <int V, bool FOUR, bool VARIANT>
-__global__ __launch_bounds__(64 * WAVES) void small_conv1_bwd_kernel(SmallDev d, const float* z1) { small_conv1_bwd_body<V, FOUR, VARIANT>(d, z1); }
+__global__ __launch_bounds__(64 * WAVES) void small_conv1_bwd_kernel(SmallDev d, const float* z1) {
+    small_conv1_bwd_body<V, FOUR, VARIANT>(d, z1, (int)gridDim.x);
+}
 template <int V, bool FOUR, bool VARIANT>
 __global__ __launch_bounds__(64 * WAVES) void small_conv1_bwd_batch_kernel(const SmallBatchEntry* table, int form) {
-    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<4, V>(table, form);
+    int n_wg;
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<4, V>(table, form, n_wg);
     if (!e) return;
     const ACM_CONST_AS SmallDev& d = e->rest;
-    small_conv1_bwd_body<V, FOUR, VARIANT>(d, d.Z1);
+    small_conv1_bwd_body<V, FOUR, VARIANT>(d, d.Z1, n_wg);
 }
 
 template <int V>
 __global__ __launch_bounds__(256) void small_finish_kernel(SmallDev d, int item_blocks, int red_blocks) { small_finish_body<V>(d, item_blocks, red_blocks); }
-// (three waves per SIMD like the single form: without the hint the table pointer costs four registers and an occupancy step)
 // Three waves per SIMD like the single form.  Left alone the compiler takes 172 registers here (the single form: 168, the
-// limit for three waves) and drops to two; held to three it parks two loop-invariant addresses in scratch (20 bytes per lane:
-// stored once per wave, read back once per work item).  EXPERIMENTS.md has the table.
+// limit for three waves) and drops to two; held to three it parks loop-invariant addresses in scratch (stored once per
+// wave, read back once per work item).  EXPERIMENTS.md has the table.
+// The slot's own width here is its own item_blocks + red_blocks (red_blocks depends on the hidden width alone): the reducing
+// blocks follow the SLOT's item blocks, wherever the envelope's end.
 template <int V>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void small_finish_batch_kernel(const SmallBatchEntry* table, int form, int item_blocks, int red_blocks) {
-    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<5, V>(table, form);
-    if (!e || e->item_blocks != item_blocks) return;
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void small_finish_batch_kernel(const SmallBatchEntry* table, int form, int red_blocks) {
+    int n_wg;
+    const ACM_CONST_AS SmallBatchEntry* e = batch_entry<5, V>(table, form, n_wg);
+    if (!e) return;
+    const int item_blocks = e->item_blocks;
+    if (item_blocks + red_blocks != n_wg) return;
     const ACM_CONST_AS SmallDev& d = e->rest;
     small_finish_body<V>(d, item_blocks, red_blocks);
 }
@@ -1283,7 +1310,9 @@ extern "C" int acm_small_step_workspace_bytes(const acm_csr_t* a_low, const acm_
 
 namespace {
 
-// The grids of the six launches: functions of the handles and the hidden width alone, so the same for every slot of a batch.
+// The grids of the six launches: functions of the handles and the hidden width alone -- the same for every slot of a batch on
+// one graph; where the slots stand on different graphs, each slot's own (its table entry records them) under a launch of
+// their element-wise maximum (acm_small_batch_grids_t).
 struct Grids {
     int proj, wide, graph, item_blocks, red_blocks;
 };
@@ -1428,29 +1457,50 @@ extern "C" int acm_small_batch_table_bytes(int32_t n_slots, size_t* bytes) {
     return ACM_OK;
 }
 
-extern "C" int acm_small_batch_bind(const acm_csr_t* a, const acm_csr_t* x, const acm_csr_t* xt, int32_t n_slots,
-                                    const acm_small_step_t* const* slots, void* table, size_t table_bytes, acm_stream_t stream) {
-    // what needs neither a handle nor a device first (acm_small_batch_host.h): count, shared fields, overlaps
-    char msg[256];
-    const int st0 = acm_small_batch_check_slots(n_slots, slots, a ? a->n_rows : 0, msg, sizeof(msg));
-    ACM_REQUIRE(st0 == ACM_OK, st0, "%s", msg);
-    ACM_REQUIRE(table, ACM_EINVAL, "acm_small_batch_bind: NULL table");
-    ACM_REQUIRE(table_bytes >= (size_t)n_slots * sizeof(SmallBatchEntry), ACM_ESHAPE, "acm_small_batch_bind: table of %zu bytes, %zu needed",
-                table_bytes, (size_t)n_slots * sizeof(SmallBatchEntry));
-    ACM_REQUIRE(a, ACM_EINVAL, "acm_small_batch_bind: NULL operator handle");
+namespace {
+
+Grids envelope_of(const acm_small_batch_grids_t& g) { return Grids{g.proj, g.wide, g.graph, g.item_blocks, g.red_blocks}; }
+void fold_max(acm_small_batch_grids_t& into, const Grids& g) {
+    into.proj = std::max(into.proj, g.proj), into.wide = std::max(into.wide, g.wide), into.graph = std::max(into.graph, g.graph);
+    into.item_blocks = std::max(into.item_blocks, g.item_blocks), into.red_blocks = std::max(into.red_blocks, g.red_blocks);
+}
+// the six launch widths of a set of grids
+void widths_of(const Grids& g, int (&w)[6]) {
+    w[0] = g.proj, w[1] = g.wide, w[2] = g.graph, w[3] = g.graph, w[4] = g.wide, w[5] = g.item_blocks + g.red_blocks;
+}
+
+// Builds and writes the table: slot i's entry from ITS handles (a[i], x[i], xt[i]) -- its workspace carve-up, its nwg3 / nwg4,
+// its long rows, its own grid widths -- and, with an envelope, the refusal of a slot whose own grid exceeds it in any launch.
+// The caller has run the handle-free checks.  Nothing is copied or launched before every slot has passed.
+int batch_bind_impl(const char* who, int32_t n_slots, const acm_csr* const* a, const acm_csr* const* x, const acm_csr* const* xt,
+                    const acm_small_step_t* const* slots, const acm_small_batch_grids_t* env, void* table, size_t table_bytes,
+                    acm_stream_t stream) {
+    ACM_REQUIRE(table, ACM_EINVAL, "%s: NULL table", who);
+    ACM_REQUIRE(table_bytes >= (size_t)n_slots * sizeof(SmallBatchEntry), ACM_ESHAPE, "%s: table of %zu bytes, %zu needed", who, table_bytes,
+                (size_t)n_slots * sizeof(SmallBatchEntry));
     std::vector<SmallBatchEntry> host((size_t)n_slots);
     for (int i = 0; i < n_slots; ++i) {
         SmallBatchEntry& e = host[(size_t)i];
         e = SmallBatchEntry{};
         const acm_small_step_t* p = slots[i];
         if (!p) continue;
-        const int st = small_prepare(a, x, xt, p, e.first, e.rest);
+        ACM_REQUIRE(a[i], ACM_EINVAL, "%s: NULL operator handle (slot %d)", who, i);
+        const int st = small_prepare(a[i], x[i], xt[i], p, e.first, e.rest);
         if (st != ACM_OK) return st;
         const int hidden = acm_small_hidden_of(p);
-        const Grids gr = grids_of(a, x, xt, p->train != 0, hidden);
+        const Grids gr = grids_of(a[i], x[i], xt[i], p->train != 0, hidden);
         const int form = form_of(p->n_channels == 4, p->relu_before != 0, p->train != 0, hidden);
-        const int gx[6] = {gr.proj, gr.wide, gr.graph, gr.graph, gr.wide, gr.item_blocks + gr.red_blocks};
-        for (int l = 0; l < 6; ++l) e.key[l] = gx[l] * 16 + form;
+        int gx[6];
+        widths_of(gr, gx);
+        if (env) {
+            int ex[6];
+            widths_of(envelope_of(*env), ex);
+            for (int l = 0; l < 6; ++l)
+                ACM_REQUIRE(gx[l] <= ex[l] && gr.red_blocks == env->red_blocks, ACM_ESHAPE,
+                            "%s: slot %d needs %d workgroups in launch %d, the batch's grids have %d (fold every run's handles into the "
+                            "grids with acm_small_batch_grids before the first bind)", who, i, gx[l], l + 1, ex[l]);
+        }
+        for (int l = 0; l < 6; ++l) e.key[l] = gx[l] * FORM_BITS + form;
         e.item_blocks = gr.item_blocks;
         e.active = 1;
     }
@@ -1460,16 +1510,12 @@ extern "C" int acm_small_batch_bind(const acm_csr_t* a, const acm_csr_t* x, cons
     return ACM_OK;
 }
 
-extern "C" int acm_small_batch_step(const acm_csr_t* a, const acm_csr_t* x, const acm_csr_t* xt, int32_t n_slots,
-                                    const acm_small_step_t* shape, const void* table, acm_stream_t stream) {
-    const int st = batch_shape_check(a, x, xt, n_slots, shape);
-    if (st != ACM_OK) return st;
-    ACM_REQUIRE(table, ACM_EINVAL, "acm_small_batch_step: NULL table");
+// The six (train = 0: three) batched launches on grids (gr's x, n_slots).
+int batch_launch(const char* who, int32_t n_slots, const acm_small_step_t* shape, const Grids& gr, const void* table, acm_stream_t stream) {
     const SmallBatchEntry* tb = (const SmallBatchEntry*)table;
     hipStream_t s = (hipStream_t)stream;
     const bool train = shape->train != 0, four = shape->n_channels == 4, variant = shape->relu_before != 0;
     const int hidden = acm_small_hidden_of(shape);
-    const Grids gr = grids_of(a, x, xt, train, hidden);
     const int form = form_of(four, variant, train, hidden);
     const unsigned B = (unsigned)n_slots;
     const dim3 wide(gr.wide, B), graph(gr.graph, B), blk(64 * WAVES);
@@ -1486,12 +1532,75 @@ extern "C" int acm_small_batch_step(const acm_csr_t* a, const acm_csr_t* x, cons
             // launch 5
             hipLaunchKernelGGL((small_conv1_bwd_batch_kernel<v(), four_c(), variant_c()>), wide, blk, 0, s, tb, form);
             // launch 6
-            hipLaunchKernelGGL(small_finish_batch_kernel<v()>, dim3(gr.item_blocks + gr.red_blocks, B), dim3(256), 0, s, tb, form,
-                               gr.item_blocks, gr.red_blocks);
+            hipLaunchKernelGGL(small_finish_batch_kernel<v()>, dim3(gr.item_blocks + gr.red_blocks, B), dim3(256), 0, s, tb, form, gr.red_blocks);
         }
         return ACM_OK;
     }, acm_one_of<2, 4>(hidden / 16), acm_flag(four), acm_flag(variant));
-    ACM_REQUIRE(picked != ACM_NO_INSTANTIATION, ACM_EUNSUPPORTED, "acm_small_batch_step: no kernels for hidden width %d", hidden);
+    ACM_REQUIRE(picked != ACM_NO_INSTANTIATION, ACM_EUNSUPPORTED, "%s: no kernels for hidden width %d", who, hidden);
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
+}
+
+}  // namespace
+
+// The special case "the same handles in every slot, the envelope = their own grids".
+extern "C" int acm_small_batch_bind(const acm_csr_t* a, const acm_csr_t* x, const acm_csr_t* xt, int32_t n_slots,
+                                    const acm_small_step_t* const* slots, void* table, size_t table_bytes, acm_stream_t stream) {
+    // what needs neither a handle nor a device first (acm_small_batch_host.h): count, shared fields, overlaps
+    char msg[256];
+    const int st0 = acm_small_batch_check_slots(n_slots, slots, a ? a->n_rows : 0, msg, sizeof(msg));
+    ACM_REQUIRE(st0 == ACM_OK, st0, "%s", msg);
+    const std::vector<const acm_csr*> av((size_t)n_slots, a), xv((size_t)n_slots, x), xtv((size_t)n_slots, xt);
+    return batch_bind_impl("acm_small_batch_bind", n_slots, av.data(), xv.data(), xtv.data(), slots, nullptr, table, table_bytes, stream);
+}
+
+extern "C" int acm_small_batch_step(const acm_csr_t* a, const acm_csr_t* x, const acm_csr_t* xt, int32_t n_slots,
+                                    const acm_small_step_t* shape, const void* table, acm_stream_t stream) {
+    const int st = batch_shape_check(a, x, xt, n_slots, shape);
+    if (st != ACM_OK) return st;
+    ACM_REQUIRE(table, ACM_EINVAL, "acm_small_batch_step: NULL table");
+    return batch_launch("acm_small_batch_step", n_slots, shape, grids_of(a, x, xt, shape->train != 0, acm_small_hidden_of(shape)), table, stream);
+}
+
+// ---- slots on different graphs (synthetic-experiments/train.py:64-164)
+extern "C" int acm_small_batch_grids(const acm_csr_t* a, const acm_csr_t* x, const acm_csr_t* xt, const acm_small_step_t* shape,
+                                     acm_small_batch_grids_t* grids) {
+    ACM_REQUIRE(grids, ACM_EINVAL, "acm_small_batch_grids: NULL grids");
+    const int st = batch_shape_check(a, x, xt, 1, shape);
+    if (st != ACM_OK) return st;
+    fold_max(*grids, grids_of(a, x, xt, shape->train != 0, acm_small_hidden_of(shape)));
+    return ACM_OK;
+}
+
+extern "C" int acm_small_batch_bind_graphs(int32_t n_slots, const acm_csr_t* const* a, const acm_csr_t* const* x, const acm_csr_t* const* xt,
+                                           const acm_small_step_t* const* slots, const acm_small_batch_grids_t* grids, void* table,
+                                           size_t table_bytes, acm_stream_t stream) {
+    ACM_REQUIRE(n_slots < 1 || n_slots > ACM_SMALL_BATCH_MAX || (a && x && xt), ACM_EINVAL,
+                "acm_small_batch_bind_graphs: NULL handle array (a_low, x and x_t are host arrays of n_slots handles)");
+    ACM_REQUIRE(grids, ACM_EINVAL, "acm_small_batch_bind_graphs: NULL grids");
+    int64_t rows[ACM_SMALL_BATCH_MAX];
+    if (n_slots >= 1 && n_slots <= ACM_SMALL_BATCH_MAX)
+        for (int i = 0; i < n_slots; ++i) rows[i] = a[i] ? a[i]->n_rows : 0;
+    char msg[256];
+    const int st0 = acm_small_batch_check_slots_graphs(n_slots, slots, rows, msg, sizeof(msg));
+    ACM_REQUIRE(st0 == ACM_OK, st0, "%s", msg);
+    return batch_bind_impl("acm_small_batch_bind_graphs", n_slots, a, x, xt, slots, grids, table, table_bytes, stream);
+}
+
+extern "C" int acm_small_batch_step_graphs(int32_t n_slots, const acm_small_step_t* shape, const acm_small_batch_grids_t* grids,
+                                           const void* table, acm_stream_t stream) {
+    ACM_REQUIRE(n_slots >= 1, ACM_EINVAL, "acm_small_batch: n_slots must be 1 .. %d (got %d)", ACM_SMALL_BATCH_MAX, (int)n_slots);
+    ACM_REQUIRE(n_slots <= ACM_SMALL_BATCH_MAX, ACM_EUNSUPPORTED, "acm_small_batch: n_slots %d > %d slots of one table", (int)n_slots,
+                ACM_SMALL_BATCH_MAX);
+    ACM_REQUIRE(shape && grids && table, ACM_EINVAL, "acm_small_batch_step_graphs: NULL argument");
+    ACM_REQUIRE(acm_small_hidden_ok(shape->hidden), ACM_EUNSUPPORTED, "acm_small_batch: hidden width %d (32 or 64; 0 means 64)", (int)shape->hidden);
+    ACM_REQUIRE(shape->n_channels == 3 || shape->n_channels == 4, ACM_EINVAL, "acm_small_batch: n_channels must be 3 or 4");
+    const Grids gr = envelope_of(*grids);
+    const int PART4 = part4_of(acm_small_hidden_of(shape));
+    // what grids_of can produce, and nothing else: a launch never gets a width the caller made up
+    ACM_REQUIRE(gr.proj >= 1 && gr.proj <= 2 * MAX_WG && gr.wide >= 1 && gr.wide <= MAX_WG_WIDE && gr.graph >= 1 && gr.graph <= MAX_WG &&
+                    gr.item_blocks >= 0 && gr.item_blocks <= 2 * MAX_WG && (shape->train != 0 || gr.item_blocks == 0) &&
+                    gr.red_blocks == (PART4 + PART3 + RED_EL - 1) / RED_EL,
+                ACM_ESHAPE, "acm_small_batch_step_graphs: grids that acm_small_batch_grids did not form for this shape");
+    return batch_launch("acm_small_batch_step_graphs", n_slots, shape, gr, table, stream);
 }

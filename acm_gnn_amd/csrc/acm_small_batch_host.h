@@ -2,7 +2,7 @@
 // fields every slot of a batch must share (they choose the kernel templates and the grids, which are per LAUNCH, not per
 // slot) and the ranges no two runs may share (each run's workspace, logits and loss are written by its own grid row).
 // Plain host C++ over include/acm_hip.h, so a stand-alone program can drive it under the host sanitizers
-// (tests/c_abi/small_batch_host.cpp); csrc/acm_small.hip calls the same function.
+// (tests/c_abi/small_batch_host.cpp, tests/c_abi/small_graphs_host.cpp); csrc/acm_small.hip calls the same functions.
 #ifndef ACM_SMALL_BATCH_HOST_H
 #define ACM_SMALL_BATCH_HOST_H
 #include <stddef.h>
@@ -23,9 +23,15 @@ inline bool acm_ranges_overlap(uintptr_t a, size_t alen, uintptr_t b, size_t ble
     return a < b ? (size_t)(b - a) < alen : (size_t)(a - b) < blen;
 }
 
-// ACM_OK, or the status of the first objection with its text in msg.  n_rows: rows of the operator (the logits of a slot are
-// n_rows x n_classes floats); <= 0 counts as one row.
-inline int acm_small_batch_check_slots(int n_slots, const acm_small_step_t* const* slots, int64_t n_rows, char* msg, size_t msg_len) {
+// ACM_OK, or the status of the first objection with its text in msg.  One implementation for the two flavours of a batch:
+//   slot_rows == NULL  every slot on ONE graph of n_rows rows (acm_small_batch_bind): the feature values, their transposed
+//                      copy and order, and the row scale are shared too;
+//   slot_rows != NULL  a graph PER SLOT (acm_small_batch_bind_graphs; synthetic-experiments/train.py:64-164): slot_rows[i] is
+//                      the row count of slot i's operator, which must agree across the active slots (the metrics launch
+//                      behind the step shares it); the four feature / operator pointers may differ.
+// The logits of a slot are rows x n_classes floats; a row count <= 0 counts as one row.
+inline int acm_small_batch_check_slots_impl(int n_slots, const acm_small_step_t* const* slots, int64_t n_rows, const int64_t* slot_rows,
+                                            char* msg, size_t msg_len) {
     if (n_slots < 1) {
         snprintf(msg, msg_len, "acm_small_batch: n_slots must be 1 .. %d (got %d)", ACM_SMALL_BATCH_MAX, n_slots);
         return ACM_EINVAL;
@@ -61,7 +67,9 @@ inline int acm_small_batch_check_slots(int n_slots, const acm_small_step_t* cons
         else if (p->update != s->update) what = "update";
         else if (p->f_in != s->f_in) what = "f_in";
         else if (acm_small_hidden_of(p) != acm_small_hidden_of(s)) what = "hidden";
-        else if (p->x_vals != s->x_vals) what = "x_vals";
+        else if (slot_rows) {
+            if (slot_rows[i] != slot_rows[first]) what = "n_rows";
+        } else if (p->x_vals != s->x_vals) what = "x_vals";
         else if (p->xt_vals != s->xt_vals) what = "xt_vals";
         else if (p->xt_src_pos != s->xt_src_pos) what = "xt_src_pos";
         else if (p->row_scale != s->row_scale) what = "row_scale";
@@ -70,6 +78,7 @@ inline int acm_small_batch_check_slots(int n_slots, const acm_small_step_t* cons
             return ACM_EINVAL;
         }
     }
+    if (slot_rows) n_rows = slot_rows[first];           // (equal in every active slot by now)
     const size_t rows = n_rows > 0 ? (size_t)n_rows : 1;
     static const char* const kind[3] = {"workspace", "logits", "loss"};
     for (int i = first; i < n_slots; ++i) {
@@ -94,6 +103,21 @@ inline int acm_small_batch_check_slots(int n_slots, const acm_small_step_t* cons
         }
     }
     return ACM_OK;
+}
+
+// every slot on one graph of n_rows rows
+inline int acm_small_batch_check_slots(int n_slots, const acm_small_step_t* const* slots, int64_t n_rows, char* msg, size_t msg_len) {
+    return acm_small_batch_check_slots_impl(n_slots, slots, n_rows, nullptr, msg, msg_len);
+}
+
+// a graph per slot: slot_rows is a host array of n_slots row counts (entries of empty slots are not read)
+inline int acm_small_batch_check_slots_graphs(int n_slots, const acm_small_step_t* const* slots, const int64_t* slot_rows, char* msg,
+                                              size_t msg_len) {
+    if (!slot_rows) {
+        snprintf(msg, msg_len, "acm_small_batch: NULL row-count array");
+        return ACM_EINVAL;
+    }
+    return acm_small_batch_check_slots_impl(n_slots, slots, 0, slot_rows, msg, msg_len);
 }
 
 #endif  // ACM_SMALL_BATCH_HOST_H

@@ -146,7 +146,7 @@ def _upload(table, host):
 
 class BatchMetrics:
     """``acm_eval_metrics`` for the slots of a batch of runs on one graph as ONE launch (acm_eval_metrics_batch): per-slot
-    logits and set weights, shared labels; results ``out[slot] = [m_tr, m_va, m_te, val_loss]`` and workspaces allocated as
+    logits and set weights, labels shared or -- runs on different graphs of one row count -- per slot; results ``out[slot] = [m_tr, m_va, m_te, val_loss]`` and workspaces allocated as
     one block.  The per-slot argument blocks live in a device table, so a captured launch survives :meth:`set_slot`."""
 
     def __init__(self, n_slots, n_rows, n_classes, n_sets, labels, loss_set=1):
@@ -164,8 +164,9 @@ class BatchMetrics:
         self.table = torch.zeros(C.sizeof(self._host), dtype=torch.uint8, device=dev)
         self._keep = [None] * self.n_slots
 
-    def set_slot(self, i, logits=None, weights=None):
-        """Slot ``i`` evaluates ``logits`` [n, C] on the sets ``weights`` [k, n]; None: an empty slot.  :meth:`flush` uploads."""
+    def set_slot(self, i, logits=None, weights=None, labels=None):
+        """Slot ``i`` evaluates ``logits`` [n, C] on the sets ``weights`` [k, n] against ``labels`` (None: the shared tensor of
+        the constructor); ``logits`` None: an empty slot.  :meth:`flush` uploads."""
         e = self._host[i]
         if logits is None:
             e.logits = e.weights = e.labels = e.out = e.workspace = None
@@ -177,9 +178,15 @@ class BatchMetrics:
             raise ValueError(f"BatchMetrics: logits must be contiguous fp32 [{self.n}, {self.c}] on {self.device}")
         if weights.dtype != _F32 or tuple(weights.shape) != (self.k, self.n) or not weights.is_contiguous() or weights.device != self.device:
             raise ValueError(f"BatchMetrics: weights must be contiguous fp32 [{self.k}, {self.n}] on {self.device}")
-        e.logits, e.weights, e.labels = logits.data_ptr(), weights.data_ptr(), self.labels.data_ptr()
+        if labels is None:
+            labels = self.labels
+        else:
+            _check_device(labels, "labels")
+            if labels.dtype != torch.int64 or tuple(labels.shape) != (self.n,) or not labels.is_contiguous() or labels.device != self.device:
+                raise ValueError(f"BatchMetrics: a slot's labels must be a contiguous int64 [{self.n}] tensor on {self.device}")
+        e.logits, e.weights, e.labels = logits.data_ptr(), weights.data_ptr(), labels.data_ptr()
         e.out, e.workspace = self.out[i].data_ptr(), self.ws[i].data_ptr()
-        self._keep[i] = (logits, weights)
+        self._keep[i] = (logits, weights, labels)
 
     def flush(self):
         _upload(self.table, self._host)

@@ -374,8 +374,8 @@ class SmallBatch:
     def _state(self):
         return tuple(bytes(p.p) if p is not None else None for p in self.plans)
 
-    def bind(self):
-        """Write the table from the plans as they are now (not capturable)."""
+    def _fill_slots(self):
+        """The plans' blocks as they are now into the host array of slot pointers (None: an empty slot)."""
         for i, p in enumerate(self.plans):
             if p is not None:
                 if p.stale():
@@ -385,6 +385,10 @@ class SmallBatch:
                 for layer, att in ((l0, p.att1), (l1, p.att2)):
                     layer._att_raw, layer._att_inv, layer._att_k = att, None, p.cfg.n_channels
             self._slots[i] = C.pointer(p.p) if p is not None else None
+
+    def bind(self):
+        """Write the table from the plans as they are now (not capturable)."""
+        self._fill_slots()
         dev = self.table.device
         with _device_ctx(dev):
             st = _lib.load().acm_small_batch_bind(self.low.handle, self.x.csr.handle, self._xt.handle if self._xt is not None else None,
@@ -413,3 +417,97 @@ class SmallBatch:
             st = _lib.load().acm_small_batch_step(self.low.handle, self.x.csr.handle, self._xt.handle if self._xt is not None else None,
                                                   self.n_slots, C.byref(self._first().p), self.table.data_ptr(), _stream())
         _lib.check(st, "acm_small_batch_step")
+
+
+def _handle_value(h):
+    return h.value if isinstance(h, C.c_void_p) else h
+
+
+class SmallGraphBatch(SmallBatch):
+    """B <= 32 :class:`SmallPlan` s on DIFFERENT graphs in ONE set of six (three) launches (``acm_small_batch_step_graphs``):
+    the runs of synthetic-experiments/train.py:64-164, which trains on ten generated graphs per edge-homophily level, each
+    with its own adjacency, features, labels and split.  The plans must agree in the number of rows, ``f_in``, the class
+    count, the model configuration and the hidden width; operator, features, row scale, labels and weights are per slot.
+    Grid row k is still plan k's single step, bit for bit: a slot's table entry is made from ITS handles, so it loops with
+    its own workgroup counts over its own workspace; the launches are as wide as the widest run and the workgroups past a
+    slot's own width return at once.
+
+    ``handles``: ``(operator, features, transposed features or None)`` of EVERY run that will ever hold a slot
+    (:meth:`handles_of`), beside those of ``plans``: their launch widths fold into ``self.grids``, the envelope a captured
+    ``run()`` bakes in.  ``set_slot`` then hands a slot to a run on another graph by table bytes; a plan whose graph needs a
+    wider launch than the envelope is refused with the library's message (and the slot keeps its run)."""
+
+    @staticmethod
+    def handles_of(x, ops, train):
+        """The handles a :class:`SmallPlan` over (x, ops) walks, without building the plan."""
+        return SmallPlan._operator(ops), x.csr, (x.csr_t if train else None)
+
+    @staticmethod
+    def why_not(plans):
+        """None if the plans can share launches, else the first reason they cannot (a string)."""
+        plans = [p for p in plans if p is not None]
+        if not plans:
+            return "no plan"
+        if len(plans) > _lib.SMALL_BATCH_MAX:
+            return f"{len(plans)} plans (<= {_lib.SMALL_BATCH_MAX} slots)"
+        first = plans[0]
+        for p in plans[1:]:
+            if (p.cfg.n_channels, p.cfg.relu_before, p.cfg.layernorm, p.cfg.scale) != \
+                    (first.cfg.n_channels, first.cfg.relu_before, first.cfg.layernorm, first.cfg.scale):
+                return "the models are configured differently"
+            if p.hidden != first.hidden:
+                return f"hidden widths {p.hidden} and {first.hidden}: the models are configured differently"
+            if p.C != first.C:
+                return f"{p.C} and {first.C} classes"
+            if p.n != first.n:
+                return f"graphs of {p.n} and {first.n} rows (one row count per batch)"
+            if p.p.f_in != first.p.f_in:
+                return f"{p.p.f_in} and {first.p.f_in} input features"
+            if (p.train, p.update) != (first.train, first.update):
+                return "training and evaluation plans (or updating and gradient-only plans) mixed"
+        return None
+
+    def __init__(self, plans, n_slots=None, handles=None):
+        super().__init__(plans, n_slots)
+        lib, first = _lib.load(), self._first()
+        self.grids = _lib.SmallBatchGrids()
+        for low, xc, xt in list(handles or []) + [(p.low, p.x.csr, p._xt) for p in self.plans if p is not None]:
+            if low.n_rows != first.n:
+                raise ValueError(f"SmallGraphBatch: graphs of {low.n_rows} and {first.n} rows (one row count per batch)")
+            _lib.check(lib.acm_small_batch_grids(low.handle, xc.handle, xt.handle if xt is not None else None, C.byref(first.p),
+                                                 C.byref(self.grids)), "acm_small_batch_grids")
+        self._a, self._x, self._t = ((C.c_void_p * self.n_slots)() for _ in range(3))
+
+    def set_slot(self, i, plan):
+        held = self.plans[i]
+        try:
+            super().set_slot(i, plan)
+        except Exception:
+            self.plans[i] = held              # (a refused bind wrote nothing: the table still holds the run before)
+            raise
+
+    def bind(self):
+        """Write the table from the plans as they are now, every slot from its own handles (not capturable)."""
+        self._fill_slots()
+        for i, p in enumerate(self.plans):
+            self._a[i] = _handle_value(p.low.handle) if p is not None else None
+            self._x[i] = _handle_value(p.x.csr.handle) if p is not None else None
+            self._t[i] = _handle_value(p._xt.handle) if p is not None and p._xt is not None else None
+        with _device_ctx(self.table.device):
+            st = _lib.load().acm_small_batch_bind_graphs(self.n_slots, self._a, self._x, self._t, self._slots, C.byref(self.grids),
+                                                         self.table.data_ptr(), self.table.numel(), _stream())
+        _lib.check(st, "acm_small_batch_bind_graphs")
+        self._bound = self._state()
+
+    def run(self):
+        """One call = every slot's step (training plans) or forward (evaluation plans), each on its own graph."""
+        capturing = self.table.is_cuda and torch.cuda.is_current_stream_capturing()
+        if not capturing and self._changed():
+            self.bind()
+        if self._bound is None:
+            raise RuntimeError("SmallGraphBatch.run: bind() the table before capturing a run")
+        from .functional import _Timed
+        with _device_ctx(self.table.device), _Timed("small_batch_step" if self.train else "small_batch_forward"):
+            st = _lib.load().acm_small_batch_step_graphs(self.n_slots, C.byref(self._first().p), C.byref(self.grids),
+                                                         self.table.data_ptr(), _stream())
+        _lib.check(st, "acm_small_batch_step_graphs")

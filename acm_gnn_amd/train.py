@@ -16,6 +16,7 @@ cannot run.
                      stays on the device across epochs (functional.SelectionState) and the selected model is returned.
 * ``fit_concurrent`` several runs of ``fit`` on the same graph, ``streams`` at a time, each on a stream of its own.
 * ``fit_batched``    several runs on the same small graph, ``batch`` at a time in the same launches (small.SmallBatch).
+* ``fit_batched_graphs`` the same for runs on DIFFERENT small graphs of one row count (small.SmallGraphBatch).
 
 Stated once for all of them: the model call (``_call_model``), the capture (``_captured``), the epoch loop (``_drive``) around
 ``enqueue`` / ``finished`` / ``result`` and the construction of a run (``_new_run``).
@@ -1034,7 +1035,7 @@ def fit_batched(runs, x, adj, labels, epochs, rule="min_val_loss", early_stoppin
     # every run against the envelope before anything is built: the fallback is decided here, not in the middle of the loop
     why, batched = _outside_batched_envelope(runs, xs, ops), None
     if why is None:
-        batched = _BatchedRuns(runs, xs, ops, labels, epochs, rule, early_stopping, min(batch, len(runs)), fused_dropout)
+        batched = _BatchedRuns(runs, [(xs, ops, labels)] * len(runs), epochs, rule, early_stopping, min(batch, len(runs)), fused_dropout)
         why = batched.refused                         # (what only the built plans can tell)
     if why is not None:
         fit_batched.last_refusal = why
@@ -1046,45 +1047,108 @@ def fit_batched(runs, x, adj, labels, epochs, rule="min_val_loss", early_stoppin
 fit_batched.last_refusal = None
 
 
+def fit_batched_graphs(runs, epochs, rule="min_val_loss", early_stopping=0, batch=DEFAULT_BATCH, sync_every=32, fused_dropout=None):
+    """``fit_batched`` for runs on DIFFERENT graphs: the synthetic study (synthetic-experiments/train.py:64-164) trains on ten
+    generated graphs per edge-homophily level, each with its own adjacency, its own features and its own split, times the
+    models and a dropout x weight-decay grid.  ``runs``: ``[(model, optimizer, x, adj, labels, train_idx, val_idx, test_idx)]``;
+    graphs of one row count, one input width, one class count and models of one configuration and hidden width share the
+    launches (small.SmallGraphBatch: the launches are as wide as the widest graph's, every slot loops with its own widths).
+    Runs that name the same ``x`` and ``adj`` objects share their operator set and features.
+
+    Returns ``[(selected, history)]`` in the order of ``runs``; each equals ``fit(..., use_graph=True, sync_every=sync_every)``
+    of that run alone, bit for bit.  The epoch loop, the hand-over of a slot and the capture are ``fit_batched``'s.  Where the
+    runs cannot share launches the call is ``fit`` run by run and the reason is left in ``fit_batched_graphs.last_refusal``
+    (None otherwise).  ``keep_best``, ``criterion="bce"`` and ``metric="rocauc"`` are not implemented here: use ``fit``."""
+    _resident_loop(sync_every, False)
+    batch = int(batch)
+    if not 1 <= batch <= _lib.SMALL_BATCH_MAX:
+        raise ValueError(f"fit_batched_graphs: batch must be 1 .. {_lib.SMALL_BATCH_MAX}, not {batch}")
+    fit_batched_graphs.last_refusal = None
+    if int(epochs) < 1 or not runs:
+        return [(0.0, []) for _ in runs]
+    made, inputs = {}, []
+    for model, _, x, adj, labels, _, _, _ in runs:
+        key = (id(x), id(adj))
+        if key not in made:                           # one operator set and one feature object per graph, as in fit_batched
+            ops, xs = (adj, x) if _is_sharded(adj) else _operators_and_features(model, x, adj, None, adj)
+            made[key] = (xs, ops)
+        inputs.append(made[key] + (labels,))
+    own = [(model, opt, tr, va, te) for model, opt, _, _, _, tr, va, te in runs]
+    # every run against the envelope before anything is built, as in fit_batched
+    why, batched = _outside_graphs_envelope(own, inputs), None
+    if why is None:
+        batched = _BatchedRuns(own, inputs, epochs, rule, early_stopping, min(batch, len(runs)), fused_dropout, graphs=True)
+        why = batched.refused
+    if why is not None:
+        fit_batched_graphs.last_refusal = why
+        return [fit(model, opt, x, adj, labels, tr, va, te, epochs, rule=rule, early_stopping=early_stopping, use_graph=True,
+                    fused_dropout=fused_dropout, sync_every=sync_every) for model, opt, x, adj, labels, tr, va, te in runs]
+    return _drive(batched, sync_every)
+
+
+fit_batched_graphs.last_refusal = None
+
+
 def _outside_batched_envelope(runs, xs, ops):
     """Why ``fit_batched`` cannot train ``runs`` in the same launches (it then calls ``fit_concurrent``), or None: every run
     inside the fused small-graph step's envelope, all of them configured alike."""
-    from .small import SmallPlan
     if _is_sharded(ops):
         return "row-sharded operators"
+    return _outside_graphs_envelope(runs, [(xs, ops, None)] * len(runs))
+
+
+def _outside_graphs_envelope(runs, inputs):
+    """``_outside_batched_envelope`` with run k on ``inputs[k]`` = (features, operators, labels): every run inside the fused
+    small-graph step's envelope on ITS graph, all models configured alike, all graphs of one row count and one input width."""
+    from .small import SmallPlan
     shape0 = None
-    for k, (model, opt, _, _, _) in enumerate(runs):
-        why = SmallPlan.why_not(model, xs, ops, opt, need_dropout_state=False)
+    for k, ((model, opt, _, _, _), (xs, ops, _)) in enumerate(zip(runs, inputs)):
+        why = "row-sharded operators" if _is_sharded(ops) else SmallPlan.why_not(model, xs, ops, opt, need_dropout_state=False)
         if why is None:
             cfg = model.gcns[0]._config()
             shape = (cfg.n_channels, cfg.relu_before, cfg.layernorm, cfg.scale, model.gcns[1].out_features, model.gcns[0].out_features)
-            shape0 = shape if shape0 is None else shape0
+            size = (ops.low.n_rows, xs.shape[1])
+            shape0, size0 = (shape, size) if shape0 is None else (shape0, size0)
             if shape != shape0:
                 why = "the models are configured differently"
                 if shape[-1] != shape0[-1]:
                     why = f"hidden width {shape[-1]} (run 0: {shape0[-1]}): {why}"
+            elif size[0] != size0[0]:
+                why = f"a graph of {size[0]} rows (run 0: {size0[0]}): one row count per batch"
+            elif size[1] != size0[1]:
+                why = f"{size[1]} input features (run 0: {size0[1]})"
         if why is not None:
             return f"run {k}: {why}"
     return None
 
 
 class _BatchedRuns:
-    """The runs of ``fit_batched`` behind the three methods of a run (``_drive``): the two ``SmallBatch``es (training step,
-    evaluation forward), the batched metrics and selection, the runs that hold a slot and those still waiting for one.  Built
+    """The runs of ``fit_batched`` / ``fit_batched_graphs`` behind the three methods of a run (``_drive``): the two batches
+    (training step, evaluation forward), the batched metrics and selection, the runs that hold a slot and those still waiting
+    for one.  ``runs[k]`` = (model, optimizer, train_idx, val_idx, test_idx) trains on ``inputs[k]`` = (features, operators,
+    labels): the same triple for every run (``small.SmallBatch``), or -- ``graphs`` -- a graph per run
+    (``small.SmallGraphBatch``, whose launch widths are formed here from the handles of EVERY run, before the capture).  Built
     and, on the GPU, captured on construction -- unless the first runs' plans cannot share launches: ``refused`` says why."""
 
-    def __init__(self, runs, xs, ops, labels, epochs, rule, early_stopping, n_slots, fused_dropout):
-        from .small import SmallBatch
-        self.runs, self.inputs, self.epochs = runs, (xs, ops, labels, fused_dropout), int(epochs)
+    def __init__(self, runs, inputs, epochs, rule, early_stopping, n_slots, fused_dropout, graphs=False):
+        from .small import SmallBatch, SmallGraphBatch
+        self.runs, self.inputs, self.fused_dropout, self.epochs = runs, inputs, fused_dropout, int(epochs)
+        self.name, self.Batch = ("fit_batched_graphs", SmallGraphBatch) if graphs else ("fit_batched", SmallBatch)
         self.pending, self.results = list(range(len(runs))), [None] * len(runs)
         self.live = first = [self._enter() for _ in range(n_slots)]
-        self.refused = next((r.refused for r in first if r.refused), None) or SmallBatch.why_not([r.step.small for r in first]) \
-            or SmallBatch.why_not([r.ev.small for r in first])
+        Batch = self.Batch
+        self.refused = next((r.refused for r in first if r.refused), None) or Batch.why_not([r.step.small for r in first]) \
+            or Batch.why_not([r.ev.small for r in first])
         if self.refused is not None:
             return
-        self.train_b = SmallBatch([r.step.small for r in first], n_slots)
-        self.eval_b = SmallBatch([r.ev.small for r in first], n_slots)
-        n, n_classes = first[0].step.small.n, first[0].step.small.C
+        if graphs:
+            seen = {(id(xs), id(ops)): (xs, ops) for xs, ops, _ in inputs}.values()          # (a graph's handles once)
+            self.train_b = Batch([r.step.small for r in first], n_slots, handles=[Batch.handles_of(xs, ops, True) for xs, ops in seen])
+            self.eval_b = Batch([r.ev.small for r in first], n_slots, handles=[Batch.handles_of(xs, ops, False) for xs, ops in seen])
+        else:
+            self.train_b = Batch([r.step.small for r in first], n_slots)
+            self.eval_b = Batch([r.ev.small for r in first], n_slots)
+        n, n_classes, labels = first[0].step.small.n, first[0].step.small.C, inputs[0][2]
         self.metrics = AF.BatchMetrics(n_slots, n, n_classes, 3, first[0].ev.labels, loss_set=1)
         self.select = AF.BatchSelection(rule, early_stopping, epochs, n_slots, labels.device)
         for i, r in enumerate(first):
@@ -1109,8 +1173,8 @@ class _BatchedRuns:
     def _enter(self):
         """The next waiting run for a slot, with its (un-captured) training step and evaluation pass objects -- made exactly as
         ``fit`` makes them, so the run's plans, optimizer state and dropout state are what ``fit`` would train."""
-        k, (xs, ops, labels, fused_dropout) = self.pending.pop(0), self.inputs
-        model, opt, tr, va, te = self.runs[k]
+        k, fused_dropout = self.pending.pop(0), self.fused_dropout
+        (model, opt, tr, va, te), (xs, ops, labels) = self.runs[k], self.inputs[k]
         step = TrainStep(model, opt, xs, ops, labels, row_weights(tr, xs.shape[0], device=labels.device), use_graph=False,
                          fused_dropout=fused_dropout)
         ev = EvalStep(model, xs, ops, labels, (tr, va, te), loss_set=1, use_graph=False)
@@ -1122,7 +1186,7 @@ class _BatchedRuns:
             self.metrics.set_slot(i)
             self.select.set_slot(i)
         else:
-            self.metrics.set_slot(i, r.ev.small.logits, r.ev.w)
+            self.metrics.set_slot(i, r.ev.small.logits, r.ev.w, r.ev.labels)
             self.select.set_slot(i, r.step.small.loss, self.metrics.out[i])
 
     def _epoch(self):
@@ -1134,17 +1198,17 @@ class _BatchedRuns:
     def _hand_over(self, i):
         """Slot ``i``'s run has stopped or used its budget up: its result is read, the slot goes to the next waiting run (or
         idles) by table writes -- nothing is re-captured."""
-        from .small import SmallBatch
+        Batch = self.Batch
         r = self.live[i]
         selected, history, _ = self.select.result(i)
         self.results[r.k] = (selected, history)
         r.model.eval()
         nxt = self.live[i] = self._enter() if self.pending else None
         if nxt is not None:
-            why = nxt.refused or SmallBatch.why_not([self.train_b._first(), nxt.step.small]) \
-                or SmallBatch.why_not([self.eval_b._first(), nxt.ev.small])
+            why = nxt.refused or Batch.why_not([self.train_b._first(), nxt.step.small]) \
+                or Batch.why_not([self.eval_b._first(), nxt.ev.small])
             if why is not None:
-                raise RuntimeError(f"fit_batched: run {nxt.k} cannot share the launches of the runs before it ({why}); "
+                raise RuntimeError(f"{self.name}: run {nxt.k} cannot share the launches of the runs before it ({why}); "
                                    "sort such runs into calls of their own")
         self.train_b.set_slot(i, nxt.step.small if nxt is not None else None)
         self.eval_b.set_slot(i, nxt.ev.small if nxt is not None else None)

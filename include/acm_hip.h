@@ -1215,8 +1215,9 @@ int acm_small_step_has_hidden(int32_t hidden);
  *                        kernels and the grids to agree across slots (n_classes, n_channels, relu_before, layernorm, train,
  *                        update, f_in, hidden, x_vals / xt_vals / xt_src_pos / row_scale), refuses two active slots whose workspace,
  *                        logits or loss ranges overlap, and writes the table (a copy ordered on `stream`, complete on return:
- *                        NOT capturable).  `slots`: HOST array of n_slots pointers.  The table also records the grids and
- *                        the kernel form it was bound for: a grid row whose launch does not match them does nothing.
+ *                        NOT capturable).  `slots`: HOST array of n_slots pointers.  The table also records the slot's grids
+ *                        and the kernel form it was bound for: a grid row of another form, or of a launch narrower than
+ *                        the slot's own grids, does nothing.
  * acm_small_batch_step   launches only (capturable).  `shape`: any active slot's block, read for the shared fields alone.
  *                        The handles must be those of the bind.
  * Errors (all before any launch): ACM_EINVAL NULL argument / n_slots < 1 / every slot empty / slots that disagree or overlap
@@ -1228,6 +1229,44 @@ int acm_small_batch_bind(const acm_csr_t* a_low, const acm_csr_t* x, const acm_c
                          const acm_small_step_t* const* slots, void* table, size_t table_bytes, acm_stream_t stream);
 int acm_small_batch_step(const acm_csr_t* a_low, const acm_csr_t* x, const acm_csr_t* x_t, int32_t n_slots,
                          const acm_small_step_t* shape, const void* table, acm_stream_t stream);
+
+/* ------------------------------------- the slots of a batch on DIFFERENT graphs (added under ABI 29) --
+ * synthetic-experiments/train.py:64-164 trains on num_graph (10) generated graphs per edge-homophily level, each with its
+ * own adjacency, its own features (load_synthetic_data(..., graph_idx, ...)) and its own split, for 28 levels, several models
+ * and a dropout x weight-decay grid: runs that share a shape and nothing else.  Runs whose operators have the same number of
+ * rows and whose blocks agree in f_in, n_classes, n_channels, relu_before, layernorm, train, update and hidden go through
+ * the same six launches as above, every slot on its OWN operator, features (x_vals / xt_vals / xt_src_pos), row scale,
+ * labels and split.  Grid row k is still, bit for bit, acm_small_step on slot k's handles and block: its workspace carve-up,
+ * producer-workgroup counts, long-row records and the width it loops with are those of its own handles; the LAUNCH is as
+ * wide as the widest run, and the workgroups past a slot's own width return at once.
+ *
+ * acm_small_batch_grids_t       the widths of the launches (an ENVELOPE: the element-wise maximum over runs).
+ * acm_small_batch_grids         folds the grids of one run's handles into *grids by maximum (zero-initialise *grids, then
+ *                               call it for EVERY run that may ever hold a slot: a captured step bakes the envelope in, so
+ *                               a slot can pass to a run on another graph between two replays by table bytes alone).
+ *                               `shape`: read for f_in, n_channels, train and hidden.
+ * acm_small_batch_bind_graphs   acm_small_batch_bind with HOST arrays of n_slots handles (entries of empty slots are not
+ *                               read; x_t entries may be NULL where train = 0).  Every active slot is validated against its
+ *                               own handles; a slot whose own grid exceeds `grids` in any launch is refused (ACM_ESHAPE),
+ *                               as are operators of different row counts (ACM_EINVAL).  Every refusal comes before any
+ *                               copy: a refused bind leaves the table as it was.  Table size: acm_small_batch_table_bytes.
+ * acm_small_batch_step_graphs   launches only (capturable), on grids (`grids`, n_slots).  `shape` as for acm_small_batch_step.
+ * acm_small_batch_bind / _step are the special case "the same handles in every slot, grids = their own"; the kernels are
+ * the same. */
+typedef struct acm_small_batch_grids {
+    int32_t proj;         /* launch 1 */
+    int32_t wide;         /* launches 2, 5 */
+    int32_t graph;        /* launches 3, 4 */
+    int32_t item_blocks;  /* launch 6: blocks that walk the transposed features (0 where train = 0) ... */
+    int32_t red_blocks;   /* ... and blocks that reduce the partial sums (a function of hidden alone) */
+} acm_small_batch_grids_t;
+int acm_small_batch_grids(const acm_csr_t* a_low, const acm_csr_t* x, const acm_csr_t* x_t, const acm_small_step_t* shape,
+                          acm_small_batch_grids_t* grids);
+int acm_small_batch_bind_graphs(int32_t n_slots, const acm_csr_t* const* a_low, const acm_csr_t* const* x, const acm_csr_t* const* x_t,
+                                const acm_small_step_t* const* slots, const acm_small_batch_grids_t* grids, void* table,
+                                size_t table_bytes, acm_stream_t stream);
+int acm_small_batch_step_graphs(int32_t n_slots, const acm_small_step_t* shape, const acm_small_batch_grids_t* grids,
+                                const void* table, acm_stream_t stream);
 
 /* ------------------------------------- homophily measures on the device (added under ABI 29) --
  * synthetic-experiments/homophily.py without its dense n x n matrices (label @ label.T at :16, A.nonzero() at :31 / :44 /
