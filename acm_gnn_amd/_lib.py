@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = (
     "acm_conv_acmii_fwd_workspace_bytes", "acm_conv_acmii_fwd", "acm_linear_fwd", "acm_bias_act", "acm_bias_act_bwd_workspace_bytes", "acm_bias_act_bwd",
     "acm_acmii_table_bytes", "acm_acmii_table", "acm_conv_acmii_v_fwd", "acm_conv_acmii_v_bwd_workspace_bytes", "acm_conv_acmii_v_bwd",
     "acm_linear_bwd_workspace_bytes", "acm_linear_bwd", "acm_linear_fwd_add", "acm_linear_bwd_recompute",
-    "acm_small_step_workspace_bytes", "acm_small_step", "acm_small_step_has_hidden", "acm_conv_head_fwd", "acm_conv_aggw_fwd", "acm_conv_aggw_bwd_workspace_bytes", "acm_conv_aggw_bwd",
+    "acm_small_step_workspace_bytes", "acm_small_step", "acm_small_step_has_hidden", "acm_small_step_workspace_bytes_for", "acm_small_step_has_residual", "acm_conv_head_fwd", "acm_conv_aggw_fwd", "acm_conv_aggw_bwd_workspace_bytes", "acm_conv_aggw_bwd",
     "acm_eval_metrics_workspace_bytes", "acm_eval_metrics",
     "acm_bce_loss_workspace_bytes", "acm_bce_loss", "acm_rocauc_scores", "acm_rocauc_workspace_bytes", "acm_rocauc",
     "acm_homophily_workspace_bytes", "acm_homophily_census", "acm_class_means_workspace_bytes", "acm_class_means", "acm_class_score",
@@ -294,12 +294,14 @@ class SmallStep(C.Structure):
     _fields_ = [("n_classes", C.c_int32), ("n_channels", C.c_int32), ("relu_before", C.c_int32), ("layernorm", C.c_int32),
                 ("scale", C.c_float), ("train", C.c_int32), ("update", C.c_int32), ("hidden", C.c_int32),
                 ("t", (AdamTensor * SMALL_ROLES) * 2),
-                ("x_vals", C.c_void_p), ("xt_src_pos", C.c_void_p), ("xt_vals", C.c_void_p), ("f_in", C.c_int32), ("reserved1", C.c_int32), ("drop_in", Dropout), ("drop_hidden", Dropout),
+                ("x_vals", C.c_void_p), ("xt_src_pos", C.c_void_p), ("xt_vals", C.c_void_p), ("f_in", C.c_int32), ("residual", C.c_int32), ("drop_in", Dropout), ("drop_hidden", Dropout),
                 ("row_scale", C.c_void_p), ("labels", C.c_void_p), ("row_weight", C.c_void_p), ("loss", C.c_void_p),
                 ("logits", C.c_void_p), ("att1", C.c_void_p), ("att2", C.c_void_p),
                 ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
                 ("weight_decay", C.c_double), ("decoupled", C.c_int32), ("also_advance", C.c_void_p), ("arrive", C.c_void_p),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                # read with `residual` alone (ACM-GCN++): mlpX.lins.0.weight / .bias and the residual branch's dropout
+                ("res", AdamTensor * 2), ("drop_res", Dropout)]
 
 
 SMALL_BATCH_MAX = 32          # ACM_SMALL_BATCH_MAX: slots of one acm_small_batch_* table
@@ -426,6 +428,8 @@ def _declare(lib):
     lib.acm_small_step_workspace_bytes.argtypes = [vp, vp, vp, C.POINTER(sz)]
     lib.acm_small_step.argtypes = [vp, vp, vp, C.POINTER(SmallStep), vp]
     lib.acm_small_step_has_hidden.argtypes = [i32]
+    lib.acm_small_step_workspace_bytes_for.argtypes = [vp, vp, vp, C.POINTER(SmallStep), C.POINTER(sz)]
+    lib.acm_small_step_has_residual.argtypes = []
     lib.acm_small_batch_table_bytes.argtypes = [i32, C.POINTER(sz)]
     lib.acm_small_batch_bind.argtypes = [vp, vp, vp, i32, C.POINTER(C.POINTER(SmallStep)), vp, sz, vp]
     lib.acm_small_batch_step.argtypes = [vp, vp, vp, i32, C.POINTER(SmallStep), vp, vp]

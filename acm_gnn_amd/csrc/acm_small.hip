@@ -1,4 +1,6 @@
-// The whole training step of the two-layer ACM model on a SMALL graph in six launches (acm_small_step, ABI 25).
+// The whole training step of the two-layer ACM model on a SMALL graph in six launches (acm_small_step, ABI 25) -- SEVEN for
+// ACM-GCN++ (acm_small_step_t::residual: launch 0 writes the residual Linear's weight transposed, launches 1, 2, 4 and 6 carry
+// the branch under `bool RES`; its evaluation pass is four launches, not three).
 //
 // Reference: one step of ACM-Pytorch/models/models.py:100-166 (dropout -> GraphConvolution -> relu -> dropout ->
 // GraphConvolution), utils.py:547-574 (log_softmax + nll_loss on the training rows, backward, optimizer.step) --
@@ -41,6 +43,12 @@ template <int V> using fv = typename vec_of<V>::type;
 
 constexpr int F_MAX = 64;             // the widest hidden width: sizes the workspace for every width
 constexpr int SLOT_PITCH = 3 * F_MAX; // floats of a long row's slot
+constexpr int SLOT_PITCH_RES = 4 * F_MAX;  // ... of a residual plan's (launches 1 and 6 carry a fourth sum there: R, dW_X)
+// The residual branch's two tensors (acm_small_step_t::res) ride behind the roles of layer 1 on the device: t[0][SR_RES_W],
+// t[0][SR_RES_B] -- step factors, step counters and the reducing blocks' updates treat them like every other role.
+constexpr int DEV_ROLES = ACM_SMALL_ROLES + 2;
+constexpr int SR_RES_W = ACM_SMALL_ROLES, SR_RES_B = ACM_SMALL_ROLES + 1;
+constexpr int TR = 32;                // launch 0's tile: TR x TR elements of W_X through LDS
 constexpr int C8 = 8;                 // padded class count
 constexpr int WAVES = 8;              // per workgroup of the gather phases (two per SIMD: the second hides the first's latency chain)
 constexpr int MAX_WG = 512;           // workgroups of the phases that leave per-workgroup partial sums (launches 3, 4): beyond that a
@@ -48,7 +56,8 @@ constexpr int MAX_WG = 512;           // workgroups of the phases that leave per
 constexpr int MAX_WG_WIDE = 2048;     // ... of the wide gather phases (launches 2, 5): one work item per wave up to 16384 items (a
                                       // wave's item is a chain of ~2 000 dependent instructions; more waves, not longer loops, hide it)
 constexpr int RED_EL = 8;             // elements of the partial-sum vectors per reducing block of the last launch (x 32 producer lanes)
-constexpr int part4_of(int f) { return 3 * f * C8 + 3 * 4 * f + 16; }      // dW2 [3][F][8] | dv1 [4][F] | dgamma1 | dbeta1 | dmix1 [4][4]
+// dW2 [3][F][8] | dv1 [4][F] | dgamma1 | dbeta1 | dmix1 [4][4] | with the residual: db_X [F]
+constexpr int part4_of(int f, bool res = false) { return 3 * f * C8 + 3 * 4 * f + 16 + (res ? f : 0); }
 constexpr int PART3 = 3 * 4 * C8 + 16 + 1;              // dv2 [4][8] | dgamma2 | dbeta2 | dmix2 | loss
 constexpr int PART3_PITCH = 128;
                                                         // (= a long row's record of launch 4: the row's terms in the layout of a partial)
@@ -72,7 +81,7 @@ struct ItemView {
 struct SmallDev {
     int n, f_in, C, k, relu_before, layernorm, train, update;
     float scale;
-    SmallTensor t[2][ACM_SMALL_ROLES];
+    SmallTensor t[2][DEV_ROLES];
     ItemView graph, x, xt;
     const float* x_vals;
     const int32_t* xt_src_pos;
@@ -94,6 +103,10 @@ struct SmallDev {
     AdamScalars hp;
     int64_t* also_advance;
     int* arrive;
+    // the residual branch (ACM-GCN++; all unused without it)
+    int residual;
+    float *WXT, *R, *XX, *DR;        // W_X^T [f_in, F] | x_d W_X^T [n, F] | xX [n, F] | dR [n, F]
+    acm_dropout_t drop_res;
 };
 
 // A sub-struct of the step's block as a value.  The block is either a kernel argument (generic reference) or an entry of the
@@ -163,9 +176,10 @@ __device__ __forceinline__ f4 ld4_coherent(const float* p) { return ldv_coherent
 // acc[c] += sum over the entries [begin, end) of an id list of  w(pos) * T_c[id(pos), V m .. V m + V - 1];  group g of the wave
 // takes the entries 4u + g.  The ids are loaded TRANSPOSED (lane (g, u) holds the id step u needs in group g), so a step
 // is one row-broadcast DPP move per lane, no LDS crossbar.  Entries past `end` read row `safe` with weight 0.
-template <int V, int NCH, int RELU_MASK, class W>
-__device__ __forceinline__ void wide_gather(const int32_t* __restrict__ ids, int begin, int end, const float* const (&tab)[3],
-                                            const int (&ld)[3], int safe, W&& weight, fv<V> (&acc)[3]) {
+// NA: the arrays' length (3; 4 where a residual plan gathers a fourth table), deduced.
+template <int V, int NCH, int RELU_MASK, int NA, class W>
+__device__ __forceinline__ void wide_gather(const int32_t* __restrict__ ids, int begin, int end, const float* const (&tab)[NA],
+                                            const int (&ld)[NA], int safe, W&& weight, fv<V> (&acc)[NA]) {
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
     int id = safe;
     float w = 0.f;
@@ -196,7 +210,13 @@ __device__ __forceinline__ void wide_gather(const int32_t* __restrict__ ids, int
                     acc[c] += ww[s] * x;                                                        \
                 }                                                                               \
         }
-        if (steps <= 4) {
+        if constexpr (NCH == 4) {
+            // four tables: four steps (sixteen rows) in flight -- eight would hold 128 registers of rows at F = 64
+            ACM_WG_BLOCK(0, 4)
+            if (steps > 4) ACM_WG_BLOCK(4, 4)
+            if (steps > 8) ACM_WG_BLOCK(8, 4)
+            if (steps > 12) ACM_WG_BLOCK(12, 4)
+        } else if (steps <= 4) {
             ACM_WG_BLOCK(0, 4)
         } else if (steps <= 8) {
             ACM_WG_BLOCK(0, 8)
@@ -226,13 +246,17 @@ __device__ __forceinline__ void wide_items(const ItemView& iv, float* slots, int
         item.row = acm_uniform(item.row), item.begin = acm_uniform(item.begin), item.end = acm_uniform(item.end), item.slot = acm_uniform(item.slot);
         auto pf = pre(item.row);
         constexpr int F = 16 * V;
-        fv<V> acc[3] = {zerov<V>(), zerov<V>(), zerov<V>()};
+        constexpr int NA = NCH > 3 ? NCH : 3;                        // four sums (and slots of four) in a residual plan's launches 1 and 6
+        constexpr int PITCH = NCH > 3 ? SLOT_PITCH_RES : SLOT_PITCH;
+        fv<V> acc[NA];
+#pragma unroll
+        for (int c = 0; c < NA; ++c) acc[c] = zerov<V>();
         gather(item, acc);
 #pragma unroll
         for (int c = 0; c < NCH; ++c) acc[c] = xsumv(acc[c]);
         if (item.slot >= 0) {                                        // a piece of a long row (uniform branch)
-            float* sp = slots + (long)item.slot * SLOT_PITCH;
-            if (g < NCH) st_coherent(sp + g * F + V * m, selv(g, acc[0], acc[1], acc[2], acc[2]));
+            float* sp = slots + (long)item.slot * PITCH;
+            if (g < NCH) st_coherent(sp + g * F + V * m, selv(g, acc[0], acc[1], acc[2], acc[NA - 1]));
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             const int li = iv.long_index[item.row];
             const AcmLongRow lr = iv.long_rows[li];
@@ -241,9 +265,10 @@ __device__ __forceinline__ void wide_items(const ItemView& iv, float* slots, int
             old = __builtin_amdgcn_readfirstlane(old);
             if (old != lr.slot_end - lr.slot_begin - 1) continue;    // another piece will finish the row
             if (lane == 0) __hip_atomic_store(counters + li, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            acc[0] = acc[1] = acc[2] = zerov<V>();
+#pragma unroll
+            for (int c = 0; c < NA; ++c) acc[c] = zerov<V>();
             for (int q = lr.slot_begin; q < lr.slot_end; ++q) {
-                const float* qp = slots + (long)q * SLOT_PITCH + V * m;
+                const float* qp = slots + (long)q * PITCH + V * m;
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) acc[c] += ldv_coherent<V>(qp + c * F);
             }
@@ -375,7 +400,7 @@ __device__ __forceinline__ float gmax8(float v) {
 // What the later launches of the step read as tables, written by the first workgroup of launch 1 (both change every step):
 //   W2T  [idx = ch * 8 + c][col < F]: layer 2's weights, classes padded to 8 -- a lane's V columns of one output are one
 //        load, for the forward projection (launch 2) and for dH = dZ2 W2^T (launch 4) alike
-//   FACT [layer * 17 + role][2]: the step-dependent Adam factors of every tensor (double-precision pow: once, not per block)
+//   FACT [layer * DEV_ROLES + role][2]: the step-dependent Adam factors of every tensor (double-precision pow: once, not per block)
 template <int V, class D>
 __device__ __forceinline__ void write_tables(const D& d) {
     constexpr int F = 16 * V;
@@ -384,8 +409,8 @@ __device__ __forceinline__ void write_tables(const D& d) {
         const int idx = e / F, col = e % F, ch = idx >> 3, c = idx & 7;
         d.W2T[e] = c < d.C ? d.t[1][ACM_SR_W_LOW + ch].p[col * d.C + c] : 0.f;
     }
-    if ((int)threadIdx.x < 2 * ACM_SMALL_ROLES && d.update) {
-        const SmallTensor t = take(d.t[threadIdx.x / ACM_SMALL_ROLES][threadIdx.x % ACM_SMALL_ROLES]);
+    if ((int)threadIdx.x < 2 * DEV_ROLES && d.update) {
+        const SmallTensor t = take(d.t[threadIdx.x / DEV_ROLES][threadIdx.x % DEV_ROLES]);
         if (t.p && t.step) acm_adam_step_factors(take(d.hp), t.step[0], d.FACT[2 * threadIdx.x], d.FACT[2 * threadIdx.x + 1]);
     }
     // the dropout counter of THIS step: the later launches draw their masks with this copy, so the last launch may advance
@@ -394,16 +419,49 @@ __device__ __forceinline__ void write_tables(const D& d) {
 }
 
 // ------------------------------------------------------------------------------------------------ launch 1: Z1 = drop(X) Wcat
-template <int V, class D>
+// ------------------------------------------------------------------------------------------------ launch 0 (residual plans): W_X^T
+// mlpX.lins[0] is an nn.Linear: its weight is [F, f_in], the transpose of the [f_in, F] tables launch 1 gathers by feature id.
+// WXT[j, c] = W_X[c, j], a TR x TR tile per workgroup through LDS (rows of W_X read along j, rows of WXT written along c).
+// Rebuilt on every call: the optimizer, a keep-best restore and load_state_dict all rewrite the parameter through its pointer.
+__global__ __launch_bounds__(256) void small_wxt_kernel(const float* __restrict__ w, float* __restrict__ wxt, int f_in, int F) {
+    __shared__ float tile[TR][TR + 1];
+    const int tx = threadIdx.x & (TR - 1), ty = threadIdx.x / TR;          // 32 x 8 threads
+    const int j0 = (int)blockIdx.x * TR, c0 = (int)blockIdx.y * TR;
+    for (int r = ty; r < TR; r += 256 / TR)
+        tile[r][tx] = (c0 + r < F && j0 + tx < f_in) ? w[(long)(c0 + r) * f_in + j0 + tx] : 0.f;
+    __syncthreads();
+    for (int r = ty; r < TR; r += 256 / TR)
+        if (j0 + r < f_in && c0 + tx < F) wxt[(long)(j0 + r) * F + c0 + tx] = tile[tx][r];
+}
+
+// RES: a fourth sum R = drop(X) W_X^T beside the three channels (the same dropped values, items and long-row machinery);
+// group 3, idle in the store without it, stores R to its own [n, F] buffer -- Z1 keeps its 3 F pitch.
+template <int V, bool RES, class D>
 __device__ __forceinline__ void small_proj1_body(const D& d, int n_wg) {
     constexpr int F = 16 * V;
     write_tables<V>(d);
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
     const int wave = (int)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = n_wg * 4;
     const AcmDropCtx dc = acm_drop_ctx(take(d.drop_in));
+    const float* __restrict__ xv = d.x_vals;
+    if constexpr (RES) {
+        const float* tab[4] = {d.t[0][ACM_SR_W_LOW].p, d.t[0][ACM_SR_W_HIGH].p, d.t[0][ACM_SR_W_MLP].p, d.WXT};
+        const int ld[4] = {F, F, F, F};
+        wide_items<V, 4>(
+            take(d.x), d.slots, d.counters, wave, n_waves, [](int) { return 0; },
+            [&](const AcmItem& item, fv<V>(&acc)[4]) {
+                wide_gather<V, 4, 0>(d.x.indices, item.begin, item.end, tab, ld, 0,
+                                     [&](int pos) { return xv[pos] * acm_drop1(dc, pos, 0); }, acc);
+            },
+            [&](int row, fv<V>(&acc)[4], int) {
+                if (g < 3) stv<V>(d.Z1 + (long)row * (3 * F) + g * F + V * m, selv(g, acc[0], acc[1], acc[2], acc[2]));
+                else stv<V>(d.R + (long)row * F + V * m, acc[3]);
+                if (d.k == 4 && g == 3 && m < C8) d.T2[(long)row * 24 + 16 + m] = m < d.C ? d.t[1][ACM_SR_STRUC].p[(long)row * d.C + m] : 0.f;
+            });
+        return;
+    }
     const float* tab[3] = {d.t[0][ACM_SR_W_LOW].p, d.t[0][ACM_SR_W_HIGH].p, d.t[0][ACM_SR_W_MLP].p};
     const int ld[3] = {F, F, F};
-    const float* __restrict__ xv = d.x_vals;
     wide_items<V, 3>(
         take(d.x), d.slots, d.counters, wave, n_waves, [](int) { return 0; },
         [&](const AcmItem& item, fv<V>(&acc)[3]) {
@@ -419,12 +477,19 @@ __device__ __forceinline__ void small_proj1_body(const D& d, int n_wg) {
 
 // ------------------------------------------------------------------------------------------------ launch 2: layer 1 forward
 // per-row math of a WIDE layer (F columns), group g = channel g.  `acc` = complete gathered sums (in every group).
-template <int V>
+template <int V, bool RES>
 struct Pre2 {
     float rs;
     fv<V> own;
 };
-template <int V, bool FOUR, bool VARIANT, class D>
+template <int V>
+struct Pre2<V, true> {
+    float rs;
+    fv<V> own, r;                                        // r: the row of R = drop(X) W_X^T (launch 1)
+};
+// RES: xX = drop_res(relu(R[row] + b_X)), element (row, column) with tag 2, is stored and joins `out` in layer 2's projection
+// (models.py:160-163: the layer after sees drop(relu(fea1)) + xX); OUT1 keeps the pure `out`.
+template <int V, bool FOUR, bool VARIANT, bool RES, class D>
 __device__ __forceinline__ void small_conv1_fwd_body(const D& d, const float* z1, int n_wg) {
     constexpr int F = 16 * V;
     typedef fv<V> vt;
@@ -433,6 +498,9 @@ __device__ __forceinline__ void small_conv1_fwd_body(const D& d, const float* z1
     constexpr int NCH = FOUR ? 3 : 2;
     constexpr int K = FOUR ? 4 : 3;
     const AcmDropCtx dh = acm_drop_ctx(take(d.drop_hidden));
+    AcmDropCtx dr = dh;
+    vt bx = zerov<V>();
+    if constexpr (RES) dr = acm_drop_ctx(take(d.drop_res)), bx = ldv<V>(d.t[0][SR_RES_B].p + V * m);
     const float* tab[3] = {z1, z1 + F, FOUR ? d.t[0][ACM_SR_STRUC].p : z1};
     const int ld[3] = {3 * F, 3 * F, F};
     const bool act = g < K;
@@ -454,15 +522,16 @@ __device__ __forceinline__ void small_conv1_fwd_body(const D& d, const float* z1
     wide_items<V, NCH>(
         take(d.graph), d.slots, d.counters, wave, n_waves,
         [&](int row) {
-            Pre2<V> pf;
+            Pre2<V, RES> pf;
             pf.rs = d.row_scale[row];
             pf.own = (g == 0 || (!FOUR && g == 3)) ? zerov<V>() : ldv<V>(own_base + (long)row * own_ld + V * m);
+            if constexpr (RES) pf.r = ldv<V>(d.R + (long)row * F + V * m);
             return pf;
         },
         [&](const AcmItem& item, vt(&acc)[3]) {
             wide_gather<V, NCH, VARIANT ? 3 : 0>(d.graph.indices, item.begin, item.end, tab, ld, item.row, [](int) { return 1.f; }, acc);
         },
-        [&](int row, vt(&acc)[3], const Pre2<V>& pf) {
+        [&](int row, vt(&acc)[3], const Pre2<V, RES>& pf) {
             const float rs = pf.rs;
             const vt own = pf.own;
             vt h;
@@ -506,6 +575,16 @@ __device__ __forceinline__ void small_conv1_fwd_body(const D& d, const float* z1
                 for (int r = 0; r < V; ++r) out[r] *= acm_drop1(dh, row, V * m + r);
             }
             if (g == 0) stv<V>(d.OUT1 + (long)row * F + V * m, out);
+            vt in2 = out;                                  // what layer 2 projects
+            if constexpr (RES) {
+                vt xx = reluv(pf.r + bx);
+                if (dr.on) {
+#pragma unroll
+                    for (int r = 0; r < V; ++r) xx[r] *= acm_drop1(dr, row, V * m + r);
+                }
+                if (g == 1) stv<V>(d.XX + (long)row * F + V * m, xx);
+                in2 = out + xx;
+            }
             if (act) stv<V>(d.H1 + (long)row * (4 * F) + g * F + V * m, h);
             if (m == 0 && act) {
                 float* st = d.ST1 + (long)row * 16;
@@ -516,7 +595,7 @@ __device__ __forceinline__ void small_conv1_fwd_body(const D& d, const float* z1
 #pragma unroll
             for (int t = 0; t < 6; ++t) {
                 const int idx = g + 4 * t, ch = idx >> 3, c = idx & 7;
-                const float s = acm_group_sum<16>(hsumv(out * w2t[t]));
+                const float s = acm_group_sum<16>(hsumv(in2 * w2t[t]));
                 if (m == 0 && c < d.C) {
                     if (ch < 2) d.T2[(long)row * 24 + ch * 8 + c] = s;
                     else d.Z2I[(long)row * C8 + c] = s;
@@ -726,13 +805,21 @@ struct Pre4 {
     fv<V> o, h;
     float mean, rstd, sa[8];
 };
-template <int V, bool FOUR, class D>
+// RES: the layer's real input is o + xX (dW2 takes it); dmix stays on the pure o; dR = the gradient through the residual's
+// dropout and ReLU goes to its own [n, F] buffer (launch 6's fourth table) and db_X = sum over rows of dR joins the partial
+// sums (the last F elements of a partial / a long row's record).
+template <int V, bool FOUR, bool RES, class D>
 __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1, int n_wg) {
-    constexpr int F = 16 * V, PART4 = part4_of(F), LONG4 = PART4;
+    constexpr int F = 16 * V, PART4 = part4_of(F, RES), LONG4 = PART4, DBX = part4_of(F);   // DBX: where db_X starts
     typedef fv<V> vt;
     __shared__ __attribute__((aligned(16))) float red[WAVES / 2][PART4];  // the waves' sums side by side (two rounds: 37 KB at F = 64)
     __shared__ __attribute__((aligned(16))) float w2s[3 * F * C8];        // W2T [idx][col]: 24 rows of F, read by every row's dH
+    // RES: db_X's running sum per wave, in LDS (the 64-wide kernel has no four registers left for it: 256 without the residual)
+    __shared__ __attribute__((aligned(16))) float dbx[RES ? WAVES : 1][F];
     for (int e = 4 * threadIdx.x; e < 3 * F * C8; e += 4 * 64 * WAVES) st4(w2s + e, ld4(d.W2T + e));
+    if constexpr (RES) {
+        if (threadIdx.x < WAVES * F / 4) st4(&dbx[0][0] + 4 * threadIdx.x, zero4());
+    }
     __syncthreads();
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15, c = lane & 7, wv = threadIdx.x >> 6;
     const int wave = (int)blockIdx.x * WAVES + wv, n_waves = n_wg * WAVES;
@@ -742,6 +829,8 @@ __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1
     const bool variant = d.relu_before != 0;
     const AcmDropCtx dh = acm_drop_ctx(take(d.drop_hidden));
     const float inv_keep = dh.on ? dh.inv_keep : 1.f;
+    float inv_keep_res = 1.f;
+    if constexpr (RES) inv_keep_res = d.drop_res.p > 0.f ? 1.0f / (1.0f - d.drop_res.p) : 1.f;    // (acm_drop_ctx's own expression)
     const bool act = g < K;
     const vt av = act ? ldv<V>(d.t[0][ACM_SR_V_LOW + g].p + V * m) : zerov<V>();
     vt gam = zerov<V>();
@@ -798,7 +887,7 @@ __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1
                 if (ts2.g) ts2.g[i] = ds;
                 if (d.update) {
                     float pp = pf.sp, mm = pf.sm, vv = pf.sv;
-                    const float* fc = d.FACT + 2 * (ACM_SMALL_ROLES + ACM_SR_STRUC);
+                    const float* fc = d.FACT + 2 * (DEV_ROLES + ACM_SR_STRUC);
                     adam_one(pp, ds, mm, vv, af.decay_eff, af.wd, af.decoupled, af.w1, af.b2, af.w2, fc[0], fc[1], af.eps);
                     ts2.p[i] = pp, ts2.m[i] = mm, ts2.v[i] = vv;
                 }
@@ -812,17 +901,34 @@ __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1
                 dz[16 + cc] = acm_lane_f(dzI, cc);
             }
             const vt o = pf.o;
+            // the layer's input: with the residual o + xX (xX requested here, not before the gather: it travels while dH is
+            // formed from LDS, and the 64-wide kernel has no registers to hold it through the gather)
+            vt xx = zerov<V>();
+            if constexpr (RES) xx = ldv<V>(d.XX + (long)row * F + V * m);
             // dH = dZ2 Wcat2^T (columns V m .. V m + V - 1) and dWcat2 += H^T dZ2 (group g: idx = g, g + 4, ...)
             // (W2T from LDS, staged once per workgroup: as global loads its 24 rows were three dependent round trips per row)
             vt dH0 = zerov<V>(), dH1 = zerov<V>();
 #pragma unroll
             for (int q = 0; q < 24; q += 2) dH0 += dz[q] * ldv<V>(w2s + q * F + V * m), dH1 += dz[q + 1] * ldv<V>(w2s + (q + 1) * F + V * m);
             const vt dH = dH0 + dH1;
+            vt in2 = o, dmix_r = o;
+            if constexpr (RES) {
+                // Everything that reads o, xX or dH on its own first, then their sum in o's place: the 64-wide kernel is at
+                // its 256 registers without the residual.
+                dmix_r = wherev(o, dH * inv_keep);
+                // through the residual's dropout(relu(.)), as dmix through the layer's
+                const vt r_dbx = wherev(xx, dH * inv_keep_res);
+                if (g == 1) stv<V>(d.DR + (long)row * F + V * m, r_dbx);
+                if (li < 0) {
+                    if (g == 0) stv<V>(dbx[wv] + V * m, ldv<V>(dbx[wv] + V * m) + r_dbx);      // (a wave's own slice: no barrier)
+                } else if (g == 0) stv<V>(d.long4 + (long)li * LONG4 + DBX + V * m, r_dbx);
+                in2 = o + xx;
+            }
             if (li < 0) {
 #pragma unroll
                 for (int t = 0; t < 6; ++t) {
                     const float zz = g == 0 ? dz[4 * t] : (g == 1 ? dz[4 * t + 1] : (g == 2 ? dz[4 * t + 2] : dz[4 * t + 3]));
-                    a_w2[t] += zz * o;
+                    a_w2[t] += zz * in2;
                 }
             } else {                                      // a long row: its dW2 term goes to the row's own record
                 float* rec = d.long4 + (long)li * LONG4;
@@ -832,11 +938,13 @@ __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1
                     const float zz = g == 0 ? dz[4 * t] : (g == 1 ? dz[4 * t + 1] : (g == 2 ? dz[4 * t + 2] : dz[4 * t + 3]));
                     float* rp = rec + ch * (F * C8) + (V * m) * C8 + cc;
 #pragma unroll
-                    for (int r = 0; r < V; ++r) rp[r * C8] = zz * o[r];
+                    for (int r = 0; r < V; ++r) rp[r * C8] = zz * in2[r];
                 }
             }
             // through dropout(relu(.)): the forward's output is non-zero exactly where both let the element pass
-            const vt dmix = wherev(o, dH * inv_keep);
+            vt dmix;
+            if constexpr (RES) dmix = dmix_r;
+            else dmix = wherev(o, dH * inv_keep);
             // row-local backward of layer 1, channel g in group g
             const float rs = pf.rs;
             const vt h = pf.h;
@@ -925,6 +1033,14 @@ __device__ __forceinline__ void small_conv2_bwd_body(const D& d, const float* z1
                 if (round == 0) rm[0] = a_dm;
                 else rm[0] += a_dm;
             }
+            if constexpr (RES) {
+                if (g == 0) {
+                    float* rx = mine + DBX + V * m;
+                    const vt a_dbx = ldv<V>(dbx[wv] + V * m);
+                    if (round == 0) stv<V>(rx, a_dbx);
+                    else stv<V>(rx, ldv<V>(rx) + a_dbx);
+                }
+            }
         }
         __syncthreads();
     }
@@ -995,9 +1111,12 @@ __device__ __forceinline__ void small_conv1_bwd_body(const D& d, const float* z1
 // blocks [0, item_blocks): dW1 = drop(X)^T dZ1 by feature row (the transposed feature handle's items) + its update;
 // blocks behind: RED_EL elements of the two partial-sum vectors per block (sum over the producer workgroups and the long
 // rows' records, then the update).  The first block advances the step counters.
-template <int V, class D>
+// RES: the feature-row blocks take dR as a fourth table, dW_X[:, j] = sum_i x_d[i, j] dR[i, :], and update W_X in the Linear's
+// own layout (element (c, j) at c f_in + j: strided scalar accesses, group 3's); the reducing blocks apply b_X from the
+// partial sums' last F elements.
+template <int V, bool RES, class D>
 __device__ __forceinline__ void small_finish_body(const D& d, int item_blocks, int red_blocks) {
-    constexpr int F = 16 * V, PART4 = part4_of(F), LONG4 = PART4;
+    constexpr int F = 16 * V, PART4 = part4_of(F, RES), LONG4 = PART4;
     typedef fv<V> vt;
     __shared__ float red8[256 / RED_EL][RED_EL];
     const float* __restrict__ fact = d.FACT;              // step factors of every tensor (launch 1 wrote them)
@@ -1007,7 +1126,7 @@ __device__ __forceinline__ void small_finish_body(const D& d, int item_blocks, i
         if (!t.p) return;
         if (t.g) t.g[i] = gsum;
         if (!d.update) return;
-        const float* s = fact + 2 * (layer * ACM_SMALL_ROLES + role);
+        const float* s = fact + 2 * (layer * DEV_ROLES + role);
         float pp = t.p[i], mm = t.m[i], vv = t.v[i];
         adam_one(pp, gsum, mm, vv, af.decay_eff, af.wd, af.decoupled, af.w1, af.b2, af.w2, s[0], s[1], af.eps);
         t.p[i] = pp, t.m[i] = mm, t.v[i] = vv;
@@ -1017,12 +1136,16 @@ __device__ __forceinline__ void small_finish_body(const D& d, int item_blocks, i
         const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
         const int wave = blk * 4 + (threadIdx.x >> 6), n_waves = item_blocks * 4;
         const AcmDropCtx dc = acm_drop_ctx(take(d.drop_in));
-        const float* tab[3] = {d.DZ1, d.DZ1 + F, d.DZ1 + 2 * F};
-        const int ld[3] = {3 * F, 3 * F, 3 * F};
+        constexpr int NT = RES ? 4 : 3;
+        const float* tab[NT] = {d.DZ1, d.DZ1 + F, d.DZ1 + 2 * F};
+        int ld[NT] = {3 * F, 3 * F, 3 * F};
+        if constexpr (RES) tab[3] = d.DR, ld[3] = F;
+        const int(&ldc)[NT] = ld;
         const float* __restrict__ xv = d.x_vals;
         const float* __restrict__ xtv = d.xt_vals;
         const int32_t* __restrict__ sp = d.xt_src_pos;
-        wide_items<V, 3>(
+        const long f_in = d.f_in;
+        wide_items<V, NT>(
             take(d.xt), d.slots, d.counters, wave, n_waves,
             [&](int frow) {                                // the weight rows this wave will update, with their moments
                 Pre5<V> pf;
@@ -1032,17 +1155,44 @@ __device__ __forceinline__ void small_finish_body(const D& d, int item_blocks, i
                     const long i = (long)frow * F + V * m;
                     pf.pp = ldv<V>(t.p + i), pf.mm = ldv<V>(t.m + i), pf.vv = ldv<V>(t.v + i);
                 }
+                if constexpr (RES) {
+                    if (g == 3 && d.update) {              // column frow of W_X: V elements f_in apart
+                        const SmallTensor t = take(d.t[0][SR_RES_W]);
+#pragma unroll
+                        for (int r = 0; r < V; ++r) {
+                            const long i = (long)(V * m + r) * f_in + frow;
+                            pf.pp[r] = t.p[i], pf.mm[r] = t.m[i], pf.vv[r] = t.v[i];
+                        }
+                    }
+                }
                 return pf;
             },
-            [&](const AcmItem& item, vt(&acc)[3]) {
+            [&](const AcmItem& item, vt(&acc)[NT]) {
                 if (xtv)
-                    wide_gather<V, 3, 0>(d.xt.indices, item.begin, item.end, tab, ld, 0,
-                                         [&](int pos) { return xtv[pos] * acm_drop1(dc, sp[pos], 0); }, acc);
+                    wide_gather<V, NT, 0>(d.xt.indices, item.begin, item.end, tab, ldc, 0,
+                                          [&](int pos) { return xtv[pos] * acm_drop1(dc, sp[pos], 0); }, acc);
                 else
-                    wide_gather<V, 3, 0>(d.xt.indices, item.begin, item.end, tab, ld, 0,
-                                         [&](int pos) { const int s = sp[pos]; return xv[s] * acm_drop1(dc, s, 0); }, acc);
+                    wide_gather<V, NT, 0>(d.xt.indices, item.begin, item.end, tab, ldc, 0,
+                                          [&](int pos) { const int s = sp[pos]; return xv[s] * acm_drop1(dc, s, 0); }, acc);
             },
-            [&](int frow, vt(&acc)[3], const Pre5<V>& pf) {
+            [&](int frow, vt(&acc)[NT], const Pre5<V>& pf) {
+                if constexpr (RES) {
+                    if (g == 3) {
+                        const SmallTensor t = take(d.t[0][SR_RES_W]);
+                        const float* fc = fact + 2 * SR_RES_W;
+#pragma unroll
+                        for (int r = 0; r < V; ++r) {
+                            const long i = (long)(V * m + r) * f_in + frow;
+                            const float gw = acc[NT - 1][r];
+                            if (t.g) t.g[i] = gw;
+                            if (d.update) {
+                                float pp = pf.pp[r], mm = pf.mm[r], vv = pf.vv[r];
+                                adam_one(pp, gw, mm, vv, af.decay_eff, af.wd, af.decoupled, af.w1, af.b2, af.w2, fc[0], fc[1], af.eps);
+                                t.p[i] = pp, t.m[i] = mm, t.v[i] = vv;
+                            }
+                        }
+                    }
+                }
                 if (g < 3) {
                     const vt gw = selv(g, acc[0], acc[1], acc[2], acc[2]);
                     const SmallTensor t = take(d.t[0][ACM_SR_W_LOW + g]);
@@ -1100,9 +1250,11 @@ __device__ __forceinline__ void small_finish_body(const D& d, int item_blocks, i
                     const int r = e - 3 * F * C8, kind = r / (4 * F), ch = (r / F) % 4, col = r % F;
                     if (ch < K && (kind == 0 || d.layernorm))
                         apply(0, (kind == 0 ? ACM_SR_V_LOW : (kind == 1 ? ACM_SR_LNW_LOW : ACM_SR_LNB_LOW)) + ch, col, s);
-                } else {
+                } else if (!RES || e < part4_of(F)) {
                     const int r = e - 3 * F * C8 - 12 * F, a = r / 4, b = r % 4;
                     if (a < K && b < K) apply(0, ACM_SR_MIX, a * K + b, s);
+                } else {
+                    apply(0, SR_RES_B, e - part4_of(F), s);
                 }
             } else if (q < 96) {
                 const int kind = q / 32, ch = (q / 8) % 4, c = q % 8;
@@ -1119,13 +1271,13 @@ __device__ __forceinline__ void small_finish_body(const D& d, int item_blocks, i
     // nothing in this launch reads a step counter (launch 1 left the factors and the dropout counter of the step in the
     // workspace): the first block advances them
     if (blk == 0 && d.update) {
-        if ((int)threadIdx.x < 2 * ACM_SMALL_ROLES) {
-            const SmallTensor t = take(d.t[threadIdx.x / ACM_SMALL_ROLES][threadIdx.x % ACM_SMALL_ROLES]);
+        if ((int)threadIdx.x < 2 * DEV_ROLES) {
+            const SmallTensor t = take(d.t[threadIdx.x / DEV_ROLES][threadIdx.x % DEV_ROLES]);
             if (t.p && t.step) {
                 // tensors that share one step scalar are advanced once (the first role that names it)
                 bool first = true;
                 for (int o = 0; o < (int)threadIdx.x; ++o) {
-                    const SmallTensor u = take(d.t[o / ACM_SMALL_ROLES][o % ACM_SMALL_ROLES]);
+                    const SmallTensor u = take(d.t[o / DEV_ROLES][o % DEV_ROLES]);
                     if (u.p && u.step == t.step) first = false;
                 }
                 if (first) t.step[0] += 1.0f;
@@ -1177,20 +1329,21 @@ __host__ __device__ constexpr int form_of(bool four, bool variant, bool train, i
     return (four ? 1 : 0) | (variant ? 2 : 0) | (train ? 4 : 0) | (hidden == 32 ? FORM_NARROW : 0);
 }
 
-template <int V>
-__global__ __launch_bounds__(256) void small_proj1_kernel(SmallDev d) { small_proj1_body<V>(d, (int)gridDim.x); }
+// (RES: single form only -- the batched forms refuse residual plans at bind, acm_small_batch_host.h)
+template <int V, bool RES>
+__global__ __launch_bounds__(256) void small_proj1_kernel(SmallDev d) { small_proj1_body<V, RES>(d, (int)gridDim.x); }
 template <int V>
 __global__ __launch_bounds__(256) void small_proj1_batch_kernel(const SmallBatchEntry* table, int form) {
     int n_wg;
     const ACM_CONST_AS SmallBatchEntry* e = batch_entry<0, V>(table, form, n_wg);
     if (!e) return;
     const ACM_CONST_AS SmallDev& d = e->first;
-    small_proj1_body<V>(d, n_wg);
+    small_proj1_body<V, false>(d, n_wg);
 }
 
-template <int V, bool FOUR, bool VARIANT>
+template <int V, bool FOUR, bool VARIANT, bool RES>
 __global__ __launch_bounds__(64 * WAVES) void small_conv1_fwd_kernel(SmallDev d, const float* z1) {
-    small_conv1_fwd_body<V, FOUR, VARIANT>(d, z1, (int)gridDim.x);
+    small_conv1_fwd_body<V, FOUR, VARIANT, RES>(d, z1, (int)gridDim.x);
 }
 template <int V, bool FOUR, bool VARIANT>
 __global__ __launch_bounds__(64 * WAVES) void small_conv1_fwd_batch_kernel(const SmallBatchEntry* table, int form) {
@@ -1198,7 +1351,7 @@ __global__ __launch_bounds__(64 * WAVES) void small_conv1_fwd_batch_kernel(const
     const ACM_CONST_AS SmallBatchEntry* e = batch_entry<1, V>(table, form, n_wg);
     if (!e) return;
     const ACM_CONST_AS SmallDev& d = e->rest;
-    small_conv1_fwd_body<V, FOUR, VARIANT>(d, d.Z1, n_wg);
+    small_conv1_fwd_body<V, FOUR, VARIANT, false>(d, d.Z1, n_wg);
 }
 
 template <bool FOUR>
@@ -1212,9 +1365,9 @@ __global__ __launch_bounds__(64 * WAVES) void small_conv2_fwd_batch_kernel(const
     small_conv2_fwd_body<FOUR>(d, n_wg);
 }
 
-template <int V, bool FOUR>
+template <int V, bool FOUR, bool RES>
 __global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_kernel(SmallDev d, const float* z1) {
-    small_conv2_bwd_body<V, FOUR>(d, z1, (int)gridDim.x);
+    small_conv2_bwd_body<V, FOUR, RES>(d, z1, (int)gridDim.x);
 }
 template <int V, bool FOUR>
 __global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_batch_kernel(const SmallBatchEntry* table, int form) {
@@ -1222,7 +1375,7 @@ __global__ __launch_bounds__(64 * WAVES) void small_conv2_bwd_batch_kernel(const
     const ACM_CONST_AS SmallBatchEntry* e = batch_entry<3, V>(table, form, n_wg);
     if (!e) return;
     const ACM_CONST_AS SmallDev& d = e->rest;
-    small_conv2_bwd_body<V, FOUR>(d, d.Z1, n_wg);
+    small_conv2_bwd_body<V, FOUR, false>(d, d.Z1, n_wg);
 }
 
 template <int V, bool FOUR, bool VARIANT>
@@ -1238,8 +1391,10 @@ __global__ __launch_bounds__(64 * WAVES) void small_conv1_bwd_batch_kernel(const
     small_conv1_bwd_body<V, FOUR, VARIANT>(d, d.Z1, n_wg);
 }
 
-template <int V>
-__global__ __launch_bounds__(256) void small_finish_kernel(SmallDev d, int item_blocks, int red_blocks) { small_finish_body<V>(d, item_blocks, red_blocks); }
+template <int V, bool RES>
+__global__ __launch_bounds__(256) void small_finish_kernel(SmallDev d, int item_blocks, int red_blocks) {
+    small_finish_body<V, RES>(d, item_blocks, red_blocks);
+}
 // Three waves per SIMD like the single form.  Left alone the compiler takes 172 registers here (the single form: 168, the
 // limit for three waves) and drops to two; held to three it parks loop-invariant addresses in scratch (stored once per
 // wave, read back once per work item).  EXPERIMENTS.md has the table.
@@ -1253,7 +1408,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void s
     const int item_blocks = e->item_blocks;
     if (item_blocks + red_blocks != n_wg) return;
     const ACM_CONST_AS SmallDev& d = e->rest;
-    small_finish_body<V>(d, item_blocks, red_blocks);
+    small_finish_body<V, false>(d, item_blocks, red_blocks);
 }
 
 ItemView view_of(const acm_csr* a) {
@@ -1268,11 +1423,15 @@ ItemView view_of(const acm_csr* a) {
 
 struct Layout {
     size_t Z1, H1, ST1, OUT1, T2, Z2I, G2, DZ2, G1, DZ1, slots, part3, part4, W2T, FACT, latch, long3, long4, counters, total;
+    size_t WXT, R, XX, DR;                 // residual plans only
 };
 
 // The carve-up is the widest width's at every width (acm_small_step_workspace_bytes takes no shape): a narrower step uses
 // the front of each block at its own pitch.  One function for the single and the batched form: they carve identically.
-Layout layout_of(const acm_csr* a, const acm_csr* x, const acm_csr* xt) {
+// `residual`: the residual branch's blocks are carved BEHIND the others (a plan without it allocates what it always did):
+// the W_X^T table, R / xX / dR, and -- each a size larger than its namesake above, which then lies unused -- slots of four
+// sums, partials and long-row records with db_X.
+Layout layout_of(const acm_csr* a, const acm_csr* x, const acm_csr* xt, bool residual = false, int64_t f_in = 0) {
     constexpr int F = F_MAX, PART4 = part4_of(F_MAX), LONG4 = PART4;
     static_assert(SLOT_PITCH == 192 && 3 * F == 192 && 4 * F == 256, "the block sizes below are written out for F_MAX = 64");
     const size_t n = (size_t)a->n_rows;
@@ -1293,9 +1452,16 @@ Layout layout_of(const acm_csr* a, const acm_csr* x, const acm_csr* xt) {
     L.slots = take((n_slots + 1) * 192);
     const size_t wg = (size_t)std::min<int64_t>(MAX_WG, (a->n_items + WAVES - 1) / WAVES);      // = the gather phases' grid
     L.part3 = take(wg * PART3_PITCH), L.part4 = take(wg * PART4);
-    L.W2T = take(3 * F * C8), L.FACT = take(2 * ACM_SMALL_ROLES * 2), L.latch = take(4);
+    L.W2T = take(3 * F * C8), L.FACT = take(2 * DEV_ROLES * 2), L.latch = take(4);
     L.long3 = take((size_t)a->n_long * PART3_PITCH + 64), L.long4 = take((size_t)a->n_long * LONG4 + 64);
     L.counters = take(n_long + 64);
+    L.WXT = L.R = L.XX = L.DR = 0;
+    if (residual) {
+        constexpr int PART4R = part4_of(F_MAX, true);
+        L.WXT = take((size_t)f_in * F), L.R = take(n * 64), L.XX = take(n * 64), L.DR = take(n * 64);
+        L.slots = take((n_slots + 1) * SLOT_PITCH_RES);
+        L.part4 = take(wg * PART4R), L.long4 = take((size_t)a->n_long * PART4R + 64);
+    }
     L.total = o * sizeof(float);
     return L;
 }
@@ -1308,6 +1474,18 @@ extern "C" int acm_small_step_workspace_bytes(const acm_csr_t* a_low, const acm_
     return ACM_OK;
 }
 
+extern "C" int acm_small_step_workspace_bytes_for(const acm_csr_t* a_low, const acm_csr_t* x, const acm_csr_t* x_t, const acm_small_step_t* shape,
+                                                  size_t* bytes) {
+    ACM_REQUIRE(a_low && shape && bytes, ACM_EINVAL, "acm_small_step_workspace_bytes_for: NULL argument");
+    ACM_REQUIRE(shape->residual == 0 || shape->residual == 1, ACM_EINVAL, "acm_small_step_workspace_bytes_for: residual must be 0 or 1 (got %d)",
+                (int)shape->residual);
+    ACM_REQUIRE(shape->f_in >= 0, ACM_EINVAL, "acm_small_step_workspace_bytes_for: f_in %d", (int)shape->f_in);
+    *bytes = layout_of(a_low, x, x_t, shape->residual != 0, shape->f_in).total;
+    return ACM_OK;
+}
+
+extern "C" int acm_small_step_has_residual(void) { return 1; }
+
 namespace {
 
 // The grids of the six launches: functions of the handles and the hidden width alone -- the same for every slot of a batch on
@@ -1316,8 +1494,8 @@ namespace {
 struct Grids {
     int proj, wide, graph, item_blocks, red_blocks;
 };
-Grids grids_of(const acm_csr* a, const acm_csr* x, const acm_csr* xt, bool train, int hidden) {
-    const int PART4 = part4_of(hidden);
+Grids grids_of(const acm_csr* a, const acm_csr* x, const acm_csr* xt, bool train, int hidden, bool residual = false) {
+    const int PART4 = part4_of(hidden, residual);
     Grids g;
     g.proj = std::max((int)std::min<int64_t>(2 * MAX_WG, (x->n_items + 3) / 4), 1);
     g.graph = (int)std::min<int64_t>(MAX_WG, (a->n_items + WAVES - 1) / WAVES);
@@ -1332,6 +1510,11 @@ Grids grids_of(const acm_csr* a, const acm_csr* x, const acm_csr* xt, bool train
 int small_prepare(const acm_csr* a, const acm_csr* x, const acm_csr* xt, const acm_small_step_t* p, SmallDev& d1, SmallDev& d) {
     ACM_REQUIRE(a && p, ACM_EINVAL, "acm_small_step: NULL argument");
     ACM_REQUIRE(acm_small_hidden_ok(p->hidden), ACM_EUNSUPPORTED, "acm_small_step: hidden width %d (32 or 64; 0 means 64)", (int)p->hidden);
+    ACM_REQUIRE(p->residual == 0 || p->residual == 1, ACM_EINVAL, "acm_small_step: residual must be 0 or 1 (got %d)", (int)p->residual);
+    const bool res = p->residual != 0;
+    if (res)
+        ACM_REQUIRE(p->res[0].param && p->res[1].param, ACM_EINVAL,
+                    "acm_small_step: residual without its parameters (res[0]: the Linear's weight, res[1]: its bias)");
     ACM_REQUIRE(a->vals == nullptr && a->n_rows == a->n_cols, ACM_EUNSUPPORTED,
                 "acm_small_step: pattern-only square operators only (acm_csr_create with vals = NULL)");
     ACM_REQUIRE(a->n_rows >= 1 && a->n_rows <= 16384, ACM_EUNSUPPORTED, "acm_small_step: 1 .. 16384 rows (got %lld)", (long long)a->n_rows);
@@ -1347,7 +1530,7 @@ int small_prepare(const acm_csr* a, const acm_csr* x, const acm_csr* xt, const a
         ACM_REQUIRE(xt && p->xt_src_pos && xt->n_rows == p->f_in && xt->n_cols == a->n_rows, ACM_EINVAL,
                     "acm_small_step: the transposed feature handle (x_t, xt_src_pos) is needed for dW1");
     }
-    const Layout L = layout_of(a, x, p->train ? xt : nullptr);
+    const Layout L = layout_of(a, x, p->train ? xt : nullptr, res, p->f_in);
     ACM_REQUIRE(p->workspace_bytes >= L.total, ACM_ESHAPE, "acm_small_step: workspace of %zu bytes, %zu needed", p->workspace_bytes, L.total);
     // required roles
     for (int l = 0; l < 2; ++l) {
@@ -1375,6 +1558,14 @@ int small_prepare(const acm_csr* a, const acm_csr* x, const acm_csr* xt, const a
             if (p->train && p->update) ACM_REQUIRE(t.m && t.v && t.step, ACM_EINVAL, "acm_small_step: layer %d role %d lacks Adam state", l, r);
             if (p->train && !p->update) ACM_REQUIRE(t.g, ACM_EINVAL, "acm_small_step: layer %d role %d has no gradient buffer (update = 0)", l, r);
         }
+    if (res)
+        for (int r = 0; r < 2; ++r) {
+            const acm_adam_tensor_t& s = p->res[r];
+            SmallTensor& t = d.t[0][SR_RES_W + r];
+            t.p = s.param, t.g = const_cast<float*>(s.grad), t.m = s.exp_avg, t.v = s.exp_avg_sq, t.step = s.step;
+            if (p->train && p->update) ACM_REQUIRE(t.m && t.v && t.step, ACM_EINVAL, "acm_small_step: residual tensor %d lacks Adam state", r);
+            if (p->train && !p->update) ACM_REQUIRE(t.g, ACM_EINVAL, "acm_small_step: residual tensor %d has no gradient buffer (update = 0)", r);
+        }
     d.graph = view_of(a), d.x = view_of(x), d.xt = view_of(p->train ? xt : nullptr);
     d.x_vals = p->x_vals, d.xt_src_pos = p->xt_src_pos, d.row_scale = p->row_scale;
     d.labels = p->labels, d.row_weight = p->row_weight, d.loss = p->loss, d.logits = p->logits, d.att1 = p->att1, d.att2 = p->att2;
@@ -1387,11 +1578,17 @@ int small_prepare(const acm_csr* a, const acm_csr* x, const acm_csr* xt, const a
     d.latch = reinterpret_cast<int64_t*>(ws + L.latch);
     d.counters = (int*)(ws + L.counters);
     d.drop_in = p->drop_in, d.drop_hidden = p->drop_hidden;
+    d.residual = res ? 1 : 0;
+    if (res) {
+        d.WXT = ws + L.WXT, d.R = ws + L.R, d.XX = ws + L.XX, d.DR = ws + L.DR;
+        d.drop_res = p->drop_res;
+    }
     d.hp = AdamScalars{p->lr, p->beta1, p->beta2, p->eps, p->weight_decay, p->decoupled};
     d.also_advance = p->also_advance, d.arrive = p->arrive;
     d1 = d;                                        // launch 1 reads the live dropout counter and latches it for the others
     if (d.drop_in.p > 0.f) d.drop_in.step = d.latch;
     if (d.drop_hidden.p > 0.f) d.drop_hidden.step = d.latch;
+    if (res && d.drop_res.p > 0.f) d.drop_res.step = d.latch;
     d.nwg3 = d.nwg4 = grids_of(a, x, xt, p->train != 0, acm_small_hidden_of(p)).graph;
     return ACM_OK;
 }
@@ -1403,6 +1600,7 @@ int batch_shape_check(const acm_csr* a, const acm_csr* x, const acm_csr* xt, int
                 ACM_SMALL_BATCH_MAX);
     ACM_REQUIRE(a && x && shape, ACM_EINVAL, "acm_small_batch: NULL argument");
     ACM_REQUIRE(acm_small_hidden_ok(shape->hidden), ACM_EUNSUPPORTED, "acm_small_batch: hidden width %d (32 or 64; 0 means 64)", (int)shape->hidden);
+    ACM_REQUIRE(shape->residual == 0, ACM_EUNSUPPORTED, "acm_small_batch: residual plans run as single steps only (residual = %d)", (int)shape->residual);
     ACM_REQUIRE(shape->n_channels == 3 || shape->n_channels == 4, ACM_EINVAL, "acm_small_batch: n_channels must be 3 or 4");
     ACM_REQUIRE(a->n_rows >= 1 && a->n_rows <= 16384 && a->vals == nullptr && a->n_rows == a->n_cols, ACM_EUNSUPPORTED,
                 "acm_small_batch: pattern-only square operators of 1 .. 16384 rows");
@@ -1423,25 +1621,29 @@ extern "C" int acm_small_step(const acm_csr_t* a, const acm_csr_t* x, const acm_
     const float* z1 = d.Z1;
     hipStream_t s = (hipStream_t)stream;
     const int hidden = acm_small_hidden_of(p);
-    const Grids gr = grids_of(a, x, xt, p->train != 0, hidden);
+    const Grids gr = grids_of(a, x, xt, p->train != 0, hidden, d.residual != 0);
     const int graph_wg = gr.graph, wide_wg = gr.wide;
-    const int picked = acm_pick([&](auto v, auto four, auto variant) {
+    const int picked = acm_pick([&](auto v, auto four, auto variant, auto res) {
+        // launch 0 (residual plans): the W_X^T table of this call
+        if (res())
+            hipLaunchKernelGGL(small_wxt_kernel, dim3((d.f_in + TR - 1) / TR, (hidden + TR - 1) / TR), dim3(256), 0, s,
+                               (const float*)d.t[0][SR_RES_W].p, d.WXT, d.f_in, hidden);
         // launch 1
-        hipLaunchKernelGGL(small_proj1_kernel<v()>, dim3(gr.proj), dim3(256), 0, s, d1);
+        hipLaunchKernelGGL((small_proj1_kernel<v(), res()>), dim3(gr.proj), dim3(256), 0, s, d1);
         // launch 2
-        hipLaunchKernelGGL((small_conv1_fwd_kernel<v(), four(), variant()>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
+        hipLaunchKernelGGL((small_conv1_fwd_kernel<v(), four(), variant(), res()>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
         // launch 3
         hipLaunchKernelGGL(small_conv2_fwd_kernel<four()>, dim3(graph_wg), dim3(64 * WAVES), 0, s, d);
         if (p->train) {
             // launch 4
-            hipLaunchKernelGGL((small_conv2_bwd_kernel<v(), four()>), dim3(graph_wg), dim3(64 * WAVES), 0, s, d, z1);
+            hipLaunchKernelGGL((small_conv2_bwd_kernel<v(), four(), res()>), dim3(graph_wg), dim3(64 * WAVES), 0, s, d, z1);
             // launch 5
             hipLaunchKernelGGL((small_conv1_bwd_kernel<v(), four(), variant()>), dim3(wide_wg), dim3(64 * WAVES), 0, s, d, z1);
             // launch 6
-            hipLaunchKernelGGL(small_finish_kernel<v()>, dim3(gr.item_blocks + gr.red_blocks), dim3(256), 0, s, d, gr.item_blocks, gr.red_blocks);
+            hipLaunchKernelGGL((small_finish_kernel<v(), res()>), dim3(gr.item_blocks + gr.red_blocks), dim3(256), 0, s, d, gr.item_blocks, gr.red_blocks);
         }
         return ACM_OK;
-    }, acm_one_of<2, 4>(hidden / 16), acm_flag(p->n_channels == 4), acm_flag(p->relu_before != 0));
+    }, acm_one_of<2, 4>(hidden / 16), acm_flag(p->n_channels == 4), acm_flag(p->relu_before != 0), acm_flag(d.residual != 0));
     ACM_REQUIRE(picked != ACM_NO_INSTANTIATION, ACM_EUNSUPPORTED, "acm_small_step: no kernels for hidden width %d", hidden);
     ACM_CHECK_HIP(hipGetLastError());
     return ACM_OK;
@@ -1594,6 +1796,7 @@ extern "C" int acm_small_batch_step_graphs(int32_t n_slots, const acm_small_step
                 ACM_SMALL_BATCH_MAX);
     ACM_REQUIRE(shape && grids && table, ACM_EINVAL, "acm_small_batch_step_graphs: NULL argument");
     ACM_REQUIRE(acm_small_hidden_ok(shape->hidden), ACM_EUNSUPPORTED, "acm_small_batch: hidden width %d (32 or 64; 0 means 64)", (int)shape->hidden);
+    ACM_REQUIRE(shape->residual == 0, ACM_EUNSUPPORTED, "acm_small_batch: residual plans run as single steps only (residual = %d)", (int)shape->residual);
     ACM_REQUIRE(shape->n_channels == 3 || shape->n_channels == 4, ACM_EINVAL, "acm_small_batch: n_channels must be 3 or 4");
     const Grids gr = envelope_of(*grids);
     const int PART4 = part4_of(acm_small_hidden_of(shape));

@@ -54,6 +54,13 @@ inline int acm_small_batch_check_slots_impl(int n_slots, const acm_small_step_t*
         snprintf(msg, msg_len, "acm_small_batch: every slot is empty");
         return ACM_EINVAL;
     }
+    // the batched kernels have no residual form (ACM-GCN++ runs as single steps): refused here, before any launch
+    for (int i = first; i < n_slots; ++i)
+        if (slots[i] && slots[i]->residual != 0) {
+            snprintf(msg, msg_len, "acm_small_batch: slot %d has the residual branch set (residual = %d): residual plans run as single steps only",
+                     i, (int)slots[i]->residual);
+            return ACM_EUNSUPPORTED;
+        }
     const acm_small_step_t* s = slots[first];
     for (int i = first + 1; i < n_slots; ++i) {
         const acm_small_step_t* p = slots[i];

@@ -137,8 +137,8 @@ def _fused_step_refusal(model, optimizer, features, labels, criterion, dataset_n
 def install_fused_train_step():
     """Bind ``utils.train_model`` -- the training step of ACM-Pytorch/train.py (utils.py:547-574: model.train(), zero_grad,
     forward, log_softmax + NLLLoss on the training rows, accuracy, backward, optimizer.step()) -- to this package's fused
-    small-graph step (train.TrainStep -> small.SmallPlan: the whole step as six launches behind one C-ABI call) WHERE IT
-    APPLIES: a two-layer acmgcn / acmgcnp model of hidden width 32 or 64 on a graph of <= 16 384 nodes with bag-of-words features,
+    small-graph step (train.TrainStep -> small.SmallPlan: the whole step as six launches behind one C-ABI call; seven for acmgcnpp) WHERE IT
+    APPLIES: a two-layer acmgcn / acmgcnp / acmgcnpp (init_layers_X = 1) model of hidden width 32 or 64 on a graph of <= 16 384 nodes with bag-of-words features,
     ``nn.NLLLoss()``, the launcher's FusedAdam.  Same signature, same return value (100 * training accuracy, training
     loss -- both of the training-mode forward, as in the reference), parameters and optimizer state updated as
     ``optimizer.step()`` leaves them.  What differs, on purpose: the dropout masks are the library's counter-based ones

@@ -1,5 +1,5 @@
-"""The training step / evaluation pass of the two-layer ACM model on a SMALL graph as six (three) launches behind ONE
-C-ABI call (``acm_small_step``, include/acm_hip.h; kernels: csrc/acm_small.hip).
+"""The training step / evaluation pass of the two-layer ACM model on a SMALL graph as six (three) launches -- seven (four)
+for ACM-GCN++, whose residual branch adds a prologue launch -- behind ONE C-ABI call (``acm_small_step``, include/acm_hip.h; kernels: csrc/acm_small.hip).
 
 Caller side of ACM-Pytorch/train.py:95-139 + utils.py:547-574 (and ACM-Geometric/train.py:119-140 on small data sets):
 ``train.TrainStep`` / ``train.EvalStep`` build a :class:`SmallPlan` when :func:`SmallPlan.why_not` finds nothing against it
@@ -8,7 +8,9 @@ autograd graph, no per-kernel Python dispatch, parameters updated in place by th
 (the optimizer's own ``state`` tensors are used, so ``state_dict`` / checkpoints / a later switch to the general path see
 exactly what ``optimizer.step()`` would have left).
 
-Envelope: ``GCN`` of model_type acmgcn | acmgcnp, two layers, hidden width 32 or 64, <= 8 classes, <= 16384 nodes, pattern-only
+Envelope: ``GCN`` of model_type acmgcn | acmgcnp | acmgcnpp (the last with ``init_layers_X = 1``: one Linear with bias of the
+hidden width as the residual branch; deeper ``mlpX`` stacks stay on the general path, and so do acmgcnpp runs in the batched
+forms below), two layers, hidden width 32 or 64, <= 8 classes, <= 16384 nodes, pattern-only
 operators on one device, CSR features (``graph.SparseFeatures``, or dense features the model's ``auto_csr`` turns into one),
 counter-based dropout (or none), this package's FusedAdam / FusedAdamW with one parameter group.  Anything else stays on
 the general path (``why_not`` says why).
@@ -35,6 +37,22 @@ def hidden_widths(lib=None):
     if probe is None:
         return (64,)
     return tuple(w for w in HIDDEN if probe(w))
+
+def has_residual(lib=None):
+    """Whether the loaded library's small step runs the ACM-GCN++ residual branch (``acm_small_step_has_residual``).  The CPU
+    test double (tests/fake_lib.py) lacks the symbol and is never offered an acmgcnpp plan."""
+    probe = getattr(lib if lib is not None else _lib.load(), "acm_small_step_has_residual", None)
+    return bool(probe is not None and probe())
+
+
+# the residual branch's two tensors: acm_small_step_t.res[k], and the names their gradients go by in plan.grads
+_RES_NAMES = ("weight", "bias")
+
+
+def _res_params(model):
+    lin = model.mlpX.lins[0]
+    return lin.weight, lin.bias
+
 
 _ROLE_NAMES = {
     _lib.SR_W_LOW: "weight_low", _lib.SR_W_HIGH: "weight_high", _lib.SR_W_MLP: "weight_mlp",
@@ -97,12 +115,25 @@ class SmallPlan:
         from .optim import _FusedAdamBase
         if tuning.HOST.small_step <= 0:
             return "switched off (tuning small_step=0)"
-        if getattr(model, "model_type", None) not in ("acmgcn", "acmgcnp"):
-            return f"model_type {getattr(model, 'model_type', None)!r} (acmgcn | acmgcnp)"
+        if getattr(model, "model_type", None) not in ("acmgcn", "acmgcnp", "acmgcnpp"):
+            return f"model_type {getattr(model, 'model_type', None)!r} (acmgcn | acmgcnp | acmgcnpp)"
         gcns = getattr(model, "gcns", None)
         if gcns is None or len(gcns) != 2:
             return "not a two-layer model"
         l0, l1 = gcns
+        residual = model.model_type == "acmgcnpp"
+        if residual:
+            if not has_residual():
+                return "model_type 'acmgcnpp' (acmgcn | acmgcnp): library without the residual step"
+            lins = getattr(getattr(model, "mlpX", None), "lins", None)
+            if lins is None or len(lins) != 1:
+                return f"mlpX with {len(lins) if lins is not None else 0} Linears (init_layers_X = 1 only)"
+            lin = lins[0]
+            if lin.bias is None:
+                return "mlpX Linear without bias"
+            if lin.in_features != l0.in_features or lin.out_features != l0.out_features:
+                return (f"mlpX Linear {lin.in_features} -> {lin.out_features} (the first layer is "
+                        f"{l0.in_features} -> {l0.out_features})")
         widths = hidden_widths()
         if l0.out_features not in widths or l1.in_features != l0.out_features:
             return f"hidden width {l0.out_features} ({' | '.join(map(str, widths))})"
@@ -146,6 +177,8 @@ class SmallPlan:
             for layer, cfg in ((l0, c0), (l1, c1)):
                 if any(id(_param(layer, r)) not in have for r in _roles(cfg)):
                     return "a parameter of the model is not in the optimizer's group"
+            if residual and any(id(t) not in have for t in _res_params(model)):
+                return "a parameter of mlpX is not in the optimizer's group"
         return None
 
     def __init__(self, model, x, ops, labels=None, weights=None, optimizer=None, update=True, keep_grads=False):
@@ -160,11 +193,20 @@ class SmallPlan:
         n, dev = ops.low.n_rows, x.values.device
         self.n, self.C, self.hidden = n, l1.out_features, l0.out_features
         self.train = labels is not None                 # labels + row weights: a training plan; neither: evaluation
+        self.residual = model.model_type == "acmgcnpp"  # (why_not has asked the library: has_residual)
         self._xt = x.csr_t if self.train else None
         self.low = self._operator(ops)
         nbytes = C.c_size_t()
-        _lib.check(lib.acm_small_step_workspace_bytes(self.low.handle, x.csr.handle, self._xt.handle if self._xt is not None else None,
-                                                      C.byref(nbytes)), "acm_small_step_workspace_bytes")
+        xt_handle = self._xt.handle if self._xt is not None else None
+        if self.residual:
+            # the residual's buffers lie behind the blocks every plan has: sized by the entry that takes the shape
+            shape = _lib.SmallStep()
+            shape.residual, shape.f_in, shape.hidden = 1, l0.in_features, l0.out_features
+            _lib.check(lib.acm_small_step_workspace_bytes_for(self.low.handle, x.csr.handle, xt_handle, C.byref(shape), C.byref(nbytes)),
+                       "acm_small_step_workspace_bytes_for")
+        else:
+            _lib.check(lib.acm_small_step_workspace_bytes(self.low.handle, x.csr.handle, xt_handle, C.byref(nbytes)),
+                       "acm_small_step_workspace_bytes")
         self.workspace = torch.zeros(nbytes.value // 4, dtype=_F32, device=dev)     # zero once: counters, pad columns
         self.logits = torch.empty(n, self.C, dtype=_F32, device=dev)
         self.att1 = torch.zeros(n, 4, dtype=_F32, device=dev)
@@ -179,12 +221,16 @@ class SmallPlan:
         # every width-dependent buffer of a plan is either the model's own (parameters, `grads` as zeros_like of them, the
         # optimizer's state) or sized for the widest width by the library (the workspace): the width is this one field
         p.hidden = self.hidden
+        p.residual = int(self.residual)
         self.update = bool(update) and self.train and optimizer is not None
         self.grads = {}
         if self.train and (keep_grads or not self.update):
             for li, layer in enumerate(model.gcns):
                 for role in _roles(cfg):
                     self.grads[(li, _ROLE_NAMES[role])] = torch.zeros_like(_param(layer, role))
+            if self.residual:
+                for name, t in zip(_RES_NAMES, _res_params(model)):
+                    self.grads[("mlpX", name)] = torch.zeros_like(t)
         p.scale, p.train, p.update = cfg.scale, int(self.train), int(self.update)
         p.f_in = l0.in_features
         p.x_vals = x.values.data_ptr()
@@ -228,33 +274,38 @@ class SmallPlan:
             cache[want] = CsrGraph.from_csr(ip, ix, None, low.n_cols, chunk=want)
         return cache[want]
 
-    def _bind_parameters(self):
+    def _tensors(self):
+        """(the struct's entry, the parameter, its key in ``grads``) of every tensor the step reads: the roles of the two
+        layers, then -- ACM-GCN++ -- the residual branch's weight and bias."""
         p = self.p
         for li, layer in enumerate(self.model.gcns):
             for role in _roles(self.cfg):
-                t = _param(layer, role)
-                e = p.t[li][role]
-                e.param, e.numel = t.data_ptr(), t.numel()
-                g = self.grads.get((li, _ROLE_NAMES[role]))
-                e.grad = g.data_ptr() if g is not None else None
-                if self.update:
-                    st = self.opt.state[t]
-                    if len(st) == 0:
-                        st["step"] = torch.zeros((), dtype=_F32, device=t.device)
-                        st["exp_avg"] = torch.zeros_like(t, memory_format=torch.preserve_format)
-                        st["exp_avg_sq"] = torch.zeros_like(t, memory_format=torch.preserve_format)
-                    else:
-                        self.opt._normalize_state(t, st)
-                    e.exp_avg, e.exp_avg_sq, e.step = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"].data_ptr()
+                yield p.t[li][role], _param(layer, role), (li, _ROLE_NAMES[role])
+        if self.residual:
+            for k, t in enumerate(_res_params(self.model)):
+                yield p.res[k], t, ("mlpX", _RES_NAMES[k])
+
+    def _bind_parameters(self):
+        for e, t, name in self._tensors():
+            e.param, e.numel = t.data_ptr(), t.numel()
+            g = self.grads.get(name)
+            e.grad = g.data_ptr() if g is not None else None
+            if self.update:
+                st = self.opt.state[t]
+                if len(st) == 0:
+                    st["step"] = torch.zeros((), dtype=_F32, device=t.device)
+                    st["exp_avg"] = torch.zeros_like(t, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(t, memory_format=torch.preserve_format)
+                else:
+                    self.opt._normalize_state(t, st)
+                e.exp_avg, e.exp_avg_sq, e.step = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"].data_ptr()
         self._bound = self._binding_key()
 
     def _binding_key(self):
         key = []
-        for layer in self.model.gcns:
-            for role in _roles(self.cfg):
-                t = _param(layer, role)
-                st = self.opt.state.get(t, {}) if self.update else {}
-                key.append((t.data_ptr(), st["exp_avg"].data_ptr() if st else 0, st["step"].data_ptr() if st else 0))
+        for _, t, _name in self._tensors():
+            st = self.opt.state.get(t, {}) if self.update else {}
+            key.append((t.data_ptr(), st["exp_avg"].data_ptr() if st else 0, st["step"].data_ptr() if st else 0))
         return tuple(key)
 
     def refresh_hyper(self):
@@ -274,8 +325,10 @@ class SmallPlan:
             if st is None:
                 raise RuntimeError("SmallPlan: the model has dropout but no dropout_state (counter-based dropout only)")
             p.drop_in, p.drop_hidden = st.spec(pd, 0, 0), st.spec(pd, 1, self.ops.row_offset)
+            # (tag 2: the mask the general path draws for the residual branch, models.GCN._forward_fused_dropout)
+            p.drop_res = st.spec(pd, 2, self.ops.row_offset) if self.residual else _lib.Dropout()
         else:
-            p.drop_in, p.drop_hidden = _lib.Dropout(), _lib.Dropout()
+            p.drop_in, p.drop_hidden, p.drop_res = _lib.Dropout(), _lib.Dropout(), _lib.Dropout()
 
     def stale(self):
         """A parameter or an optimizer state tensor was replaced (load_state_dict, .to()): bind again."""
@@ -296,6 +349,9 @@ class SmallPlan:
         for layer, att in ((l0, self.att1), (l1, self.att2)):
             layer._att_raw, layer._att_inv, layer._att_k = att, None, self.cfg.n_channels
         return self.loss if self.train else self.logits
+
+
+_BATCH_RESIDUAL = "residual plans (acmgcnpp) run as single steps: the batched launches have no residual form"
 
 
 class SmallBatch:
@@ -320,6 +376,8 @@ class SmallBatch:
         if len(plans) > _lib.SMALL_BATCH_MAX:
             return f"{len(plans)} plans (<= {_lib.SMALL_BATCH_MAX} slots)"
         first = plans[0]
+        if any(p.residual for p in plans):
+            return _BATCH_RESIDUAL
         for p in plans[1:]:
             if (p.cfg.n_channels, p.cfg.relu_before, p.cfg.layernorm, p.cfg.scale) != \
                     (first.cfg.n_channels, first.cfg.relu_before, first.cfg.layernorm, first.cfg.scale):
@@ -451,6 +509,8 @@ class SmallGraphBatch(SmallBatch):
         if len(plans) > _lib.SMALL_BATCH_MAX:
             return f"{len(plans)} plans (<= {_lib.SMALL_BATCH_MAX} slots)"
         first = plans[0]
+        if any(p.residual for p in plans):
+            return _BATCH_RESIDUAL
         for p in plans[1:]:
             if (p.cfg.n_channels, p.cfg.relu_before, p.cfg.layernorm, p.cfg.scale) != \
                     (first.cfg.n_channels, first.cfg.relu_before, first.cfg.layernorm, first.cfg.scale):

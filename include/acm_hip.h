@@ -1137,6 +1137,21 @@ int acm_adam_step(int32_t n_tensors, const acm_adam_tensor_t* tensors, const acm
  * With `update` the Adam / AdamW update of every parameter is applied where its gradient becomes final (same formulas
  * as acm_adam_step); without it the gradients are written to t[..].grad and nothing is updated.
  * `train = 0`: launches 1-3 only, forward (evaluation pass: logits, att).  Dense features: convert once (CSR copy).
+ *
+ * ACM-GCN++ (`residual` = 1; ACM-Pytorch/models/models.py:40-41,116-122,160-163 with init_layers_X = 1): layer 2 reads
+ * drop(relu(fea1)) + xX, xX = drop_res(relu(x_d W_X^T + b_X)).  SEVEN launches (evaluation: four):
+ *   0  W_X^T [f_in, F] from the Linear's [F, f_in] weight, tiled through LDS; rebuilt on every call (the optimizer, a
+ *      keep-best restore and load_state_dict rewrite the parameter through its pointer: no freshness signal to trust)
+ *   1  + R = drop(X) W_X^T as a fourth sum (slots of four sums for these plans), to its own [n, F] buffer
+ *   2  + xX = drop_res(relu(R + b_X)) stored; Z2 projects H + xX
+ *   4  + dW2 partial sums take H + xX; dR = dH through xX's dropout and ReLU, stored; db_X joins the partial sums
+ *   6  + dW_X[:, j] = sum_i x_d[i, j] dR[i, :] as a fourth table of the feature-row blocks, updated in the Linear's layout
+ *      (strided); b_X from the partial sums
+ * Launches 3 and 5 are the same kernels.  The batched forms below have no residual kernels: ACM_EUNSUPPORTED at bind.
+ * (Added under ABI 29: `residual` was a reserved zero and the new fields lie behind the old end of the block, read with
+ * `residual` alone, so a caller built against the block as it was is served as before.  The other way round there is no
+ * version number to catch a mistake: a caller that sets `residual = 1` must have allocated its block with the sizeof of THIS
+ * header -- `res` and `drop_res` are read behind what was the block's end.)
  */
 #define ACM_SMALL_ROLES 17
 enum {
@@ -1166,7 +1181,8 @@ typedef struct {
     const int32_t* xt_src_pos;  /* nnz(X): position in x_vals of every entry of the TRANSPOSED handle                */
     const float* xt_vals;       /* optional: x_vals in the transposed handle's order (x_vals[xt_src_pos[k]]), made once     */
     int32_t f_in;
-    int32_t reserved1;
+    int32_t residual;           /* 1: ACM-GCN++ -- the residual branch below (`res`, `drop_res`); 0: the step without it.  The
+                                   field was reserved1 and zero.  Anything else: ACM_EINVAL, before any launch         */
     acm_dropout_t drop_in;      /* on x_vals: element (position, 0)                                                  */
     acm_dropout_t drop_hidden;  /* on the hidden activations: element (row, column)                                  */
     const float* row_scale;     /* 1 / d_i                                                                           */
@@ -1181,11 +1197,24 @@ typedef struct {
     int32_t* arrive;            /* reserved (not read: the last launch needs no arrival barrier)                     */
     void*   workspace;          /* acm_small_step_workspace_bytes; ZERO-FILLED by the caller once, kept between calls */
     size_t  workspace_bytes;
+    /* ---- read with `residual` alone: a block that ends at workspace_bytes (a caller from before) is complete without it */
+    acm_adam_tensor_t res[2];   /* [0] mlpX.lins.0.weight, [F, f_in] row-major (the nn.Linear's own layout: the TRANSPOSE of
+                                   the [f_in, F] tables above); [1] its bias, [F].  Both required; state / grad as for t    */
+    acm_dropout_t drop_res;     /* on relu(x_d W_X^T + b_X): element (row, column), the tag of the residual branch (2)     */
 } acm_small_step_t;
 
 /* The workspace of one run.  No shape argument: the size is the one hidden width 64 needs, an upper bound for width 32
  * (a 32-wide step uses the front of each block of the same carve-up). */
 int acm_small_step_workspace_bytes(const acm_csr_t* a_low, const acm_csr_t* x, const acm_csr_t* x_t, size_t* bytes);
+/* The same with the block's shape: reads shape->residual and shape->f_in.  Without the residual the size above; with it the
+ * residual's buffers (W_X^T [f_in, 64], R / xX / dR [n, 64], slots of four sums, partial sums with db_X) lie BEHIND the
+ * blocks of the size above.  A residual step on a smaller workspace: ACM_ESHAPE. */
+int acm_small_step_workspace_bytes_for(const acm_csr_t* a_low, const acm_csr_t* x, const acm_csr_t* x_t, const acm_small_step_t* shape,
+                                       size_t* bytes);
+/* 1 if acm_small_step runs the residual branch (acm_small_step_t::residual).  The Python host asks before it offers an
+ * acmgcnpp model, as it asks acm_small_step_has_hidden for a width: the CPU test double lacks the symbol and is never
+ * offered one. */
+int acm_small_step_has_residual(void);
 /* x / x_t: CSR handles of the features and of their transpose (pattern; values come from p->x_vals; x_t may be NULL with
  * train = 0).  Errors: ACM_EUNSUPPORTED outside the envelope (explicit values, > 8 classes, > 16384 rows, a hidden width
  * other than 32 or 64, ...). */
